@@ -33,7 +33,8 @@
 extern "C" {
 #endif
 
-/* 6 (round 6): MRCA_F_HIT_BITS -- what a beam hit is a bit plane of its own, MRCA_F_SCAN_RING holds plain ranges (5: the sign
+/* 6, additive: mrca_lidar_features_bf16 (the bf16 MFMA front end of the opt-in bf16 rollout inference).
+ * 6 (round 6): MRCA_F_HIT_BITS -- what a beam hit is a bit plane of its own, MRCA_F_SCAN_RING holds plain ranges (5: the sign
  * bit of a ring entry); mrca_step_many's run-ahead schedule (chains < 0: the chained one).
  * 5 (round 5): mrca_policy_tail takes fc1_b_dev (may be NULL) after h1_dev; added since 4, all additive: mrca_step_worlds,
  * mrca_move_worlds, mrca_observe_worlds, mrca_step_many, mrca_adam_step, mrca_policy_heads(_backward), mrca_relu_cat(_backward), mrca_rollout_rows +
@@ -305,6 +306,17 @@ int mrca_lidar_features(const float* obs_dev, const uint8_t* obs_head_dev, int32
 int mrca_lidar_features_rows(const float* frames_dev, const int32_t* rows_dev, int32_t n_samples, int32_t frames, int32_t beams,
                              const float* w1_dev, const float* b1_dev, const float* w2_dev, const float* b2_dev, float* feat_dev,
                              void* stream);
+
+/* bf16 form of mrca_lidar_features (same inputs; frames 3, beams 512, else MRCA_ERR_UNSUPPORTED) on bf16 MFMAs
+ * (csrc/mrca_policy_bf16.hip), the front end of the opt-in bf16 rollout inference.  Rounding points, each round to nearest
+ * even: (1) the observation (raw ranges: x / 6 - 0.5 formed in fp32 as mrca_lidar_features does) to bf16; (2) w1, w2 to bf16,
+ * b1, b2 stay fp32 and are added to the fp32 accumulators; (3) h1 = relu(conv1 + b1) to bf16 (never leaves the CU);
+ * (4) feat = relu(conv2 + b2) to bf16.  feat_dev = bf16 bit patterns [2][N][4096] (tower-major, the flatten order of
+ * [32,128]); obs_dev, w1_dev, w2_dev and feat_dev 16-byte aligned (MRCA_ERR_INVALID otherwise).  Deterministic (no atomics).
+ * Arguments are validated before the first HIP call. */
+int mrca_lidar_features_bf16(const float* obs_dev, const uint8_t* obs_head_dev, int32_t raw_scans, int32_t n_robots,
+                             int32_t frames, int32_t beams, const float* w1_dev, const float* b1_dev, const float* w2_dev,
+                             const float* b2_dev, uint16_t* feat_dev, void* stream);
 
 /* The rest of the rollout inference behind fc1 in one kernel (model/net.py:41-55,61-70: ReLU, cat with goal and speed,
  * fc2 + ReLU of both towers, actor1 / actor2 / critic heads with sigmoid / tanh; model/ppo.py:57-82 generate_action:

@@ -31,6 +31,9 @@ EXPORTS = ["mrca_abi_version", "mrca_last_error", "mrca_arena_bytes", "mrca_crea
            "mrca_policy_heads", "mrca_policy_heads_backward_scratch", "mrca_policy_heads_backward", "mrca_relu_cat",
            "mrca_relu_cat_backward", "mrca_policy_heads_backward_bias", "mrca_relu_cat_backward_bias_scratch",
            "mrca_relu_cat_backward_bias"]
+# declared in include/mrca_env.h like the names above, listed apart: tests/test_abi.py's header scan reads names of letters
+# and underscores only (tests/test_policy_bf16_host.py checks these against the header and the library)
+EXPORTS_WITH_DIGITS = ["mrca_lidar_features_bf16"]
 
 
 class RolloutRows(C.Structure):
@@ -98,6 +101,7 @@ def load(path=None):
                              C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.mrca_lidar_features.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.mrca_lidar_features_bf16.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 6
     lib.mrca_lidar_features_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 6
     lib.mrca_lidar_features_backward_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 11 + \
         [C.c_size_t, C.c_void_p]

@@ -50,14 +50,15 @@ def staggered_roundabout_policy(num_robots, bias=1.4, near=3.5, vgain=0.8, stop=
     return fn
 
 
-def cnn_policy_fn(policy, fused=False, env=None):
-    """``fused`` with ``env``: the policy's HIP front end reads the env's frame ring in place (no materialised stacks)."""
+def cnn_policy_fn(policy, fused=False, env=None, fused_bf16=False):
+    """``fused`` with ``env``: the policy's HIP front end reads the env's frame ring in place (no materialised stacks).
+    ``fused_bf16``: the fused path's opt-in bf16 inference (needs ``fused``)."""
     def fn(obs, local_goal, speed):
         head = None
         if fused and env is not None:
             obs, head = ppo.policy_input(env, True)
         _mean, scaled = ppo.generate_action_no_sampling(policy, obs, local_goal, speed, ACTION_BOUND, fused=fused,
-                                                        obs_head=head)
+                                                        obs_head=head, fused_bf16=fused_bf16)
         return scaled
     fn.wants_obs = not (fused and env is not None)
     return fn
@@ -160,7 +161,11 @@ def main():
     ap.add_argument("--stage-resolution", action="store_true", help="fidelity mode: the map at Stage's own cell size "
                                                                       "(worlds/circle.world:3) -- the clearances a Stage-trained policy lives with")
     ap.add_argument("--fused", action="store_true", help="policy inference through the fp32 HIP conv front end")
+    ap.add_argument("--fused-bf16", action="store_true", help="policy inference through the bf16 MFMA front end and a bf16 "
+                                                              "fc1 (opt-in precision, not the reference's; implies --fused)")
     a = ap.parse_args()
+    if a.fused_bf16:
+        a.fused = True
     from .vec_env import VecStageWorld
     if a.robots == 50 and a.radius == 25.0:
         sc = scenario.circle(num_worlds=a.circles, seed=a.seed, stage_resolution=a.stage_resolution)
@@ -171,7 +176,7 @@ def main():
     if a.policy:
         pol = CNNPolicy(3, 2).to(env.device)
         pol.load_state_dict(torch.load(a.policy, map_location=env.device))
-        fn, name = cnn_policy_fn(pol, fused=a.fused, env=env), a.policy
+        fn, name = cnn_policy_fn(pol, fused=a.fused, env=env, fused_bf16=a.fused_bf16), a.policy
     else:
         fn, name = staggered_roundabout_policy(env.N), "staggered-roundabout stand-in (no checkpoint given)"
     perturb = tuple(float(v) for v in a.perturb.split(",")) if a.perturb else None
@@ -179,6 +184,7 @@ def main():
     out["policy"] = name
     out["robots_per_circle"], out["radius_m"] = a.robots, a.radius
     out["perturb_xy_th"], out["seed"], out["stage_resolution"] = perturb, a.seed, bool(a.stage_resolution)
+    out["inference_precision"] = ("bf16 (fused bf16 MFMA front end + bf16 fc1)" if a.fused_bf16 else "fp32") if a.policy else None
     print(json.dumps(out))
 
 

@@ -136,6 +136,14 @@ class CNNPolicy(nn.Module):
                     old[k].copy_(v)
             else:
                 self._rc = new
+            # the bf16 rollout path's copy of fc1 (built by its first call, _rollout_cache_bf16): refreshed in place too --
+            # but only where it exists, fp32 users never pay for it
+            bf = getattr(self, "_rc_bf16", None)
+            if bf is not None:
+                if bf.shape == self._rc["fc1_w"].shape and bf.device == self._rc["fc1_w"].device:
+                    bf.copy_(self._rc["fc1_w"])
+                else:
+                    self._rc_bf16 = self._rc["fc1_w"].to(torch.bfloat16)
             self._rc_stamp = self._param_stamp()
         return self._rc
 
@@ -155,16 +163,40 @@ class CNNPolicy(nn.Module):
             self.refresh_rollout_cache()
         return self._rc
 
-    def mean_value_fused(self, x, goal, speed, head=None):
+    def _rollout_cache_bf16(self):
+        """-> (the cache, fc1_w as bf16 [2, 4096, 256]).  The bf16 copy is made by the first bf16 call and from then on
+        kept in step, in place, by refresh_rollout_cache."""
+        rc = self._rollout_cache()
+        if getattr(self, "_rc_bf16", None) is None:
+            with torch.no_grad():
+                self._rc_bf16 = rc["fc1_w"].to(torch.bfloat16)
+        return rc, self._rc_bf16
+
+    def _fc1_bf16(self, x, rc, fc1_w_bf16, head):
+        """The bf16 front end (csrc/mrca_policy_bf16.hip) and fc1 as a bf16 x bf16 batched GEMM with fp32 accumulation and
+        an fp32 result, before bias and ReLU -> f32[2, N, 256]"""
+        from . import policy_ops
+        feat = policy_ops.lidar_features_bf16(x, rc["w1"], rc["b1"], rc["w2"], rc["b2"], head=head)    # bf16 [2, N, 4096]
+        return torch.bmm(feat, fc1_w_bf16, out_dtype=torch.float32)
+
+    def mean_value_fused(self, x, goal, speed, head=None, bf16=False):
         """mean_value for the rollout: the conv front end of BOTH towers in one HIP kernel (csrc/mrca_policy.hip,
         fp32 MFMA), fc1 / fc2 of both towers as batched fp32 GEMMs.  fp32 throughout; differs from mean_value by
         summation order only (tests/test_gpu_policy_ops.py: 1e-5).  No autograd.  ``head``: ``x`` is the env's frame
-        ring and head[n] the slot of robot n's newest frame (VecStageWorld.policy_obs())."""
+        ring and head[n] the slot of robot n's newest frame (VecStageWorld.policy_obs()).  ``bf16=True``: the opt-in bf16
+        inference -- the front end on bf16 MFMAs (csrc/mrca_policy_bf16.hip) and fc1 as a bf16 GEMM with fp32
+        accumulation; fc2 and the heads stay fp32."""
         from . import policy_ops
-        rc = self._rollout_cache()
+        if bf16:
+            rc, w_bf16 = self._rollout_cache_bf16()
+        else:
+            rc = self._rollout_cache()
         with torch.no_grad():
-            feat = policy_ops.lidar_features(x, rc["w1"], rc["b1"], rc["w2"], rc["b2"], head=head)   # [2, N, 4096]
-            h = torch.relu(torch.baddbmm(rc["fc1_b"], feat, rc["fc1_w"]))                      # [2, N, 256]
+            if bf16:
+                h = torch.relu(self._fc1_bf16(x, rc, w_bf16, head) + rc["fc1_b"])                 # [2, N, 256]
+            else:
+                feat = policy_ops.lidar_features(x, rc["w1"], rc["b1"], rc["w2"], rc["b2"], head=head)   # [2, N, 4096]
+                h = torch.relu(torch.baddbmm(rc["fc1_b"], feat, rc["fc1_w"]))                      # [2, N, 256]
             gs = torch.cat((goal, speed), dim=-1).unsqueeze(0).expand(2, -1, -1)
             h = torch.relu(torch.baddbmm(rc["fc2_b"], torch.cat((h, gs), dim=-1), rc["fc2_w"]))   # [2, N, 128]
             m = torch.addmm(rc["head_b"], h[0], rc["head_w"])
@@ -172,18 +204,26 @@ class CNNPolicy(nn.Module):
             v = self.critic(h[1])
         return mean, v
 
-    def act_fused(self, x, goal, speed, noise, lo, hi, head=None):
+    def act_fused(self, x, goal, speed, noise, lo, hi, head=None, bf16=False):
         """generate_action for the rollout in three launches: the conv front end of both towers (csrc/mrca_policy.hip),
         fc1 of both towers as one batched fp32 GEMM (a plain bmm: a baddbmm first copies the broadcast bias into its
         output, 8 MB and 7 us per tick at 4096 robots -- the tail adds the bias while it stages h1), and everything
         behind it -- bias, ReLU, cat, fc2, heads, sample, logprob, clip -- in csrc/mrca_policy_tail.hip.  ``noise`` f32[N,2] standard normal draws or None (mean action).
         -> value [N,1], action [N,2], logprob [N,1], scaled [N,2], mean [N,2].  fp32; differs from the stock path by
-        summation order only (tests/test_gpu_policy_ops.py)."""
+        summation order only (tests/test_gpu_policy_ops.py).  ``bf16=True``: the opt-in bf16 inference -- the front end on
+        bf16 MFMAs (csrc/mrca_policy_bf16.hip, bf16 features) and fc1 as a bf16 x bf16 batched GEMM with fp32 accumulation
+        and result; the tail is the same fp32 kernel (tests/test_gpu_policy_bf16.py)."""
         from . import policy_ops
-        rc = self._rollout_cache()
+        if bf16:
+            rc, w_bf16 = self._rollout_cache_bf16()
+        else:
+            rc = self._rollout_cache()
         with torch.no_grad():
-            feat = policy_ops.lidar_features(x, rc["w1"], rc["b1"], rc["w2"], rc["b2"], head=head)   # [2, N, 4096]
-            h1 = torch.bmm(feat, rc["fc1_w"])                                        # [2, N, 256], before bias and ReLU
+            if bf16:
+                h1 = self._fc1_bf16(x, rc, w_bf16, head)                                # [2, N, 256] fp32, before bias and ReLU
+            else:
+                feat = policy_ops.lidar_features(x, rc["w1"], rc["b1"], rc["w2"], rc["b2"], head=head)   # [2, N, 4096]
+                h1 = torch.bmm(feat, rc["fc1_w"])                                        # [2, N, 256], before bias and ReLU
             return policy_ops.policy_tail(h1, goal.contiguous(), speed.contiguous(), rc["fc2_w"], rc["fc2_b"], rc["head_w"],
                                           rc["head_b"], rc["critic_w"], rc["critic_b"], rc["logstd"], noise, lo, hi,
                                           fc1_b=rc["fc1_b"])

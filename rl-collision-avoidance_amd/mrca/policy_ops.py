@@ -128,6 +128,38 @@ def lidar_features(obs, w1, b1, w2, b2, out=None, head=None):
     return out
 
 
+def lidar_features_bf16(obs, w1, b1, w2, b2, out=None, head=None):
+    """lidar_features on bf16 MFMAs (csrc/mrca_policy_bf16.hip): same arguments (fp32 weights, tower-major), returns
+    bf16[2,N,4096].  Rounding points (include/mrca_env.h: mrca_lidar_features_bf16): the observation, w1, w2, h1 and the
+    output are rounded to bf16 (nearest even); the biases are added in fp32.  Rollout inference only: a FrameTable (the
+    update's row-table form) is refused."""
+    lib = _lib.load()
+    if isinstance(obs, FrameTable):
+        raise ValueError("lidar_features_bf16: inference only -- a FrameTable (the update path) is not supported")
+    head, raw = unwrap_head(head)
+    if obs.dim() != 3:
+        raise ValueError(f"lidar_features_bf16: expected obs of shape [N, 3, 512], got {tuple(obs.shape)}")
+    N, F, B = obs.shape
+    for t, shape in ((obs, (N, 3, 512)), (w1, (2, 32, 3, 5)), (b1, (2, 32)), (w2, (2, 32, 32, 3)), (b2, (2, 32))):
+        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape):
+            raise ValueError(f"lidar_features_bf16: expected a contiguous cuda float32 tensor of shape {shape}, got "
+                             f"{tuple(t.shape)} {t.dtype} {t.device}")
+    if head is not None and not (head.is_cuda and head.dtype == torch.uint8 and head.is_contiguous() and head.numel() == N):
+        raise ValueError("lidar_features_bf16: head must be a contiguous cuda uint8 tensor with one entry per robot")
+    if out is None:
+        out = torch.empty(2, N, 4096, dtype=torch.bfloat16, device=obs.device)
+    elif not (out.is_cuda and out.dtype == torch.bfloat16 and out.is_contiguous() and tuple(out.shape) == (2, N, 4096)
+              and out.device == obs.device and out.data_ptr() % 16 == 0):
+        raise ValueError("lidar_features_bf16: out must be a contiguous 16-byte aligned cuda bfloat16 tensor [2, N, 4096] "
+                         "on obs' device")
+    with torch.cuda.device(obs.device):
+        stream = C.c_void_p(torch.cuda.current_stream(obs.device).cuda_stream)
+        _lib.check(lib.mrca_lidar_features_bf16(obs.data_ptr(), None if head is None else head.data_ptr(), int(raw), N, F, B,
+                                                w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), out.data_ptr(),
+                                                stream), "mrca_lidar_features_bf16")
+    return out
+
+
 def policy_tail(h1, goal, speed, fc2_w, fc2_b, head_w, head_b, critic_w, critic_b, logstd, noise, lo, hi, fc1_b=None):
     """Everything of the rollout inference behind fc1 in one launch (include/mrca_env.h: mrca_policy_tail).
     h1 f32[2,N,256] = fc1 outputs before the ReLU -- with their bias, or without it and ``fc1_b`` f32[2,256] (any shape

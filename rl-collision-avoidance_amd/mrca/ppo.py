@@ -26,26 +26,29 @@ def _bounds(action_bound, device, dtype):
 
 # ---------------------------------------------------------------------------------------------
 def generate_action(policy, obs, goal, speed, action_bound, generator=None, autocast_dtype=None, fused=False,
-                    obs_head=None, noise=None):
+                    obs_head=None, noise=None, fused_bf16=False):
     """model/ppo.py:57-82: sample a ~ N(mean, std); the UNclipped action and its logprob are what
     the buffer stores, the clipped one drives the robot.  ``fused=True`` evaluates the policy through its fp32
     rollout path (HIP conv front end + batched GEMMs, net.CNNPolicy.mean_value_fused; same numbers to 1e-5);
     ``autocast_dtype=torch.bfloat16`` runs the stock towers on the bf16 MFMA path (opt-in).  ``obs_head`` (fused
     only): ``obs`` is the env's frame ring, see ``policy_input``.  ``noise`` f32[N,2]: standard normal draws made by the
     caller (a rollout replayed as a hipGraph of several ticks draws all of them in one launch) instead of a ``randn``
-    here."""
+    here.  ``fused_bf16=True`` (with ``fused``): the fused path's opt-in bf16 inference (bf16 MFMA front end and fc1,
+    net.CNNPolicy.act_fused)."""
     from .net import gaussian_logprob
     if obs_head is not None and not fused:
         raise ValueError("a frame ring (obs_head) can only be read by the fused policy path")
+    if fused_bf16 and not fused:
+        raise ValueError("fused_bf16 is a precision of the fused policy path: it needs fused=True")
     if fused and hasattr(policy, "act_fused"):
         lo, hi = _bounds(action_bound, goal.device, torch.float32)
         if noise is None:
             noise = torch.randn((goal.shape[0], 2), device=goal.device, dtype=torch.float32, generator=generator)
-        v, a, logprob, scaled, _mean = policy.act_fused(obs, goal, speed, noise, lo, hi, head=obs_head)
+        v, a, logprob, scaled, _mean = policy.act_fused(obs, goal, speed, noise, lo, hi, head=obs_head, bf16=fused_bf16)
         return v, a, logprob, scaled
     with torch.no_grad():
         if fused:
-            mean, v = policy.mean_value_fused(obs, goal, speed, head=obs_head)
+            mean, v = policy.mean_value_fused(obs, goal, speed, head=obs_head, bf16=fused_bf16)
         elif autocast_dtype is not None:
             with torch.autocast(obs.device.type, dtype=autocast_dtype):
                 mean, v = policy.mean_value(obs, goal, speed)
@@ -70,14 +73,17 @@ def policy_input(env, fused):
     return env.obs, None
 
 
-def generate_action_no_sampling(policy, obs, goal, speed, action_bound, fused=False, obs_head=None):
-    """model/ppo.py:84-107: deterministic mean action (circle_test.py:58-59)."""
+def generate_action_no_sampling(policy, obs, goal, speed, action_bound, fused=False, obs_head=None, fused_bf16=False):
+    """model/ppo.py:84-107: deterministic mean action (circle_test.py:58-59).  ``fused_bf16``: as generate_action."""
+    if fused_bf16 and not fused:
+        raise ValueError("fused_bf16 is a precision of the fused policy path: it needs fused=True")
     if fused and hasattr(policy, "act_fused"):
         lo, hi = _bounds(action_bound, goal.device, torch.float32)
-        _v, _a, _lp, scaled, mean = policy.act_fused(obs, goal, speed, None, lo, hi, head=obs_head)
+        _v, _a, _lp, scaled, mean = policy.act_fused(obs, goal, speed, None, lo, hi, head=obs_head, bf16=fused_bf16)
         return mean, scaled
     with torch.no_grad():
-        mean, _v = policy.mean_value_fused(obs, goal, speed, head=obs_head) if fused else policy.mean_value(obs, goal, speed)
+        mean, _v = policy.mean_value_fused(obs, goal, speed, head=obs_head, bf16=fused_bf16) if fused else \
+            policy.mean_value(obs, goal, speed)
         lo, hi = _bounds(action_bound, mean.device, mean.dtype)
         scaled = torch.minimum(torch.maximum(mean, lo), hi)
     return mean, scaled

@@ -71,6 +71,8 @@ def main(argv=None):
     ap.add_argument("--lr-max", type=float, default=1e-3)
     ap.add_argument("--bf16-update", action="store_true", help="bf16 autocast in the PPO update (opt-in)")
     ap.add_argument("--bf16-inference", action="store_true", help="bf16 autocast in the rollout policy (opt-in)")
+    ap.add_argument("--fused-bf16-inference", action="store_true", help="rollout inference through the fused path at bf16: "
+                                                                         "the bf16 MFMA front end and a bf16 fc1 (opt-in precision)")
     ap.add_argument("--init", default=None, help="state_dict to start from (overrides the resume file)")
     ap.add_argument("--circle-every", type=int, default=0, help="run the circle test every K updates (rank 0)")
     ap.add_argument("--circle-sizes", default="50:25", help="validation circles as 'robots:radius,...' (50:25 = the reference's "
@@ -105,6 +107,9 @@ def main(argv=None):
                                                                   "(what ppo_stage2.py's dead robots do under stageros), and the "
                                                                   "speed input survives a reset")
     a = ap.parse_args(argv)
+    if a.fused_bf16_inference and (a.bf16_inference or a.stock_policy_path):
+        ap.error("--fused-bf16-inference runs the fused policy path: it cannot be combined with --bf16-inference or "
+                 "--stock-policy-path")
 
     world_size = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -147,6 +152,7 @@ def main(argv=None):
     if a.logstd_min is not None:
         hp.logstd_min = a.logstd_min
     hp.rollout_fused = not a.stock_policy_path and not a.bf16_inference
+    hp.rollout_bf16 = bool(a.fused_bf16_inference)
     hp.graph_tick = bool(a.graph) and not a.no_graph
     hp.update_fused = a.update_path == "fused" and not a.bf16_update and torch.cuda.is_available()
     if a.bf16_update:

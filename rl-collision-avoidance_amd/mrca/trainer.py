@@ -35,6 +35,7 @@ class HParams:
     single_frame_buffer: bool = True  # rollout buffer keeps one lidar frame per tick, not the 3-frame stack (ppo.RolloutBuffer)
     graph_tick: bool = False          # capture the rollout tick (policy + sampling + env tick + buffer stores) in a hipGraph
     rollout_fused: bool = False       # rollout inference through the HIP conv front end (net.mean_value_fused, fp32)
+    rollout_bf16: bool = False        # ... with the bf16 MFMA front end and a bf16 fc1 (opt-in precision; needs rollout_fused)
     # the PPO update differentiates the conv front end through the HIP forward / backward kernels (net.CNNPolicy.fused_train)
     update_fused: bool = False
     kl_target: float = 0.0            # > 0: KL-adaptive learning rate (ppo.KLAdaptiveLR; opt-in, large-batch regime)
@@ -110,7 +111,8 @@ class Stage1Trainer:
         env, hp, buf = self.env, self.hp, self.buffer
         obs, head = ppo.policy_input(env, hp.rollout_fused)
         v, a, logprob, scaled = ppo.generate_action(self.policy, obs, env.local_goal, env.speed, hp.action_bound, self.gen,
-                                                    hp.inference_dtype, hp.rollout_fused, head, noise=noise)
+                                                    hp.inference_dtype, hp.rollout_fused, head, noise=noise,
+                                                    fused_bf16=hp.rollout_bf16)
         so, sn = (None, None) if buf.env_bound else self._stored_obs()
         buf.store_state_at(self._t_idx, so, env.local_goal, env.speed, a, logprob, v, env.fresh, newest=sn)
         env.step(scaled.contiguous())
@@ -178,7 +180,8 @@ class Stage1Trainer:
         else:
             obs, head = ppo.policy_input(env, hp.rollout_fused)
             v, a, logprob, scaled = ppo.generate_action(self.policy, obs, env.local_goal, env.speed,
-                                                        hp.action_bound, self.gen, hp.inference_dtype, hp.rollout_fused, head)
+                                                        hp.action_bound, self.gen, hp.inference_dtype, hp.rollout_fused, head,
+                                                        fused_bf16=hp.rollout_bf16)
             so, sn = self._stored_obs()
             buf.store_state(self.t, so, env.local_goal, env.speed, a, logprob, v, env.fresh, newest=sn)
             env.step(scaled.contiguous())
@@ -194,7 +197,7 @@ class Stage1Trainer:
         with torch.no_grad():                                                           # ppo_stage1.py:94-97
             obs, head = ppo.policy_input(env, hp.rollout_fused)
             if hp.rollout_fused:
-                _mean, last_v = self.policy.mean_value_fused(obs, env.local_goal, env.speed, head=head)
+                _mean, last_v = self.policy.mean_value_fused(obs, env.local_goal, env.speed, head=head, bf16=hp.rollout_bf16)
             else:
                 _mean, last_v = self.policy.mean_value(obs, env.local_goal, env.speed)
         targets, advs = ppo.generate_train_data(buf.reward, hp.gamma, buf.value, last_v, buf.done, hp.lam)
@@ -255,10 +258,11 @@ class Stage1Trainer:
 
 
 def make_bench_step(env, mode, dist, batch_size=16384, inference_dtype=None, update_dtype=None, fused=False,
-                    graph=False, update_fused=False):
-    """bench.py --mode rollout|train: returns step_fn(k) doing one tick for all robots."""
+                    graph=False, update_fused=False, fused_bf16=False):
+    """bench.py --mode rollout|train: returns step_fn(k) doing one tick for all robots.  ``fused_bf16``: the fused rollout
+    path's opt-in bf16 inference (tools/rollout_bf16_probe.py times it)."""
     hp = HParams(batch_size=batch_size, inference_dtype=inference_dtype, update_dtype=update_dtype, rollout_fused=fused,
-                 graph_tick=graph, update_fused=update_fused)
+                 graph_tick=graph, update_fused=update_fused, rollout_bf16=fused_bf16)
     tr = Stage1Trainer(env, hp=hp, dist=dist, seed=0)
     tr.started = True  # bench.py resets the env itself
     if mode == "rollout" and graph:
@@ -269,7 +273,8 @@ def make_bench_step(env, mode, dist, batch_size=16384, inference_dtype=None, upd
         def body(noise=None):
             obs, head = ppo.policy_input(env, hp.rollout_fused)
             _v, _a, _lp, scaled = ppo.generate_action(tr.policy, obs, env.local_goal, env.speed, hp.action_bound, tr.gen,
-                                                      hp.inference_dtype, hp.rollout_fused, head, noise=noise)
+                                                      hp.inference_dtype, hp.rollout_fused, head, noise=noise,
+                                                      fused_bf16=hp.rollout_bf16)
             env.step(scaled.contiguous())
         env.enable_timing(False)
         side = torch.cuda.Stream(device=env.device)
@@ -308,7 +313,8 @@ def make_bench_step(env, mode, dist, batch_size=16384, inference_dtype=None, upd
         def step_fn(_k):
             obs, head = ppo.policy_input(env, hp.rollout_fused)
             _v, _a, _lp, scaled = ppo.generate_action(tr.policy, obs, env.local_goal, env.speed,
-                                                      hp.action_bound, tr.gen, hp.inference_dtype, hp.rollout_fused, head)
+                                                      hp.action_bound, tr.gen, hp.inference_dtype, hp.rollout_fused, head,
+                                                      fused_bf16=hp.rollout_bf16)
             env.step(scaled.contiguous())
         return step_fn
 
