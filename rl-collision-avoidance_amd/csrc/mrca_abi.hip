@@ -13,6 +13,8 @@
 #include <memory>
 #include <mutex>
 #include <new>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "../../include/mrca_env.h"
@@ -220,42 +222,85 @@ std::shared_ptr<const HostField> host_field(const mrca_config* c) {
     return f;
 }
 
+// Owners of what an env holds beside its arena.  A stream is synchronised before it is destroyed.
+struct StreamDeleter { void operator()(hipStream_t s) const { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } };
+struct EventDeleter { void operator()(hipEvent_t e) const { (void)hipEventDestroy(e); } };
+struct DeviceFree { void operator()(void* p) const { (void)hipFree(p); } };
+using Stream = std::unique_ptr<std::remove_pointer_t<hipStream_t>, StreamDeleter>;
+using Event = std::unique_ptr<std::remove_pointer_t<hipEvent_t>, EventDeleter>;
+template <class T> using DeviceBuffer = std::unique_ptr<T, DeviceFree>;
+
+hipError_t make_stream(Stream* s) {
+    hipStream_t h = nullptr;
+    const hipError_t e = hipStreamCreateWithFlags(&h, hipStreamNonBlocking);
+    if (e == hipSuccess) s->reset(h);
+    return e;
+}
+hipError_t make_event(Event* ev, unsigned flags = hipEventDisableTiming) {
+    hipEvent_t h = nullptr;
+    const hipError_t e = hipEventCreateWithFlags(&h, flags);
+    if (e == hipSuccess) ev->reset(h);
+    return e;
+}
+template <class T> hipError_t device_alloc(DeviceBuffer<T>* p, size_t bytes) {
+    void* d = nullptr;
+    const hipError_t e = hipMalloc(&d, bytes);
+    if (e == hipSuccess) p->reset(static_cast<T*>(d));
+    return e;
+}
+
+// mrca_step_many's run-ahead schedule: the move launches of a call's ticks run on a stream of their own,
+// AHEAD of the ray casts, each tick writing the five things a ray cast reads of a move launch -- pose, head record, goal,
+// fresh flag, outline -- into a slot of its own, so that no move launch ever waits for a ray cast.  Slot 0 is the env's
+// own fields (where a call starts and where its last tick ends); slots 1 .. slots live in `mem`.
+struct AheadRing {
+    DeviceBuffer<char> mem;
+    size_t slot_bytes = 0;
+    size_t off[5] = {0, 0, 0, 0, 0};  // pose, head, goal, fresh, outline inside a slot
+    int slots = 0;                    // 0: the ring could not be allocated -> the chained schedule
+    Stream move_stream;
+    std::vector<Event> moved;         // [kAheadTicks] "tick k's move launch is through"
+};
+
+// mrca_step_many with chains > 1: world range c >= 1's stream and the events that order it against the caller's -- `moved`:
+// range c - 1's first move launch is through (the chained schedule starts range c behind it), `done`: range c is through
+struct WorldRange { Stream stream; Event moved, done; };
+
+// stream choice (choose_streams below)
+struct StreamCheck {
+    // (at most 8, oldest first) the move stream and the streams of ranges 1 .. ranges - 1 overlap with `caller` and each other
+    struct Record { hipStream_t caller; int ranges; };
+    std::vector<Record> checked;                 // the caller's streams the env's CURRENT streams were checked against
+    DeviceBuffer<unsigned long long> stamps;     // [4] start / end of the two probe kernels
+    std::vector<Stream> parked;                  // found to share a hardware queue with another stream: kept until mrca_destroy
+    // has the caller's stream `s` been checked against the env's current streams for P ranges or more?
+    bool covers(hipStream_t s, int P) const {
+        return std::any_of(checked.begin(), checked.end(), [&](const Record& r) { return r.caller == s && r.ranges >= P; });
+    }
+};
+
 }  // namespace
 
+// Members are destroyed bottom-up: every stream (world ranges, the move stream, parked ones) is synchronised before the memory
+// above it that its launches may read (the ring, the probe stamps, the view copy, an owned arena) is freed.
 struct mrca_env {
+    DeviceBuffer<char> own_arena;         // the arena when the library allocated it
     mrca_config cfg;
     Layout layout;
     char* arena = nullptr;
-    bool owns_arena = false;
     mrca::EnvView view;
-    mrca::EnvView* view_dev = nullptr;    // `view` in device memory (outside the arena): what move_kernel / raycast_kernel read
+    DeviceBuffer<mrca::EnvView> view_dev;   // `view` in device memory (outside the arena): what move_kernel / raycast_kernel read
     size_t lds_bytes = 0;
     // timing
     int timing = 0;      // 0 off, n > 0: record events on every n-th step
     int step_count = 0;
-    std::vector<hipEvent_t> ev;  // 4 per recorded step: begin / end of the move launch, begin / end of the ray cast
+    std::vector<Event> ev;       // 4 per recorded step: begin / end of the move launch, begin / end of the ray cast
     int ev_used = 0;
     int last_ray_count = 0;   // workgroups of the last ray-cast launch (profiling build: whose stamps are current)
-    // mrca_step_many with chains > 1: the streams of world ranges 1 .. P-1 and the events that order them against the caller's
-    std::vector<hipStream_t> chain_stream;
-    std::vector<hipEvent_t> chain_moved, chain_done;
-    hipEvent_t chain_fork = nullptr;
-    // mrca_step_many's run-ahead schedule: the move launches of a call's ticks run on a stream of their own,
-    // AHEAD of the ray casts, each tick writing the five things a ray cast reads of a move launch -- pose, head record, goal,
-    // fresh flag, outline -- into a slot of its own, so that no move launch ever waits for a ray cast.  Slot 0 is the env's
-    // own fields (where a call starts and where its last tick ends); slots 1 .. ahead_slots live in `ahead_mem`.
-    char* ahead_mem = nullptr;
-    size_t ahead_bytes = 0;                 // per slot
-    size_t ahead_off[5] = {0, 0, 0, 0, 0};  // pose, head, goal, fresh, outline inside a slot
-    int ahead_slots = 0;                    // 0: the ring could not be allocated -> the chained schedule
-    hipStream_t move_stream = nullptr;
-    std::vector<hipEvent_t> moved;          // [kAheadTicks] "tick k's move launch is through"
-    // stream choice (choose_streams below): the caller's stream the env's streams were last checked against, how many
-    // ranges that check covered, the streams found to share a hardware queue with another one (parked until mrca_destroy)
-    std::vector<hipStream_t> checked_against;    // caller's streams the env's CURRENT streams have been checked against
-    int checked_ranges = 0;
-    std::vector<hipStream_t> parked;
-    unsigned long long* probe_stamps = nullptr;   // [4] device: start / end of the two probe kernels
+    StreamCheck check;                    // (these four: mrca_step_many)
+    AheadRing ahead;
+    std::vector<WorldRange> ranges;       // world ranges 1 .. P - 1
+    Event fork;                           // an early exit's join of the move stream
 };
 
 constexpr int kAheadTicks = 256;            // most ticks one run-ahead pass covers (a pass ends with every stream joined: ~90 us)
@@ -269,124 +314,78 @@ constexpr int kChainStreamsAtCreate = 1;
 static mrca::EnvView slot_view(const mrca_env* env, int b) {
     mrca::EnvView v = env->view;
     if (b > 0) {
-        char* base = env->ahead_mem + (size_t)(b - 1) * env->ahead_bytes;
-        v.pose = reinterpret_cast<float*>(base + env->ahead_off[0]);
-        v.head = reinterpret_cast<float4*>(base + env->ahead_off[1]);
-        v.goal = reinterpret_cast<float*>(base + env->ahead_off[2]);
-        v.fresh = reinterpret_cast<uint8_t*>(base + env->ahead_off[3]);
-        if (env->view.outline) v.outline = reinterpret_cast<mrca::OutlineBits*>(base + env->ahead_off[4]);
+        const AheadRing& r = env->ahead;
+        char* base = r.mem.get() + (size_t)(b - 1) * r.slot_bytes;
+        v.pose = reinterpret_cast<float*>(base + r.off[0]);
+        v.head = reinterpret_cast<float4*>(base + r.off[1]);
+        v.goal = reinterpret_cast<float*>(base + r.off[2]);
+        v.fresh = reinterpret_cast<uint8_t*>(base + r.off[3]);
+        if (env->view.outline) v.outline = reinterpret_cast<mrca::OutlineBits*>(base + r.off[4]);
     }
     return v;
+}
+
+// world range c of mrca_step_many's P: its stream (range 0: the caller's) and its first world
+static inline hipStream_t range_stream(const mrca_env* env, hipStream_t s0, int c) { return c ? env->ranges[c - 1].stream.get() : s0; }
+static inline int range_first_world(int W, int P, int c) { return (int)((int64_t)c * W / P); }
+
+// the stream and both events of the next world range: appended only when all three exist
+static hipError_t add_world_range(mrca_env* env) {
+    WorldRange r;
+    hipError_t e = make_stream(&r.stream);
+    if (e == hipSuccess) e = make_event(&r.moved);
+    if (e == hipSuccess) e = make_event(&r.done);
+    if (e == hipSuccess) env->ranges.push_back(std::move(r));
+    return e;
+}
+
+// join: the caller's stream continues when world ranges 1 .. upto - 1 are through, all of them whatever fails (a forked stream
+// left unjoined would dangle from a capture, and its launches would race the caller's next call) -> the first error
+static hipError_t join_ranges(const mrca_env* env, hipStream_t s0, int upto) {
+    hipError_t err = hipSuccess;
+    for (int c = 1; c < upto; ++c) {
+        const WorldRange& r = env->ranges[c - 1];
+        const hipError_t e1 = hipEventRecord(r.done.get(), r.stream.get());
+        const hipError_t e2 = hipStreamWaitEvent(s0, r.done.get(), 0);
+        if (err == hipSuccess) err = e1 != hipSuccess ? e1 : e2;
+    }
+    return err;
+}
+
+// is `s` being captured?  A query that fails counts as yes: what a capture cannot hold is not tried then
+static bool capturing(hipStream_t s) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    return hipStreamIsCapturing(s, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone;
 }
 
 // env->view -> its device copy (mrca_create; the profiling build's debug switches).  Synchronous: no launch that reads the
 // copy is in flight at either place.
 static hipError_t upload_view(mrca_env* env) {
-    hipError_t e = hipSuccess;
-    if (!env->view_dev) e = hipMalloc(reinterpret_cast<void**>(&env->view_dev), sizeof(mrca::EnvView));
+    hipError_t e = env->view_dev ? hipSuccess : device_alloc(&env->view_dev, sizeof(mrca::EnvView));
     if (e != hipSuccess) return e;
-    env->view.dev = env->view_dev;
+    env->view.dev = env->view_dev.get();
     if ((e = hipDeviceSynchronize()) != hipSuccess) return e;
-    return hipMemcpy(env->view_dev, &env->view, sizeof(mrca::EnvView), hipMemcpyHostToDevice);
+    return hipMemcpy(env->view_dev.get(), &env->view, sizeof(mrca::EnvView), hipMemcpyHostToDevice);
 }
 
-// the streams, events and the run-ahead ring an env owns beside its arena (mrca_destroy, and mrca_create when it gives up)
-static void release_side_objects(mrca_env* env) {
-    for (hipEvent_t e : env->ev) (void)hipEventDestroy(e);
-    for (hipStream_t s : env->chain_stream) {
-        (void)hipStreamSynchronize(s);
-        (void)hipStreamDestroy(s);
+// the caller's arena, or one of the library's own
+static int attach_arena(mrca_env* env, void* arena_dev, size_t arena_bytes) {
+    const size_t total = env->layout.total;
+    if (arena_dev) {
+        if (arena_bytes < total) return fail(MRCA_ERR_NOMEM, "arena of %zu bytes < required %zu", arena_bytes, total);
+        if (reinterpret_cast<uintptr_t>(arena_dev) % kAlign) return fail(MRCA_ERR_INVALID, "arena must be %zu-byte aligned", kAlign);
+        env->arena = static_cast<char*>(arena_dev);
+        return MRCA_OK;
     }
-    if (env->move_stream) {
-        (void)hipStreamSynchronize(env->move_stream);
-        (void)hipStreamDestroy(env->move_stream);
-    }
-    for (hipEvent_t e : env->moved)
-        if (e) (void)hipEventDestroy(e);
-    if (env->ahead_mem) (void)hipFree(env->ahead_mem);
-    if (env->view_dev) (void)hipFree(env->view_dev);
-    env->view_dev = nullptr;
-    env->view.dev = nullptr;
-    if (env->probe_stamps) (void)hipFree(env->probe_stamps);
-    env->probe_stamps = nullptr;
-    for (hipStream_t s : env->parked) (void)hipStreamDestroy(s);
-    env->parked.clear();
-    for (hipEvent_t e : env->chain_moved) (void)hipEventDestroy(e);
-    for (hipEvent_t e : env->chain_done) (void)hipEventDestroy(e);
-    if (env->chain_fork) (void)hipEventDestroy(env->chain_fork);
-    env->ev.clear();
-    env->chain_stream.clear();
-    env->moved.clear();
-    env->chain_moved.clear();
-    env->chain_done.clear();
-    env->move_stream = nullptr;
-    env->ahead_mem = nullptr;
-    env->chain_fork = nullptr;
-}
-
-extern "C" {
-
-int mrca_abi_version(void) { return MRCA_ABI_VERSION; }
-
-const char* mrca_last_error(void) { return g_err; }
-
-int mrca_arena_bytes(const mrca_config* cfg, size_t* bytes_out) {
-    if (int rc = validate(cfg)) return rc;
-    if (!bytes_out) return fail(MRCA_ERR_INVALID, "bytes_out is NULL");
-    Layout L;
-    make_layout(cfg, &L);
-    *bytes_out = L.total;
+    const hipError_t e = device_alloc(&env->own_arena, total);
+    if (e != hipSuccess) return fail(MRCA_ERR_NOMEM, "hipMalloc(%zu) failed: %s", total, hipGetErrorString(e));
+    env->arena = env->own_arena.get();
     return MRCA_OK;
 }
 
-int mrca_create(const mrca_config* cfg, void* arena_dev, size_t arena_bytes, mrca_env** env_out) {
-    if (int rc = validate(cfg)) return rc;
-    if (!env_out) return fail(MRCA_ERR_INVALID, "env_out is NULL");
-    *env_out = nullptr;
-    int ndev = 0;
-    HIP_TRY(hipGetDeviceCount(&ndev));
-    if (cfg->device < 0 || cfg->device >= ndev)
-        return fail(MRCA_ERR_INVALID, "device %d not in [0,%d)", cfg->device, ndev);
-    HIP_TRY(hipSetDevice(cfg->device));
-
-    mrca_env* env = new (std::nothrow) mrca_env();
-    if (!env) return fail(MRCA_ERR_NOMEM, "host allocation failed");
-    env->cfg = *cfg;
-    make_layout(cfg, &env->layout);
-    const Layout& L = env->layout;
-    if (arena_dev) {
-        if (arena_bytes < L.total) {
-            delete env;
-            return fail(MRCA_ERR_NOMEM, "arena of %zu bytes < required %zu", arena_bytes, L.total);
-        }
-        if (reinterpret_cast<uintptr_t>(arena_dev) % kAlign) {
-            delete env;
-            return fail(MRCA_ERR_INVALID, "arena must be %zu-byte aligned", kAlign);
-        }
-        env->arena = static_cast<char*>(arena_dev);
-    } else {
-        hipError_t e = hipMalloc(reinterpret_cast<void**>(&env->arena), L.total);
-        if (e != hipSuccess) {
-            delete env;
-            return fail(MRCA_ERR_NOMEM, "hipMalloc(%zu) failed: %s", L.total, hipGetErrorString(e));
-        }
-        env->owns_arena = true;
-    }
-    auto bail = [&](int rc) {
-        release_side_objects(env);
-        if (env->owns_arena) (void)hipFree(env->arena);
-        delete env;
-        return rc;
-    };
-#define HIP_TRY_BAIL(expr)                                                                        \
-    do {                                                                                          \
-        hipError_t _e = (expr);                                                                   \
-        if (_e != hipSuccess)                                                                     \
-            return bail(fail(MRCA_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(_e)));       \
-    } while (0)
-
-    HIP_TRY_BAIL(hipMemset(env->arena, 0, L.total));
-
+// the arena's contents at construction (tables, poses, beams, map) -> the free-rectangle field's pitch, the robot groups
+static int upload_tables(const mrca_config* cfg, const Layout& L, char* arena, int* free_rect_pitch, int* num_groups_out) {
+    HIP_TRY(hipMemset(arena, 0, L.total));
     const int R = cfg->robots_per_world, B = cfg->beams;
     const size_t N = (size_t)cfg->num_worlds * R;
     // scenario tables
@@ -400,6 +399,7 @@ int mrca_create(const mrca_config* cfg, void* arena_dev, size_t arena_bytes, mrc
     if (cfg->goal_table) memcpy(goal_tab.data(), cfg->goal_table, R * 2 * 4);
     int num_groups = 0;
     for (int i = 0; i < R; ++i) num_groups = group[i] + 1 > num_groups ? group[i] + 1 : num_groups;
+    *num_groups_out = num_groups;
     // beam directions: bearing_i = -pi/2 + i*pi/(B-1) (stageros.cpp:495-497), evaluated in
     // double, rounded once to fp32
     std::vector<float> bcos(B), bsin(B);
@@ -408,11 +408,11 @@ int mrca_create(const mrca_config* cfg, void* arena_dev, size_t arena_bytes, mrc
         bcos[i] = (float)std::cos(b);
         bsin[i] = (float)std::sin(b);
     }
-    HIP_TRY_BAIL(hipMemcpy(env->arena + L.off_reset_mode, reset_mode.data(), R * 4, hipMemcpyHostToDevice));
-    HIP_TRY_BAIL(hipMemcpy(env->arena + L.off_goal_mode, goal_mode.data(), R * 4, hipMemcpyHostToDevice));
-    HIP_TRY_BAIL(hipMemcpy(env->arena + L.off_group_id, group.data(), R * 4, hipMemcpyHostToDevice));
-    HIP_TRY_BAIL(hipMemcpy(env->arena + L.off_init_table, init_tab.data(), R * 3 * 4, hipMemcpyHostToDevice));
-    HIP_TRY_BAIL(hipMemcpy(env->arena + L.off_goal_table, goal_tab.data(), R * 2 * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(arena + L.off_reset_mode, reset_mode.data(), R * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(arena + L.off_goal_mode, goal_mode.data(), R * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(arena + L.off_group_id, group.data(), R * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(arena + L.off_init_table, init_tab.data(), R * 3 * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(arena + L.off_goal_table, goal_tab.data(), R * 2 * 4, hipMemcpyHostToDevice));
     {
         // before the first reset the robots stand at their table poses (= the agent lines of the world file): a start
         // sampled in Stage-2's region keeps 7 m away from the robot's CURRENT position, its first one included
@@ -420,38 +420,39 @@ int mrca_create(const mrca_config* cfg, void* arena_dev, size_t arena_bytes, mrc
         std::vector<float> pose0((size_t)N * 3);
         for (size_t n = 0; n < N; ++n)
             for (int k = 0; k < 3; ++k) pose0[n * 3 + k] = init_tab[(n % (size_t)R) * 3 + k];
-        HIP_TRY_BAIL(hipMemcpy(env->arena + L.field_off[MRCA_F_POSE], pose0.data(), pose0.size() * 4, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(arena + L.field_off[MRCA_F_POSE], pose0.data(), pose0.size() * 4, hipMemcpyHostToDevice));
     }
-    HIP_TRY_BAIL(hipMemcpy(env->arena + L.off_beam_cos, bcos.data(), B * 4, hipMemcpyHostToDevice));
-    HIP_TRY_BAIL(hipMemcpy(env->arena + L.off_beam_sin, bsin.data(), B * 4, hipMemcpyHostToDevice));
-    HIP_TRY_BAIL(hipMemcpy(env->arena + L.off_map, cfg->map_bits,
-                           (size_t)cfg->map_height * cfg->map_words_per_row * 4, hipMemcpyHostToDevice));
-    int free_rect_pitch = 0;
+    HIP_TRY(hipMemcpy(arena + L.off_beam_cos, bcos.data(), B * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(arena + L.off_beam_sin, bsin.data(), B * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(arena + L.off_map, cfg->map_bits, (size_t)cfg->map_height * cfg->map_words_per_row * 4,
+                      hipMemcpyHostToDevice));
     {
         const std::shared_ptr<const HostField> hf = host_field(cfg);
-        free_rect_pitch = hf->pitch;
-        HIP_TRY_BAIL(hipMemcpy(env->arena + L.off_free_rect, hf->entries.data(), hf->entries.size() * sizeof(uint16_t),
-                               hipMemcpyHostToDevice));
+        *free_rect_pitch = hf->pitch;
+        HIP_TRY(hipMemcpy(arena + L.off_free_rect, hf->entries.data(), hf->entries.size() * sizeof(uint16_t),
+                          hipMemcpyHostToDevice));
     }
     {
         std::vector<uint8_t> cf;
         mrca::build_cell_field(cfg->map_bits, cfg->map_width, cfg->map_height, cfg->map_words_per_row, &cf);
-        HIP_TRY_BAIL(hipMemcpy(env->arena + L.off_cellfield, cf.data(), cf.size(), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(arena + L.off_cellfield, cf.data(), cf.size(), hipMemcpyHostToDevice));
     }
     if (R > 64)    // the collision hash starts empty; every tick leaves it empty again (bw_finish_kernel)
-        HIP_TRY_BAIL(hipMemset(env->arena + L.off_bw_chead, 0xFF, ((size_t)L.bw_cmask + 1) * 4));
+        HIP_TRY(hipMemset(arena + L.off_bw_chead, 0xFF, ((size_t)L.bw_cmask + 1) * 4));
     // live = 1, t = 1 at construction (a robot exists and is idle before the first reset)
-    HIP_TRY_BAIL(hipMemset(env->arena + L.field_off[MRCA_F_LIVE], 1, N));
+    HIP_TRY(hipMemset(arena + L.field_off[MRCA_F_LIVE], 1, N));
     {
         std::vector<int32_t> ones(N, 1);
-        HIP_TRY_BAIL(hipMemcpy(env->arena + L.field_off[MRCA_F_T], ones.data(), N * 4, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(arena + L.field_off[MRCA_F_T], ones.data(), N * 4, hipMemcpyHostToDevice));
     }
-    env->cfg.map_bits = nullptr;  // host pointers are not retained
-    env->cfg.reset_mode = env->cfg.goal_mode = env->cfg.group_id = nullptr;
-    env->cfg.init_table = env->cfg.goal_table = nullptr;
+    return MRCA_OK;
+}
 
-    mrca::EnvView& v = env->view;
-    char* a = env->arena;
+// the view of the arena `a` and of the config that every launch takes
+static mrca::EnvView make_view(const mrca_config* cfg, const Layout& L, char* a, int free_rect_pitch, int num_groups) {
+    const int R = cfg->robots_per_world, B = cfg->beams;
+    const size_t N = (size_t)cfg->num_worlds * R;
+    mrca::EnvView v = mrca::EnvView();
     v.N = (int32_t)N;
     v.R = R;
     v.W = cfg->num_worlds;
@@ -573,65 +574,97 @@ int mrca_create(const mrca_config* cfg, void* arena_dev, size_t arena_bytes, mrc
     v.ray_shift = product_ray_shift(cfg->beams, v.big);
     v.ray_prep_wave = 0;
     v.ray_sequential = 1;
+    return v;
+}
+
+// what the move launch and the ray cast need of a CU's LDS
+static int check_lds(mrca_env* env) {
+    const mrca::EnvView& v = env->view;
     env->lds_bytes = mrca::ray_lds_bytes(v);
     if (!v.big && mrca::move_lds_bytes(v) > 64 * 1024)
-        return bail(fail(MRCA_ERR_UNSUPPORTED, "map_cell %.4f m is too fine for the LDS patches: use >= 0.01 m",
-                         (double)cfg->map_cell));
+        return fail(MRCA_ERR_UNSUPPORTED, "map_cell %.4f m is too fine for the LDS patches: use >= 0.01 m", (double)env->cfg.map_cell);
     if (env->lds_bytes > 160 * 1024)
-        return bail(fail(MRCA_ERR_UNSUPPORTED, "the ray cast needs %zu B of LDS per robot (> 160 KiB): too many beams",
-                         env->lds_bytes));
-    if (!v.big) {
-        // the run-ahead ring of mrca_step_many (outside the arena: a caller-provided arena keeps its documented size).  As many
-        // slots as fit the budget, at most one per tick of a pass; none (allocation failed) = the chained schedule, no error
-        size_t off = 0;
-        const size_t part[5] = {N * 3 * 4, N * sizeof(float4), N * 2 * 4, N, v.outline ? N * sizeof(mrca::OutlineBits) : 0};
-        for (int i = 0; i < 5; ++i) {
-            env->ahead_off[i] = off;
-            off += align_up(part[i]);
-        }
-        env->ahead_bytes = off;
-        size_t slots = kAheadMaxBytes / off;
-        if (slots > (size_t)kAheadTicks - 1) slots = kAheadTicks - 1;
-        if (slots >= 1 && hipMalloc(reinterpret_cast<void**>(&env->ahead_mem), slots * off) == hipSuccess) {
-            env->ahead_slots = (int)slots;
-        } else {
-            (void)hipGetLastError();
-            env->ahead_mem = nullptr;
-        }
-        bool ok = hipStreamCreateWithFlags(&env->move_stream, hipStreamNonBlocking) == hipSuccess;
-        env->moved.assign(kAheadTicks, nullptr);
-        for (auto& e : env->moved) ok = ok && hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess;
-        for (int c = 0; c < kChainStreamsAtCreate && ok; ++c) {
-            hipStream_t st = nullptr;
-            hipEvent_t ea = nullptr, eb = nullptr;
-            ok = hipStreamCreateWithFlags(&st, hipStreamNonBlocking) == hipSuccess &&
-                 hipEventCreateWithFlags(&ea, hipEventDisableTiming) == hipSuccess &&
-                 hipEventCreateWithFlags(&eb, hipEventDisableTiming) == hipSuccess;
-            if (ok) {
-                env->chain_stream.push_back(st);
-                env->chain_moved.push_back(ea);
-                env->chain_done.push_back(eb);
-            }
-        }
-        if (!ok) {
-            (void)hipGetLastError();
-            env->ahead_slots = 0;       // (whatever was created is released by mrca_destroy)
-        }
-    }
-    HIP_TRY_BAIL(upload_view(env));       // (the view is final from here on)
-    mrca::launch_head_init(v, nullptr);   // head records of the construction-time poses (all at the origin)
-    HIP_TRY_BAIL(hipGetLastError());
-    HIP_TRY_BAIL(hipDeviceSynchronize());
-    *env_out = env;
+        return fail(MRCA_ERR_UNSUPPORTED, "the ray cast needs %zu B of LDS per robot (> 160 KiB): too many beams", env->lds_bytes);
     return MRCA_OK;
-#undef HIP_TRY_BAIL
+}
+
+// mrca_step_many's ring (outside the arena: a caller-provided arena keeps its documented size), move stream and first ranges.  As
+// many slots as fit the budget, at most one per tick of a pass; none (something could not be made) = the chained schedule, no error
+static void init_step_many(mrca_env* env) {
+    AheadRing& r = env->ahead;
+    const size_t N = (size_t)env->view.N;
+    size_t off = 0;
+    const size_t part[5] = {N * 3 * 4, N * sizeof(float4), N * 2 * 4, N, env->view.outline ? N * sizeof(mrca::OutlineBits) : 0};
+    for (int i = 0; i < 5; ++i) {
+        r.off[i] = off;
+        off += align_up(part[i]);
+    }
+    r.slot_bytes = off;
+    size_t slots = kAheadMaxBytes / off;
+    if (slots > (size_t)kAheadTicks - 1) slots = kAheadTicks - 1;
+    if (slots >= 1 && device_alloc(&r.mem, slots * off) == hipSuccess) r.slots = (int)slots;
+    else (void)hipGetLastError();
+    bool ok = make_stream(&r.move_stream) == hipSuccess;
+    r.moved.resize(kAheadTicks);
+    for (Event& e : r.moved) ok = ok && make_event(&e) == hipSuccess;
+    for (int c = 0; c < kChainStreamsAtCreate && ok; ++c) ok = add_world_range(env) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        r.slots = 0;
+    }
+}
+
+extern "C" {
+
+int mrca_abi_version(void) { return MRCA_ABI_VERSION; }
+
+const char* mrca_last_error(void) { return g_err; }
+
+int mrca_arena_bytes(const mrca_config* cfg, size_t* bytes_out) {
+    if (int rc = validate(cfg)) return rc;
+    if (!bytes_out) return fail(MRCA_ERR_INVALID, "bytes_out is NULL");
+    Layout L;
+    make_layout(cfg, &L);
+    *bytes_out = L.total;
+    return MRCA_OK;
+}
+
+int mrca_create(const mrca_config* cfg, void* arena_dev, size_t arena_bytes, mrca_env** env_out) {
+    if (int rc = validate(cfg)) return rc;
+    if (!env_out) return fail(MRCA_ERR_INVALID, "env_out is NULL");
+    *env_out = nullptr;
+    int ndev = 0;
+    HIP_TRY(hipGetDeviceCount(&ndev));
+    if (cfg->device < 0 || cfg->device >= ndev)
+        return fail(MRCA_ERR_INVALID, "device %d not in [0,%d)", cfg->device, ndev);
+    HIP_TRY(hipSetDevice(cfg->device));
+
+    std::unique_ptr<mrca_env> env(new (std::nothrow) mrca_env());   // (an early return frees what it holds by then)
+    if (!env) return fail(MRCA_ERR_NOMEM, "host allocation failed");
+    env->cfg = *cfg;
+    make_layout(cfg, &env->layout);
+    if (int rc = attach_arena(env.get(), arena_dev, arena_bytes)) return rc;
+    int free_rect_pitch = 0, num_groups = 0;
+    if (int rc = upload_tables(cfg, env->layout, env->arena, &free_rect_pitch, &num_groups)) return rc;
+    env->cfg.map_bits = nullptr;  // host pointers are not retained
+    env->cfg.reset_mode = env->cfg.goal_mode = env->cfg.group_id = nullptr;
+    env->cfg.init_table = env->cfg.goal_table = nullptr;
+    env->view = make_view(cfg, env->layout, env->arena, free_rect_pitch, num_groups);
+    if (int rc = check_lds(env.get())) return rc;
+    if (!env->view.big) init_step_many(env.get());
+    HIP_TRY(upload_view(env.get()));       // (the view is final from here on)
+    mrca::launch_head_init(env->view, nullptr);   // head records of the construction-time poses (all at the origin)
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    *env_out = env.release();
+    return MRCA_OK;
 }
 
 int mrca_destroy(mrca_env* env) {
     if (!env) return MRCA_OK;
-    release_side_objects(env);
-    if (env->owns_arena) HIP_TRY(hipFree(env->arena));
+    char* arena = env->own_arena.release();   // (freed last: the one failure reported)
     delete env;
+    if (arena) HIP_TRY(hipFree(arena));
     return MRCA_OK;
 }
 
@@ -694,13 +727,13 @@ static int step_impl(mrca_env* env, const float* actions_dev, int32_t first, int
     v.world_count = world_count;
     env->last_ray_count = count;
     // timing: the launches' own begin / end stamps (hipExtLaunchKernel), not event records around them
-    hipEvent_t* ev = rec ? &env->ev[env->ev_used] : nullptr;
-    if (phases & kPhaseMove) mrca::launch_move(v, actions_dev, s, rec ? ev[0] : nullptr, rec ? ev[1] : nullptr);
+    const Event* ev = rec ? &env->ev[env->ev_used] : nullptr;
+    if (phases & kPhaseMove) mrca::launch_move(v, actions_dev, s, rec ? ev[0].get() : nullptr, rec ? ev[1].get() : nullptr);
     if (phases & kPhaseObserve) {
         mrca::launch_lidar_grid(v, /*counted=*/1, s);
         // (lazy_obs = 0: the ray cast forms MRCA_F_SCAN / MRCA_F_OBS of its robots itself -- no materialize launch behind it)
         v.eager_views = env->cfg.lazy_obs ? 0 : (MRCA_VIEW_SCAN | MRCA_VIEW_OBS);
-        mrca::launch_raycast(v, /*only_fresh=*/0, s, rec ? ev[2] : nullptr, rec ? ev[3] : nullptr);
+        mrca::launch_raycast(v, /*only_fresh=*/0, s, rec ? ev[2].get() : nullptr, rec ? ev[3].get() : nullptr);
     }
     if (rec) env->ev_used += 4;
     HIP_TRY(hipGetLastError());
@@ -747,8 +780,8 @@ int mrca_observe_worlds(mrca_env* env, int32_t first_world, int32_t num_worlds, 
 // pair (both warmed first: a stream's first launch creates its queue), stamped with the constant clock; if the second started
 // only after the first had ended, the pair shares a queue: the env parks that stream (a parked stream keeps its use count on
 // its queue, so the next candidate lands elsewhere) and tries another.  At the first mrca_step_many call on a given caller's
-// stream (again if that stream changes or more ranges are asked for), never inside a capture: ~1 ms, and the one place where a
-// call of this library synchronises.
+// stream (again if more ranges are asked for on it, or a check had to replace one of the env's streams), never inside a capture:
+// ~1 ms, and the one place where a call of this library synchronises.
 __global__ void stream_probe_kernel(unsigned long long ticks, unsigned long long* stamps, int slot) {
     const unsigned long long t0 = wall_clock64();
     while (wall_clock64() - t0 < ticks) __builtin_amdgcn_s_sleep(4);
@@ -762,11 +795,11 @@ __global__ void stream_probe_kernel(unsigned long long ticks, unsigned long long
 static int streams_overlap(mrca_env* env, hipStream_t a, hipStream_t b) {
     int serial = 0;
     for (int rep = 0; rep < 3; ++rep) {
-        hipLaunchKernelGGL(stream_probe_kernel, dim3(1), dim3(64), 0, a, 4000ull, env->probe_stamps, 0);      // 40 us
-        hipLaunchKernelGGL(stream_probe_kernel, dim3(1), dim3(64), 0, b, 4000ull, env->probe_stamps, 1);
+        hipLaunchKernelGGL(stream_probe_kernel, dim3(1), dim3(64), 0, a, 4000ull, env->check.stamps.get(), 0);      // 40 us
+        hipLaunchKernelGGL(stream_probe_kernel, dim3(1), dim3(64), 0, b, 4000ull, env->check.stamps.get(), 1);
         if (hipStreamSynchronize(a) != hipSuccess || hipStreamSynchronize(b) != hipSuccess) return -1;
         unsigned long long h[4];
-        if (hipMemcpy(h, env->probe_stamps, sizeof(h), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+        if (hipMemcpy(h, env->check.stamps.get(), sizeof(h), hipMemcpyDeviceToHost) != hipSuccess) return -1;
         if (h[2] >= h[1] || h[0] >= h[3]) ++serial;
     }
     return serial >= 2 ? 0 : 1;
@@ -778,51 +811,49 @@ static int warm_stream(hipStream_t st) {
     return MRCA_OK;
 }
 
-// make `*slot` a stream that overlaps with every stream of `others`; the ones that do not are parked
-static int choose_stream(mrca_env* env, hipStream_t* slot, const std::vector<hipStream_t>& others) {
+// make `*slot` a stream that overlaps with every stream of `chosen` and add it there; the ones that do not are parked
+static int choose_stream(mrca_env* env, Stream* slot, std::vector<hipStream_t>* chosen) {
     for (int attempt = 0; attempt < 6; ++attempt) {
-        if (!*slot) HIP_TRY(hipStreamCreateWithFlags(slot, hipStreamNonBlocking));
-        if (int rc = warm_stream(*slot)) return rc;
+        if (!*slot) HIP_TRY(make_stream(slot));
+        if (int rc = warm_stream(slot->get())) return rc;
         bool good = true;
-        for (hipStream_t o : others) {
-            const int ov = streams_overlap(env, o, *slot);
+        for (hipStream_t o : *chosen) {
+            const int ov = streams_overlap(env, o, slot->get());
             if (ov < 0) return fail(MRCA_ERR_HIP, "mrca_step_many: stream probe failed: %s", hipGetErrorString(hipGetLastError()));
             if (ov == 0) {
                 good = false;
                 break;
             }
         }
-        if (good) return MRCA_OK;
-        env->parked.push_back(*slot);
-        *slot = nullptr;
+        if (good) break;
+        env->check.parked.push_back(std::move(*slot));
     }
-    // six candidates in a row shared a queue with somebody: take one more as it comes (correct, only not concurrent)
-    HIP_TRY(hipStreamCreateWithFlags(slot, hipStreamNonBlocking));
+    // (six candidates in a row shared a queue with somebody: take one more as it comes -- correct, only not concurrent)
+    if (!*slot) HIP_TRY(make_stream(slot));
+    chosen->push_back(slot->get());
     return MRCA_OK;
 }
 
 static int choose_streams(mrca_env* env, hipStream_t s0, int P) {
-    if (!env->probe_stamps) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&env->probe_stamps), 4 * sizeof(unsigned long long)));
-    const size_t parked_before = env->parked.size();
+    StreamCheck& chk = env->check;
+    if (!chk.stamps) HIP_TRY(device_alloc(&chk.stamps, 4 * sizeof(unsigned long long)));
+    const size_t parked_before = chk.parked.size();
     if (int rc = warm_stream(s0)) return rc;
     std::vector<hipStream_t> chosen{s0};
-    if (env->ahead_slots > 0) {
-        if (int rc = choose_stream(env, &env->move_stream, chosen)) return rc;
-        chosen.push_back(env->move_stream);
-    }
-    for (int c = 1; c < P; ++c) {
-        if (int rc = choose_stream(env, &env->chain_stream[c - 1], chosen)) return rc;
-        chosen.push_back(env->chain_stream[c - 1]);
-    }
+    if (env->ahead.slots > 0)
+        if (int rc = choose_stream(env, &env->ahead.move_stream, &chosen)) return rc;
+    for (int c = 1; c < P; ++c)
+        if (int rc = choose_stream(env, &env->ranges[c - 1].stream, &chosen)) return rc;
     // (a caller that alternates between a few streams is checked once per stream, not once per call -- unless a check had to
     // replace one of the env's streams: then what was verified before no longer holds)
-    if (env->parked.size() != parked_before || P > env->checked_ranges) env->checked_against.clear();
-    if (env->checked_against.size() >= 8) env->checked_against.erase(env->checked_against.begin());
-    env->checked_against.push_back(s0);
-    if (P > env->checked_ranges) env->checked_ranges = P;
+    std::vector<StreamCheck::Record>& rec = chk.checked;
+    if (chk.parked.size() != parked_before) rec.clear();
+    rec.erase(std::remove_if(rec.begin(), rec.end(), [s0](const StreamCheck::Record& r) { return r.caller == s0; }), rec.end());
+    if (rec.size() >= 8) rec.erase(rec.begin());
+    rec.push_back({s0, P});
     if (std::getenv("MRCA_DEBUG_STREAMS"))
         std::fprintf(stderr, "[mrca] stream check against %p: %d range stream(s) + move stream chosen, %zu candidate(s) parked\n",
-                     (void*)s0, env->checked_ranges - 1, env->parked.size());
+                     (void*)s0, P - 1, chk.parked.size());
     return MRCA_OK;
 }
 
@@ -901,7 +932,7 @@ static void log_end() {
 #endif
 
 
-// One run-ahead pass of mrca_step_many: K <= ahead_slots + 1 ticks.  Tick k's move launch covers ALL worlds and writes slot
+// One run-ahead pass of mrca_step_many: K <= ahead.slots + 1 ticks.  Tick k's move launch covers ALL worlds and writes slot
 // w(k) = K - 1 - k (slot 0 = the env's own fields: the pass starts from them and its last tick leaves them current), reading
 // slot w(k - 1); tick 0 goes out on the caller's stream, ticks 1 .. K - 1 on the env's move stream, back to back -- a slot per
 // tick, so a move launch waits for no ray cast.  The ray casts of world range c run on the range's stream (range 0: the
@@ -911,8 +942,7 @@ static void log_end() {
 // Every dependency is a stream order or an event; nothing spins.
 static int run_ahead_pass(mrca_env* env, const float* const* act, int K, int P, hipStream_t s0) {
     const int W = env->view.W, R = env->view.R;
-    auto stream_of = [&](int c) { return c == 0 ? s0 : env->chain_stream[c - 1]; };
-    auto first_world = [&](int c) { return (int)((int64_t)c * W / P); };
+    hipStream_t const ms = env->ahead.move_stream.get();
     hipError_t herr = hipSuccess;
     bool move_forked = false;
     MRCA_LOG_BEGIN();
@@ -933,9 +963,9 @@ static int run_ahead_pass(mrca_env* env, const float* const* act, int K, int P, 
     constexpr int own = 1;                       // ticks below this one: move launches on the caller's stream
     auto moves_of = [&](int b) {
         const int a = first_of[b], e = first_of[b + 1];
-        hipStream_t sm = a < own ? s0 : env->move_stream;
+        hipStream_t sm = a < own ? s0 : ms;
         if (a >= own && !move_forked) {       // the move stream starts behind the caller's last move launch (and so behind the caller's work)
-            herr = hipStreamWaitEvent(env->move_stream, env->moved[a - 1], 0);
+            herr = hipStreamWaitEvent(ms, env->ahead.moved[a - 1].get(), 0);
             if (herr != hipSuccess) return;
             move_forked = true;
         }
@@ -947,17 +977,17 @@ static int run_ahead_pass(mrca_env* env, const float* const* act, int K, int P, 
             MRCA_LOG_TAG(mv, "move", k, 0);
             mrca::launch_move(mv, act[k], sm, nullptr, nullptr, &in);
         }
-        herr = hipEventRecord(env->moved[e - 1], sm);
+        herr = hipEventRecord(env->ahead.moved[e - 1].get(), sm);
     };
     auto rays_of = [&](int b) {
         const int a = first_of[b], e = first_of[b + 1];
         for (int c = 0; c < P && herr == hipSuccess; ++c) {
-            hipStream_t sc = stream_of(c);
+            hipStream_t sc = range_stream(env, s0, c);
             if (c > 0 || a >= own) {        // (range 0's first ray casts follow their ticks' move launches on the caller's stream itself)
-                herr = hipStreamWaitEvent(sc, env->moved[e - 1], 0);
+                herr = hipStreamWaitEvent(sc, env->ahead.moved[e - 1].get(), 0);
                 if (herr != hipSuccess) return;
             }
-            const int w0 = first_world(c), wn = first_world(c + 1) - w0;
+            const int w0 = range_first_world(W, P, c), wn = range_first_world(W, P, c + 1) - w0;
             for (int k = a; k < e; ++k) {
                 mrca::EnvView rv = slot_view(env, K - 1 - k);
                 rv.ray_first = w0 * R;
@@ -979,14 +1009,10 @@ static int run_ahead_pass(mrca_env* env, const float* const* act, int K, int P, 
     // join: the caller's stream continues when every range is through (the move stream is: range 0 waited for its last launch)
     hipError_t jerr = hipSuccess;
     if (K > 0) {
-        for (int c = 1; c < P; ++c) {
-            hipError_t e1 = hipEventRecord(env->chain_done[c - 1], stream_of(c));
-            hipError_t e2 = hipStreamWaitEvent(s0, env->chain_done[c - 1], 0);
-            if (jerr == hipSuccess) jerr = e1 != hipSuccess ? e1 : e2;
-        }
+        jerr = join_ranges(env, s0, P);
         if (move_forked && herr != hipSuccess) {     // an early exit: the move stream may still be forked off the caller's
-            hipError_t e1 = hipEventRecord(env->chain_fork, env->move_stream);
-            hipError_t e2 = hipStreamWaitEvent(s0, env->chain_fork, 0);
+            hipError_t e1 = hipEventRecord(env->fork.get(), ms);
+            hipError_t e2 = hipStreamWaitEvent(s0, env->fork.get(), 0);
             if (jerr == hipSuccess) jerr = e1 != hipSuccess ? e1 : e2;
         }
     }
@@ -1014,34 +1040,20 @@ int mrca_step_many(mrca_env* env, const float* const* actions_dev, int32_t num_a
     DeviceGuard guard(env->cfg.device);
     hipStream_t s0 = static_cast<hipStream_t>(stream);
     // streams and events of ranges beyond the ones mrca_create made: never inside a capture (stream creation is not capturable)
-    while ((int)env->chain_stream.size() < P - 1) {
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        (void)hipStreamIsCapturing(s0, &cs);
-        if (cs != hipStreamCaptureStatusNone)
+    while ((int)env->ranges.size() < P - 1) {
+        if (capturing(s0))
             return fail(MRCA_ERR_INVALID, "mrca_step_many: chains %d needs streams the env has not created yet -- call it once "
                                           "outside the capture first (mrca_create prepares chains <= %d)", P, kChainStreamsAtCreate + 1);
-        hipStream_t s;
-        hipEvent_t a, b;
-        HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-        HIP_TRY(hipEventCreateWithFlags(&a, hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&b, hipEventDisableTiming));
-        env->chain_stream.push_back(s);
-        env->chain_moved.push_back(a);
-        env->chain_done.push_back(b);
+        HIP_TRY(add_world_range(env));
     }
-    if (!env->chain_fork) HIP_TRY(hipEventCreateWithFlags(&env->chain_fork, hipEventDisableTiming));
+    if (!env->fork) HIP_TRY(make_event(&env->fork));
     if (num_ticks == 0) return MRCA_OK;
-    if (!env->view.big && (P > 1 || (!chained && env->ahead_slots > 0)) &&
-        (env->checked_ranges < P ||
-         std::find(env->checked_against.begin(), env->checked_against.end(), s0) == env->checked_against.end())) {
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        (void)hipStreamIsCapturing(s0, &cs);
-        if (cs == hipStreamCaptureStatusNone)          // (inside a capture: the streams as they are)
-            if (int rc = choose_streams(env, s0, P)) return rc;
-    }
-    if (!chained && !env->view.big && env->ahead_slots > 0) {
-        // the run-ahead schedule, in passes of at most ahead_slots + 1 ticks (a pass ends with every stream joined)
-        const int per = env->ahead_slots + 1 < kAheadTicks ? env->ahead_slots + 1 : kAheadTicks;
+    if (!env->view.big && (P > 1 || (!chained && env->ahead.slots > 0)) && !env->check.covers(s0, P) &&
+        !capturing(s0))                                // (inside a capture: the streams as they are)
+        if (int rc = choose_streams(env, s0, P)) return rc;
+    if (!chained && !env->view.big && env->ahead.slots > 0) {
+        // the run-ahead schedule, in passes of at most ahead.slots + 1 ticks (a pass ends with every stream joined)
+        const int per = env->ahead.slots + 1 < kAheadTicks ? env->ahead.slots + 1 : kAheadTicks;
         std::vector<const float*> a((size_t)per);
         for (int k0 = 0; k0 < num_ticks; k0 += per) {
             const int K = num_ticks - k0 < per ? num_ticks - k0 : per;
@@ -1055,8 +1067,6 @@ int mrca_step_many(mrca_env* env, const float* const* actions_dev, int32_t num_a
             if (int rc = step_impl(env, act(k), 0, env->view.N, stream)) return rc;
         return MRCA_OK;
     }
-    auto stream_of = [&](int c) { return c == 0 ? s0 : env->chain_stream[c - 1]; };
-    auto first_world = [&](int c) { return (int)((int64_t)c * W / P); };
     // (fork: range c's stream starts behind range c - 1's FIRST move launch -- which sits behind everything queued on the caller's
     // stream before this call, so that one wait is the fork AND the half tick between the ranges; the first launch of the call
     // goes out before any event is touched)
@@ -1066,26 +1076,21 @@ int mrca_step_many(mrca_env* env, const float* const* actions_dev, int32_t num_a
     for (int k = 0; k < num_ticks && rc == MRCA_OK && herr == hipSuccess; ++k) {
         const float* a = act(k);
         for (int c = 0; c < P; ++c) {
-            hipStream_t sc = stream_of(c);
-            const int w0 = first_world(c), wn = first_world(c + 1) - w0;
+            hipStream_t sc = range_stream(env, s0, c);
+            const int w0 = range_first_world(W, P, c), wn = range_first_world(W, P, c + 1) - w0;
             // half a tick behind the previous range, once: its first move launch has finished, its first ray cast is starting
             if (k == 0 && c > 0) {
-                herr = hipStreamWaitEvent(sc, env->chain_moved[c - 1], 0);
+                herr = hipStreamWaitEvent(sc, env->ranges[c - 1].moved.get(), 0);
                 if (herr != hipSuccess) break;
                 forked = c + 1;
             }
             if ((rc = worlds_impl(env, a, w0, wn, sc, kPhaseMove))) break;
-            if (k == 0 && c + 1 < P && (herr = hipEventRecord(env->chain_moved[c], sc)) != hipSuccess) break;
+            if (k == 0 && c + 1 < P && (herr = hipEventRecord(env->ranges[c].moved.get(), sc)) != hipSuccess) break;
             if ((rc = worlds_impl(env, nullptr, w0, wn, sc, kPhaseObserve))) break;
         }
     }
-    // join: the caller's stream continues when every range is through -- on the error paths too (a forked stream left
-    // unjoined would dangle from a capture, and its launches would race the caller's next call)
-    for (int c = 1; c < forked; ++c) {
-        hipError_t e1 = hipEventRecord(env->chain_done[c - 1], stream_of(c));
-        hipError_t e2 = hipStreamWaitEvent(s0, env->chain_done[c - 1], 0);
-        if (herr == hipSuccess) herr = e1 != hipSuccess ? e1 : e2;
-    }
+    const hipError_t jerr = join_ranges(env, s0, forked);      // (on the error paths too)
+    if (herr == hipSuccess) herr = jerr;
     if (rc != MRCA_OK) return rc;
     if (herr != hipSuccess) return fail(MRCA_ERR_HIP, "mrca_step_many: %s", hipGetErrorString(herr));
     return MRCA_OK;
@@ -1190,8 +1195,9 @@ int mrca_gae(const float* rewards_dev, const float* values_dev, const float* las
 int mrca_enable_timing(mrca_env* env, int32_t on) {
     if (!env) return fail(MRCA_ERR_INVALID, "env is NULL");
     if (on && env->ev.empty()) {
-        env->ev.resize(4 * kTimingRing);
-        for (auto& e : env->ev) HIP_TRY(hipEventCreate(&e));
+        std::vector<Event> ev(4 * kTimingRing);     // (the env's only when every one exists)
+        for (Event& e : ev) HIP_TRY(make_event(&e, hipEventDefault));
+        env->ev = std::move(ev);
     }
     env->timing = on > 0 ? on : 0;
     env->step_count = 0;
@@ -1212,21 +1218,18 @@ int mrca_event_pair_overhead(void* stream, int32_t samples, float* us_out) {
         HIP_TRY(hipGetDevice(&dev));
     }
     DeviceGuard guard(dev);
-    hipEvent_t a = nullptr, b = nullptr;
-    HIP_TRY(hipEventCreate(&a));
-    hipError_t err = hipEventCreate(&b);
+    Event a, b;
+    HIP_TRY(make_event(&a, hipEventDefault));
+    HIP_TRY(make_event(&b, hipEventDefault));
     double sum = 0.0;
-    for (int i = 0; err == hipSuccess && i < samples; ++i) {
+    for (int i = 0; i < samples; ++i) {
         float ms = 0.0f;
-        if ((err = hipEventRecord(a, s)) != hipSuccess) break;
-        if ((err = hipEventRecord(b, s)) != hipSuccess) break;
-        if ((err = hipEventSynchronize(b)) != hipSuccess) break;
-        if ((err = hipEventElapsedTime(&ms, a, b)) != hipSuccess) break;
+        HIP_TRY(hipEventRecord(a.get(), s));
+        HIP_TRY(hipEventRecord(b.get(), s));
+        HIP_TRY(hipEventSynchronize(b.get()));
+        HIP_TRY(hipEventElapsedTime(&ms, a.get(), b.get()));
         sum += ms;
     }
-    (void)hipEventDestroy(a);          // on every path
-    if (b) (void)hipEventDestroy(b);
-    if (err != hipSuccess) return fail(MRCA_ERR_HIP, "mrca_event_pair_overhead: %s", hipGetErrorString(err));
     *us_out = (float)(sum / samples * 1e3);
     return MRCA_OK;
 }
@@ -1255,9 +1258,7 @@ int mrca_set_debug_flags(mrca_env* env, int32_t flags) {
     HIP_TRY(upload_view(env));            // move_kernel / raycast_kernel read the switches from the device copy
     return MRCA_OK;
 }
-#endif
 
-#if defined(MRCA_PROFILING)
 // Profiling build only: average s_memtime ticks between the move kernel's phase stamps (0 -> 1 ... 7 -> 8) over the worlds
 // of the LAST launch (synchronises the device).
 int mrca_debug_move_stamps(mrca_env* env, double* avg_ticks_out /* [9]: 8 deltas + entry-to-end */) {
@@ -1277,9 +1278,7 @@ int mrca_debug_move_stamps(mrca_env* env, double* avg_ticks_out /* [9]: 8 deltas
     avg_ticks_out[8] = sum / W;
     return MRCA_OK;
 }
-#endif
 
-#if defined(MRCA_PROFILING)
 // Profiling build only: the raw stamps of the LAST move launch, out[k * worlds + w] = stamp k (0..8) of world w -- for the
 // DISTRIBUTION over worlds (a launch lasts as long as its slowest world): tools/move_tail.py
 int mrca_debug_move_stamps_raw(mrca_env* env, unsigned long long* out /* [10 * worlds] */, int32_t* worlds_out) {
@@ -1291,9 +1290,7 @@ int mrca_debug_move_stamps_raw(mrca_env* env, unsigned long long* out /* [10 * w
     *worlds_out = W;
     return MRCA_OK;
 }
-#endif
 
-#if defined(MRCA_PROFILING)
 // Profiling build only: s_memtime stamps of the LAST ray-cast launch (synchronises the device).  out[w * 7 + k], w = 0, 1
 // (wave 0 prepares the neighbour list, wave 1 only marches), k = 0..6: mean over workgroups of stamp k minus the
 // workgroup's entry stamp; out[14..16] = 0 (reserved).
@@ -1323,11 +1320,11 @@ int mrca_read_timing(mrca_env* env, float* move_ms_total, float* ray_ms_total, i
     if (!env) return fail(MRCA_ERR_INVALID, "env is NULL");
     float mv = 0.0f, ry = 0.0f;
     const int n = env->ev_used / 4;
-    if (n > 0) HIP_TRY(hipEventSynchronize(env->ev[env->ev_used - 1]));
+    if (n > 0) HIP_TRY(hipEventSynchronize(env->ev[env->ev_used - 1].get()));
     for (int i = 0; i < n; ++i) {
         float a = 0.0f, b = 0.0f;
-        HIP_TRY(hipEventElapsedTime(&a, env->ev[4 * i], env->ev[4 * i + 1]));
-        HIP_TRY(hipEventElapsedTime(&b, env->ev[4 * i + 2], env->ev[4 * i + 3]));
+        HIP_TRY(hipEventElapsedTime(&a, env->ev[4 * i].get(), env->ev[4 * i + 1].get()));
+        HIP_TRY(hipEventElapsedTime(&b, env->ev[4 * i + 2].get(), env->ev[4 * i + 3].get()));
         mv += a;
         ry += b;
     }

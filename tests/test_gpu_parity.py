@@ -352,6 +352,78 @@ def test_step_many_from_alternating_caller_streams(hip):
     env.close()
 
 
+def test_step_many_checks_a_caller_stream_again_for_more_ranges(hip, monkeypatch, capfd):
+    """The stream check keeps, per caller's stream, how many world ranges it covered: calls of chains 2 on A,
+    3 on B, 2 on A, 3 on A -- A's last call is checked again, B's check for three ranges says nothing about A.  A's second call
+    is checked again only if B's check had to park one of the env's streams (that voids every record).  MRCA_DEBUG_STREAMS
+    prints one line per check (the library reads it at every check)."""
+    import re
+    import bench
+    monkeypatch.setenv("MRCA_DEBUG_STREAMS", "1")
+    sc = S.stage1(num_worlds=6, robots_per_world=16, seed=43)
+    env = hip.VecStageWorld(sc)
+    ora = U.COracleEnv(sc)
+    pool = bench.action_pool(sc.num_robots, env.device, 17, depth=32)
+    host_pool = [a.cpu().numpy() for a in pool]
+    env.reset()
+    ora.reset()
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Stream(), torch.cuda.Stream()
+    capfd.readouterr()
+    checks, k, prev = [], 0, torch.cuda.current_stream()
+    for s, chains in ((a, 2), (b, 3), (a, 2), (a, 3)):
+        s.wait_stream(prev)
+        with torch.cuda.stream(s):
+            env.step_many(pool, k, 8, chains)
+        prev = s
+        for j in range(8):
+            ora.step(host_pool[k + j])
+        k += 8
+        checks.append([ln for ln in capfd.readouterr().err.splitlines() if ln.startswith("[mrca] stream check")])
+    torch.cuda.synchronize()
+
+    def against(line, s, ranges):
+        return f"against {hex(s.cuda_stream)}: {ranges} range stream(s)" in line
+
+    def parked(line):
+        return int(re.search(r"(\d+) candidate\(s\) parked", line).group(1))
+
+    assert [len(c) for c in checks[:2]] == [1, 1] and len(checks[3]) == 1, checks
+    assert against(checks[0][0], a, 1) and against(checks[1][0], b, 2), checks
+    assert len(checks[2]) == (1 if parked(checks[1][0]) > parked(checks[0][0]) else 0), checks
+    assert against(checks[3][0], a, 2), checks       # the stale record: A was checked for two ranges only
+    env.invalidate_views()
+    U.assert_state_equal(U.HostView(env), ora, what="32 ticks from two caller streams and two range counts")
+    env.check()
+    env.close()
+
+
+def test_env_teardown_returns_its_device_memory(hip):
+    """mrca_destroy releases what an env holds beside its arena -- the run-ahead ring (the library's own allocation), the view
+    copy, the probe buffer, the streams and events: create / step_many of three world ranges (a range added at first use, the
+    stream check) / close, 20 times over, leaves the device's free memory where one such cycle left it."""
+    import gc
+    import bench
+    sc = S.stage1(num_worlds=128, robots_per_world=32, seed=5)      # 4096 robots: a ring of 255 slots, 256 move events
+    pool = bench.action_pool(sc.num_robots, torch.device("cuda"), 19, depth=4)
+
+    def cycle():
+        env = hip.VecStageWorld(sc)
+        env.reset()
+        env.step_many(pool, 0, 4, 3)
+        env.check()
+        env.close()
+        del env
+        gc.collect()
+        torch.cuda.synchronize()
+        torch.cuda.empty_cache()
+        return torch.cuda.mem_get_info()[0]
+
+    first = cycle()
+    free = [cycle() for _ in range(20)]
+    assert all(abs(f - first) <= 4 << 20 for f in free), [(f - first) >> 20 for f in free]
+
+
 def test_world_range_calls_leave_the_other_worlds_alone(hip):
     """mrca_step_worlds / mrca_move_worlds / mrca_observe_worlds: only the worlds of the range tick; a world stepped alone
     ends where the same world of a fully stepped env ends."""
