@@ -1011,6 +1011,10 @@ MRCA_HD int hash_cell_coord(float x, float cs) { return (int)floorf(x * (1.0f / 
 MRCA_HD uint32_t hash_cell(int ix, int iy, int world) {
     return ((uint32_t)ix * 73856093u) ^ ((uint32_t)iy * 19349663u) ^ ((uint32_t)world * 83492791u);
 }
+// the bucket of the point (x, y) of `world` in a hash of cs-metre cells with mask + 1 buckets
+MRCA_HD uint32_t hash_bucket(float x, float y, float cs, int world, int mask) {
+    return hash_cell(hash_cell_coord(x, cs), hash_cell_coord(y, cs), world) & (uint32_t)mask;
+}
 
 // ------------------------------------------------------------------------------------------
 // reset_pose / generate_goal_point
@@ -1078,6 +1082,121 @@ MRCA_HD void sample_goal(int mode, uint32_t gid, uint32_t episode, uint32_t k0, 
                          float* gx, float* gy) {
     for (int k = 0; k < kMaxTriesGoal; ++k)
         if (goal_try(mode, gid, episode, (uint32_t)k, k0, k1, curx, cury, gx, gy) || k == kMaxTriesGoal - 1) return;
+}
+
+// ------------------------------------------------------------------------------------------
+// The rules that decide what a tick does to ONE robot, over plain values.  move_kernel, the bw_* kernels, reset_kernel and
+// the host build (tests/host_emul) all call these: the CPU comparison with the oracle runs the kernels' own statement of them.
+
+// Command latch + explicit Euler step with the heading (s, c) at tick start (stageros.cpp:445-449).  A robot whose script no
+// longer sends cmd_vel (dead, ppo_stage2.py:72-74) idles, or -- hold_velocity, what Stage does with the last SetSpeed --
+// keeps driving at the command it was given last (held_v, held_w).
+struct Motion {
+    float v, w;                   // the latched command
+    float nx, ny, nth, ns, nc;    // the provisional pose, sin / cos of its heading
+    bool moving;
+};
+MRCA_HD Motion latch_and_integrate(bool live, float act_v, float act_w, bool hold_velocity, float held_v, float held_w,
+                                   float x, float y, float th, float s, float c) {
+    Motion m;
+    m.v = live ? sane_cmd(act_v) : (hold_velocity ? held_v : 0.0f);
+    m.w = live ? sane_cmd(act_w) : (hold_velocity ? held_w : 0.0f);
+    const float d = m.v * kDt;
+    m.nx = x + d * c;
+    m.ny = y + d * s;
+    m.nth = wrap_angle(th + m.w * kDt);
+    sincos_det(m.nth, &m.ns, &m.nc);
+    m.moving = (m.v != 0.0f) || (m.w != 0.0f);
+    return m;
+}
+
+// After the collision pass: GT velocity = finite difference of the pose (stageros.cpp:585-590), reward / terminal
+// (stage_world1.py:180-211) at the settled pose (x, y).  Both terminals on one tick are kept (arrive + crash = 0), the result
+// takes timeout over crash over reach, first_result is latched once, and only a live robot's books move.
+struct Settled {
+    bool done_now;
+    float vgt, wgt;
+};
+MRCA_HD Settled settle_robot(bool live, bool moved, float v, float w, float x, float y, float gx, float gy, uint8_t crashed,
+                             float w_thresh, int timeout, float& prev_dist, int& t, float& reward, uint8_t& done,
+                             uint8_t& result, uint8_t& first_result) {
+    Settled o;
+    o.vgt = moved ? fabsf(v) : 0.0f;
+    o.wgt = moved ? w : 0.0f;
+    const float ddx = gx - x, ddy = gy - y;
+    const float dist = sqrtf(ddx * ddx + ddy * ddy);
+    float rg = (prev_dist - dist) * kKProgress;
+    const bool reach = dist < kGoalRadius;
+    rg = reach ? kRArrive : rg;
+    const bool crash = crashed == 1;
+    const float rc = crash ? kRCrash : 0.0f;
+    const float aw = fabsf(o.wgt);
+    const float rw = (aw > w_thresh) ? kKOmega * aw : 0.0f;
+    const bool tout = t > timeout;
+    uint8_t r = reach ? 1 : 0;
+    r = crash ? 2 : r;
+    r = tout ? 3 : r;
+    o.done_now = reach || crash || tout;
+    if (live) {
+        reward = (rg + rc) + rw;
+        done = o.done_now ? 1 : 0;
+        result = r;
+        prev_dist = dist;
+        t = t + 1;
+        if (o.done_now && first_result == 0) first_result = r;
+    }
+    return o;
+}
+
+// How episodes start: the scenario's tables per local robot index, the Philox key, two switches.
+struct EpisodeRules {
+    const int32_t* reset_mode;
+    const int32_t* goal_mode;
+    const float* init_table;   // [R,3]
+    const float* goal_table;   // [R,2]
+    uint32_t key0, key1;
+    int32_t pre_dist_zero, hold_velocity;
+};
+
+// Pose and goal of robot n's episode `episode` (ppo_stage1.py:51-58), one lane: the caller's override, the table row (mode 0)
+// or the first acceptable draw.  (curx, cury): where the robot stands now (region mode keeps away from it).
+MRCA_HD void begin_episode(const EpisodeRules& r, int n, int local, uint32_t episode, float curx, float cury,
+                           const float* pose_override, const float* goal_override, float* x, float* y, float* th, float* gx,
+                           float* gy) {
+    const int mode = r.reset_mode[local], gmode = r.goal_mode[local];
+    if (pose_override) {
+        *x = pose_override[0];
+        *y = pose_override[1];
+        *th = pose_override[2];
+    } else if (mode == 0) {
+        *x = r.init_table[local * 3 + 0];
+        *y = r.init_table[local * 3 + 1];
+        *th = wrap_angle(r.init_table[local * 3 + 2]);
+    } else {
+        sample_pose(mode, (uint32_t)n, episode, r.key0, r.key1, curx, cury, x, y, th);
+    }
+    if (goal_override) {
+        *gx = goal_override[0];
+        *gy = goal_override[1];
+    } else if (gmode == 0) {
+        *gx = r.goal_table[local * 2 + 0];
+        *gy = r.goal_table[local * 2 + 1];
+    } else {
+        sample_goal(gmode, (uint32_t)n, episode, r.key0, r.key1, *x, *y, gx, gy);
+    }
+}
+
+// What a new episode sets besides pose and goal.  (hold_velocity: the odom twist survives the teleport.)
+MRCA_HD void open_episode(const EpisodeRules& r, float x, float y, float gx, float gy, float& prev_dist, int& t,
+                          uint8_t& crashed, uint8_t& live, float& speed_v, float& speed_w, float& gt_v, float& gt_w) {
+    const float ddx = gx - x, ddy = gy - y;
+    const float d = sqrtf(ddx * ddx + ddy * ddy);
+    prev_dist = r.pre_dist_zero ? 0.0f : d;
+    t = 1;
+    crashed = 0;
+    live = 1;
+    gt_v = gt_w = 0.0f;
+    if (!r.hold_velocity) speed_v = speed_w = 0.0f;
 }
 
 }  // namespace mrca

@@ -25,6 +25,11 @@
 //   reset_kernel   explicit reset_pose / control_pose / generate_goal_point.
 //   gae_kernel     reverse GAE scan, thread per robot, coalesced over N.
 //
+// What a tick does to ONE robot is stated once, in mrca_device.h, and called from here: latch_and_integrate (move_kernel,
+// bw_integrate_kernel), settle_robot (move_kernel, bw_finish_kernel), begin_episode (reset_kernel, bw_finish_kernel;
+// move_kernel samples wave-parallel -- group_sample_* below, the same draw) and open_episode (all three).  The host build of
+// that header (tests/host_emul) runs the same functions against the oracle.
+//
 // No dense contraction anywhere in the environment: MFMA is deliberately unused here (BASELINE.json north_star); the
 // policy's conv front end (mrca_policy.hip) is where it is used.
 #include "mrca_kernels.h"
@@ -40,49 +45,35 @@ constexpr int kPatchLoads = 6;   // independent patch-word loads a thread of mov
 constexpr int kMoveWaves = 4;    // wavefronts per world in move_kernel
 constexpr int kEventOutlineTasks = 3 * kWave * kMoveWaves;   // outline test by events up to three passes of the block's threads, else by walks
 
-__device__ __forceinline__ void begin_episode(const EnvView& e, int n, int local, float curx, float cury, float* px,
-                                              float* py, float* pth, float* gx, float* gy, float* pdist,
-                                              const float* pose_override, const float* goal_override) {
-    const uint32_t ep = (uint32_t)e.episode[n];
-    float x, y, th;
-    if (pose_override) {
-        x = pose_override[0];
-        y = pose_override[1];
-        th = pose_override[2];
-    } else {
-        const int mode = e.reset_mode[local];
-        if (mode == 0) {
-            x = e.init_table[local * 3 + 0];
-            y = e.init_table[local * 3 + 1];
-            th = wrap_angle(e.init_table[local * 3 + 2]);
-        } else {
-            sample_pose(mode, (uint32_t)n, ep, e.key0, e.key1, curx, cury, &x, &y, &th);
-        }
-    }
-    float qx, qy;
-    if (goal_override) {
-        qx = goal_override[0];
-        qy = goal_override[1];
-    } else {
-        const int gmode = e.goal_mode[local];
-        if (gmode == 0) {
-            qx = e.goal_table[local * 2 + 0];
-            qy = e.goal_table[local * 2 + 1];
-        } else {
-            sample_goal(gmode, (uint32_t)n, ep, e.key0, e.key1, x, y, &qx, &qy);
-        }
-    }
-    const float ddx = qx - x, ddy = qy - y;
-    const float d = sqrtf(ddx * ddx + ddy * ddy);
-    *px = x;
-    *py = y;
-    *pth = th;
-    *gx = qx;
-    *gy = qy;
-    *pdist = e.pre_dist_zero ? 0.0f : d;
-    e.init_pose[n * 3 + 0] = x;
-    e.init_pose[n * 3 + 1] = y;
-    e.init_pose[n * 3 + 2] = th;
+__device__ __forceinline__ EpisodeRules episode_rules(const EnvView& e) {
+    return EpisodeRules{e.reset_mode, e.goal_mode, e.init_table, e.goal_table, e.key0, e.key1, e.pre_dist_zero, e.hold_velocity};
+}
+
+// the per-robot stores that end a tick (move_kernel, bw_finish_kernel)
+__device__ __forceinline__ void store_robot(const EnvView& e, int n, float x, float y, float th, float sp_v, float sp_w,
+                                            float gt_v, float gt_w, float gx, float gy, float prev_dist, int t, float reward,
+                                            uint8_t done, uint8_t result, uint8_t first_result, uint8_t crashed, uint8_t live,
+                                            int episode, bool fresh, float s, float c, uint32_t cellv, uint32_t cellw) {
+    e.pose[n * 3 + 0] = x;
+    e.pose[n * 3 + 1] = y;
+    e.pose[n * 3 + 2] = th;
+    e.speed[n * 2 + 0] = sp_v;
+    e.speed[n * 2 + 1] = sp_w;
+    e.speed_gt[n * 2 + 0] = gt_v;
+    e.speed_gt[n * 2 + 1] = gt_w;
+    e.goal[n * 2 + 0] = gx;
+    e.goal[n * 2 + 1] = gy;
+    e.prev_dist[n] = prev_dist;
+    e.t[n] = t;
+    e.reward[n] = reward;
+    e.done[n] = done;
+    e.result[n] = result;
+    e.first_result[n] = first_result;
+    e.crashed[n] = crashed;
+    e.live[n] = live;
+    e.episode[n] = episode;
+    e.fresh[n] = fresh ? 1 : 0;
+    e.head[n] = make_float4(s, c, __uint_as_float(cellv), __uint_as_float(cellw));
 }
 
 // lane must be wave-uniform: v_readlane_b32
@@ -331,26 +322,16 @@ __global__ __launch_bounds__(kWave * kMoveWaves) void move_kernel(int R_, int wo
     const bool raster = e.raster_inv > 0.0f;
     OutlineBits ob_old{0, 0, 0u, 0u};
     if (raster) ob_old = outline_p[n];
-    // a robot whose script no longer sends cmd_vel (dead, ppo_stage2.py:72-74): idles, or -- hold_velocity, what Stage
-    // does with the last SetSpeed -- keeps driving at the command it was given last
-    float held_v = 0.0f, held_w = 0.0f;
+    float held_v = 0.0f, held_w = 0.0f;     // (the last command: read only where a dead robot keeps driving at it)
     if (e.hold_velocity) {
         held_v = e.speed[n * 2 + 0];
         held_w = e.speed[n * 2 + 1];
     }
-    const float v = live ? sane_cmd(act_v) : held_v;
-    const float w = live ? sane_cmd(act_w) : held_w;
-
-    // integrate: explicit Euler with the heading at tick start
     float s = hd.x, c = hd.y;
     uint32_t cellv = __float_as_uint(hd.z), cellw = __float_as_uint(hd.w);
-    const float d = v * kDt;
-    const float nx = x + d * c;
-    const float ny = y + d * s;
-    const float nth = wrap_angle(th + w * kDt);
-    float ns, nc;
-    sincos_det(nth, &ns, &nc);
-    const bool moving = valid && ((v != 0.0f) || (w != 0.0f));
+    const Motion mo = latch_and_integrate(live, act_v, act_w, e.hold_velocity != 0, held_v, held_w, x, y, th, s, c);
+    const float v = mo.v, w = mo.w, nx = mo.nx, ny = mo.ny, nth = mo.nth, ns = mo.ns, nc = mo.nc;
+    const bool moving = valid && mo.moving;
     MRCA_STAMP(1);      // state loaded, integrated
 
     // --- outline-vs-grid test.  Skipped (same answer: free) when the coarse free-distance field says
@@ -585,34 +566,11 @@ __global__ __launch_bounds__(kWave * kMoveWaves) void move_kernel(int R_, int wo
     }
 
     MRCA_STAMP(5);      // ordered collision pass done
-    // GT velocity = finite difference of the pose (stageros.cpp:585-590)
-    const float vgt = moved ? fabsf(v) : 0.0f;
-    const float wgt = moved ? w : 0.0f;
-
-    // reward / terminal (stage_world1.py:180-211)
-    const float ddx = gx - x, ddy = gy - y;
-    const float dist = sqrtf(ddx * ddx + ddy * ddy);
-    float rg = (pdist - dist) * kKProgress;
-    const bool reach = dist < kGoalRadius;
-    rg = reach ? kRArrive : rg;
-    const bool crash = crashed == 1;
-    const float rc = crash ? kRCrash : 0.0f;
-    const float aw = fabsf(wgt);
-    const float rw = (aw > e.w_thresh) ? kKOmega * aw : 0.0f;
-    const bool tout = t > e.timeout;
-    uint8_t result = reach ? 1 : 0;
-    result = crash ? 2 : result;
-    result = tout ? 3 : result;
-    const bool done_now = reach || crash || tout;
+    // GT velocity, reward / terminal
+    const Settled st = settle_robot(live, moved, v, w, x, y, gx, gy, crashed, e.w_thresh, e.timeout, pdist, t, reward, done, res,
+                                    first);
+    const bool done_now = st.done_now;
     uint8_t lv = live ? 1 : 0;
-    if (live) {
-        reward = (rg + rc) + rw;
-        done = done_now ? 1 : 0;
-        res = result;
-        pdist = dist;
-        t = t + 1;
-        if (done_now && first == 0) first = result;
-    }
 
     // episode bookkeeping
     bool fresh = false;
@@ -627,7 +585,7 @@ __global__ __launch_bounds__(kWave * kMoveWaves) void move_kernel(int R_, int wo
             if (in && members == finished) fresh = true;
         }
     }
-    float spv = v, spw = w, ovgt = vgt, owgt = wgt;
+    float spv = v, spw = w, ovgt = st.vgt, owgt = st.wgt;
     if (MRCA_DBG(e, 32)) fresh = false;
     MRCA_STAMP(6);      // reward / terminal / group ballots done
     // new episodes, FOUR robots per round: group g = lane / 16 samples for the g-th lowest restarting robot of the round
@@ -666,17 +624,10 @@ __global__ __launch_bounds__(kWave * kMoveWaves) void move_kernel(int R_, int wo
             th = rpth;
             gx = rqx;
             gy = rqy;
-            const float ex = rqx - rpx, ey = rqy - rpy;
-            const float d0 = sqrtf(ex * ex + ey * ey);
-            pdist = e.pre_dist_zero ? 0.0f : d0;
             e.init_pose[n * 3 + 0] = rpx;
             e.init_pose[n * 3 + 1] = rpy;
             e.init_pose[n * 3 + 2] = rpth;
-            t = 1;
-            crashed = 0;
-            lv = 1;
-            ovgt = owgt = 0.0f;
-            if (!e.hold_velocity) spv = spw = 0.0f;   // hold_velocity: the odom twist survives the teleport
+            open_episode(episode_rules(e), rpx, rpy, rqx, rqy, pdist, t, crashed, lv, spv, spw, ovgt, owgt);
         }
     }
     // head records of the new poses, for every restarted robot AT ONCE: inside the loop above the field entry of each new
@@ -708,26 +659,8 @@ __global__ __launch_bounds__(kWave * kMoveWaves) void move_kernel(int R_, int wo
 
     MRCA_STAMP(7);      // restarts done
     if (valid) {
-        e.pose[n * 3 + 0] = x;
-        e.pose[n * 3 + 1] = y;
-        e.pose[n * 3 + 2] = th;
-        e.speed[n * 2 + 0] = spv;
-        e.speed[n * 2 + 1] = spw;
-        e.speed_gt[n * 2 + 0] = ovgt;
-        e.speed_gt[n * 2 + 1] = owgt;
-        e.goal[n * 2 + 0] = gx;
-        e.goal[n * 2 + 1] = gy;
-        e.prev_dist[n] = pdist;
-        e.t[n] = t;
-        e.reward[n] = reward;
-        e.done[n] = done;
-        e.result[n] = res;
-        e.first_result[n] = first;
-        e.crashed[n] = crashed;
-        e.live[n] = lv;
-        e.episode[n] = ep;
-        e.fresh[n] = fresh ? 1 : 0;
-        e.head[n] = make_float4(s, c, __uint_as_float(cellv), __uint_as_float(cellw));
+        store_robot(e, n, x, y, th, spv, spw, ovgt, owgt, gx, gy, pdist, t, reward, done, res, first, crashed, lv, ep, fresh, s, c,
+                    cellv, cellw);
         if (raster) e.outline[n] = ob_cur;
     }
     MRCA_STAMP(8);      // stores drained
@@ -763,25 +696,18 @@ __global__ void reset_kernel(EnvView e, const uint8_t* __restrict__ mask, const 
     if (!sel) return;
     const int local = n % e.R;
     e.episode[n] += 1;
-    float x, y, th, gx, gy, pd;
-    begin_episode(e, n, local, e.pose[n * 3 + 0], e.pose[n * 3 + 1], &x, &y, &th, &gx, &gy, &pd,
-                  poses ? poses + n * 3 : nullptr, goals ? goals + n * 2 : nullptr);
-    e.pose[n * 3 + 0] = x;
-    e.pose[n * 3 + 1] = y;
-    e.pose[n * 3 + 2] = th;
+    const EpisodeRules rules = episode_rules(e);
+    float x, y, th, gx, gy;
+    begin_episode(rules, n, local, (uint32_t)e.episode[n], e.pose[n * 3 + 0], e.pose[n * 3 + 1], poses ? poses + n * 3 : nullptr,
+                  goals ? goals + n * 2 : nullptr, &x, &y, &th, &gx, &gy);
+    e.pose[n * 3 + 0] = e.init_pose[n * 3 + 0] = x;
+    e.pose[n * 3 + 1] = e.init_pose[n * 3 + 1] = y;
+    e.pose[n * 3 + 2] = e.init_pose[n * 3 + 2] = th;
     write_head(e, n, x, y, th);
     e.goal[n * 2 + 0] = gx;
     e.goal[n * 2 + 1] = gy;
-    e.prev_dist[n] = pd;
-    e.t[n] = 1;
-    e.crashed[n] = 0;
-    e.live[n] = 1;
-    if (!e.hold_velocity) {
-        e.speed[n * 2 + 0] = 0.0f;
-        e.speed[n * 2 + 1] = 0.0f;
-    }
-    e.speed_gt[n * 2 + 0] = 0.0f;
-    e.speed_gt[n * 2 + 1] = 0.0f;
+    open_episode(rules, x, y, gx, gy, e.prev_dist[n], e.t[n], e.crashed[n], e.live[n], e.speed[n * 2 + 0], e.speed[n * 2 + 1],
+                 e.speed_gt[n * 2 + 0], e.speed_gt[n * 2 + 1]);
     e.done[n] = 0;
     e.result[n] = 0;
     e.reward[n] = 0.0f;
@@ -1239,16 +1165,18 @@ __global__ void bw_integrate_kernel(EnvView e, const float* __restrict__ actions
     const float x = e.pose[n * 3 + 0], y = e.pose[n * 3 + 1], th = e.pose[n * 3 + 2];
     const float4 hd = e.head[n];
     const bool live = e.live[n] != 0;
-    const float v = live ? sane_cmd(actions[n * 2 + 0]) : (e.hold_velocity ? e.speed[n * 2 + 0] : 0.0f);
-    const float w = live ? sane_cmd(actions[n * 2 + 1]) : (e.hold_velocity ? e.speed[n * 2 + 1] : 0.0f);
-    const float s = hd.x, c = hd.y;
-    const float d = v * kDt;
-    const float nx = x + d * c;
-    const float ny = y + d * s;
-    const float nth = wrap_angle(th + w * kDt);
-    float ns, nc;
-    sincos_det(nth, &ns, &nc);
-    const bool moving = (v != 0.0f) || (w != 0.0f);
+    // (a robot's command is read from one place only: its action, or -- dead under hold_velocity -- its last one)
+    float act_v = 0.0f, act_w = 0.0f, held_v = 0.0f, held_w = 0.0f;
+    if (live) {
+        act_v = actions[n * 2 + 0];
+        act_w = actions[n * 2 + 1];
+    } else if (e.hold_velocity) {
+        held_v = e.speed[n * 2 + 0];
+        held_w = e.speed[n * 2 + 1];
+    }
+    const Motion mo = latch_and_integrate(live, act_v, act_w, e.hold_velocity != 0, held_v, held_w, x, y, th, hd.x, hd.y);
+    const float v = mo.v, w = mo.w, nx = mo.nx, ny = mo.ny, nth = mo.nth, ns = mo.ns, nc = mo.nc;
+    const bool moving = mo.moving;
     // outline-vs-grid test: free for sure when the footprint's patch lies outside the map (cells outside are
     // free) or the distance field clears it; otherwise the four outline edges are walked in the bitmap
     const int hc = e.foot_hc;
@@ -1266,16 +1194,8 @@ __global__ void bw_integrate_kernel(EnvView e, const float* __restrict__ actions
     e.bw_prov[2 * n + 1] = make_float4(ns, nc, v, w);
     e.bw_state[n] = moving ? 0 : 1;
     const int world = n / e.R;
-    {
-        const uint32_t h = hash_cell(hash_cell_coord(x, kCollideCell), hash_cell_coord(y, kCollideCell), world) &
-                           (uint32_t)e.bw_cmask;
-        e.bw_cnext[2 * n] = atomicExch(&e.bw_chead[h], 2 * n);
-    }
-    if (moving) {
-        const uint32_t h = hash_cell(hash_cell_coord(nx, kCollideCell), hash_cell_coord(ny, kCollideCell), world) &
-                           (uint32_t)e.bw_cmask;
-        e.bw_cnext[2 * n + 1] = atomicExch(&e.bw_chead[h], 2 * n + 1);
-    }
+    e.bw_cnext[2 * n] = atomicExch(&e.bw_chead[hash_bucket(x, y, kCollideCell, world, e.bw_cmask)], 2 * n);
+    if (moving) e.bw_cnext[2 * n + 1] = atomicExch(&e.bw_chead[hash_bucket(nx, ny, kCollideCell, world, e.bw_cmask)], 2 * n + 1);
 }
 
 __global__ void bw_collide_kernel(EnvView e) {
@@ -1405,103 +1325,35 @@ __global__ void bw_finish_kernel(EnvView e) {
     float reward = e.reward[n];
     uint8_t done = e.done[n], res = e.result[n], first = e.first_result[n], crashed = e.crashed[n];
     int ep = e.episode[n];
+    // the collision hash is per tick: every robot empties the (at most two) buckets it filled, so the next tick needs
+    // no 4N-entry memset  (up here: the two centres are not kept alive to the end of the kernel for it)
+    const int world = n / e.R;
+    e.bw_chead[hash_bucket(ox0, oy0, kCollideCell, world, e.bw_cmask)] = -1;
+    if (flags & kFlagMoving) e.bw_chead[hash_bucket(p0.x, p0.y, kCollideCell, world, e.bw_cmask)] = -1;
 
-    // GT velocity = finite difference of the pose (stageros.cpp:585-590)
-    const float vgt = moved ? fabsf(v) : 0.0f;
-    const float wgt = moved ? w : 0.0f;
-    // reward / terminal (stage_world1.py:180-211)
-    const float ddx = gx - x, ddy = gy - y;
-    const float dist = sqrtf(ddx * ddx + ddy * ddy);
-    float rg = (pdist - dist) * kKProgress;
-    const bool reach = dist < kGoalRadius;
-    rg = reach ? kRArrive : rg;
-    const bool crash = crashed == 1;
-    const float rc = crash ? kRCrash : 0.0f;
-    const float aw = fabsf(wgt);
-    const float rw = (aw > e.w_thresh) ? kKOmega * aw : 0.0f;
-    const bool tout = t > e.timeout;
-    uint8_t result = reach ? 1 : 0;
-    result = crash ? 2 : result;
-    result = tout ? 3 : result;
-    const bool done_now = reach || crash || tout;
+    // GT velocity, reward / terminal
+    const Settled st = settle_robot(live, moved, v, w, x, y, gx, gy, crashed, e.w_thresh, e.timeout, pdist, t, reward, done, res,
+                                    first);
     uint8_t lv = live ? 1 : 0;
-    if (live) {
-        reward = (rg + rc) + rw;
-        done = done_now ? 1 : 0;
-        res = result;
-        pdist = dist;
-        t = t + 1;
-        if (done_now && first == 0) first = result;
-    }
-    float spv = v, spw = w, ovgt = vgt, owgt = wgt;
-    const bool fresh = e.auto_reset == 1 && live && done_now && !MRCA_DBG(e, 32);
+    float spv = v, spw = w, ovgt = st.vgt, owgt = st.wgt;
+    const bool fresh = e.auto_reset == 1 && live && st.done_now && !MRCA_DBG(e, 32);
     if (fresh) {   // new episode (ppo_stage1.py:51-58): the one-lane form of the sampling loops
+        const EpisodeRules rules = episode_rules(e);
         ep = ep + 1;
-        const int rm = e.reset_mode[local], gm = e.goal_mode[local];
-        float px, py, pth, qx, qy;
-        if (rm == 0) {
-            px = e.init_table[local * 3 + 0];
-            py = e.init_table[local * 3 + 1];
-            pth = wrap_angle(e.init_table[local * 3 + 2]);
-        } else {
-            sample_pose(rm, (uint32_t)n, (uint32_t)ep, e.key0, e.key1, x, y, &px, &py, &pth);
-        }
-        if (gm == 0) {
-            qx = e.goal_table[local * 2 + 0];
-            qy = e.goal_table[local * 2 + 1];
-        } else {
-            sample_goal(gm, (uint32_t)n, (uint32_t)ep, e.key0, e.key1, px, py, &qx, &qy);
-        }
-        x = px;
-        y = py;
-        th = pth;
-        sincos_det(pth, &s, &c);
-        gx = qx;
-        gy = qy;
-        const float ex = qx - px, ey = qy - py;
-        pdist = e.pre_dist_zero ? 0.0f : sqrtf(ex * ex + ey * ey);
-        e.init_pose[n * 3 + 0] = px;
-        e.init_pose[n * 3 + 1] = py;
-        e.init_pose[n * 3 + 2] = pth;
-        t = 1;
-        crashed = 0;
-        lv = 1;
-        ovgt = owgt = 0.0f;
-        if (!e.hold_velocity) spv = spw = 0.0f;
+        begin_episode(rules, n, local, (uint32_t)ep, x, y, nullptr, nullptr, &x, &y, &th, &gx, &gy);
+        sincos_det(th, &s, &c);
+        e.init_pose[n * 3 + 0] = x;
+        e.init_pose[n * 3 + 1] = y;
+        e.init_pose[n * 3 + 2] = th;
+        open_episode(rules, x, y, gx, gy, pdist, t, crashed, lv, spv, spw, ovgt, owgt);
     }
     const FreeRectField rect_field{e.free_rect, e.g.width, e.g.height, e.free_rect_pitch};
     uint32_t cellv, cellw;
     rect_field.cell((int)floorf((x - e.g.x0) * e.g.inv_cell), (int)floorf((y - e.g.y0) * e.g.inv_cell), &cellv, &cellw);
-    e.pose[n * 3 + 0] = x;
-    e.pose[n * 3 + 1] = y;
-    e.pose[n * 3 + 2] = th;
-    e.speed[n * 2 + 0] = spv;
-    e.speed[n * 2 + 1] = spw;
-    e.speed_gt[n * 2 + 0] = ovgt;
-    e.speed_gt[n * 2 + 1] = owgt;
-    e.goal[n * 2 + 0] = gx;
-    e.goal[n * 2 + 1] = gy;
-    e.prev_dist[n] = pdist;
-    e.t[n] = t;
-    e.reward[n] = reward;
-    e.done[n] = done;
-    e.result[n] = res;
-    e.first_result[n] = first;
-    e.crashed[n] = crashed;
-    e.live[n] = lv;
-    e.episode[n] = ep;
-    e.fresh[n] = fresh ? 1 : 0;
-    e.head[n] = make_float4(s, c, __uint_as_float(cellv), __uint_as_float(cellw));
-    // the collision hash is per tick: every robot empties the (at most two) buckets it filled, so the next tick needs
-    // no 4N-entry memset; and the lidar hash's population count of the FINAL pose rides here as well
-    const int world = n / e.R;
-    e.bw_chead[hash_cell(hash_cell_coord(ox0, kCollideCell), hash_cell_coord(oy0, kCollideCell), world) &
-               (uint32_t)e.bw_cmask] = -1;
-    if (flags & kFlagMoving)
-        e.bw_chead[hash_cell(hash_cell_coord(p0.x, kCollideCell), hash_cell_coord(p0.y, kCollideCell), world) &
-                   (uint32_t)e.bw_cmask] = -1;
-    atomicAdd(&e.bw_lcount[hash_cell(hash_cell_coord(x, kLidarCell), hash_cell_coord(y, kLidarCell), world) &
-                           (uint32_t)e.bw_lmask], 1);
+    store_robot(e, n, x, y, th, spv, spw, ovgt, owgt, gx, gy, pdist, t, reward, done, res, first, crashed, lv, ep, fresh, s, c, cellv,
+                cellw);
+    // the lidar hash's population count of the FINAL pose rides here as well
+    atomicAdd(&e.bw_lcount[hash_bucket(x, y, kLidarCell, world, e.bw_lmask)], 1);
 }
 
 // lidar hash = counting sort of the robots by the bucket of their (final) cell.  (Stand-alone count: after explicit
@@ -1509,8 +1361,7 @@ __global__ void bw_finish_kernel(EnvView e) {
 __global__ void bw_lidar_count_kernel(EnvView e) {
     const int n = blockIdx.x * blockDim.x + threadIdx.x;
     if (n >= e.N) return;
-    const uint32_t h = hash_cell(hash_cell_coord(e.pose[n * 3 + 0], kLidarCell), hash_cell_coord(e.pose[n * 3 + 1], kLidarCell),
-                                 n / e.R) & (uint32_t)e.bw_lmask;
+    const uint32_t h = hash_bucket(e.pose[n * 3 + 0], e.pose[n * 3 + 1], kLidarCell, n / e.R, e.bw_lmask);
     atomicAdd(&e.bw_lcount[h], 1);
 }
 
@@ -1567,8 +1418,7 @@ __global__ __launch_bounds__(1024) void bw_lidar_scan_apply_kernel(EnvView e) {
 __global__ void bw_lidar_fill_kernel(EnvView e) {
     const int n = blockIdx.x * blockDim.x + threadIdx.x;
     if (n >= e.N) return;
-    const uint32_t h = hash_cell(hash_cell_coord(e.pose[n * 3 + 0], kLidarCell), hash_cell_coord(e.pose[n * 3 + 1], kLidarCell),
-                                 n / e.R) & (uint32_t)e.bw_lmask;
+    const uint32_t h = hash_bucket(e.pose[n * 3 + 0], e.pose[n * 3 + 1], kLidarCell, n / e.R, e.bw_lmask);
     e.bw_lsorted[e.bw_lstart[h] + atomicAdd(&e.bw_lcursor[h], 1)] = n;
 }
 
@@ -1656,35 +1506,30 @@ void launch_move(const EnvView& e, const float* actions, hipStream_t s, hipEvent
     hipLaunchKernelGGL(bw_finish_kernel, dim3(nb), dim3(bs), 0, s, e);      // + the lidar hash's counts
 }
 
+// workgroups of 256 threads for a grid-stride loop over `total` items: one item per thread up to 8192 workgroups
+static dim3 stride_grid(long long total) {
+    const long long blocks = (total + 255) / 256;
+    return dim3((unsigned)(blocks > 8192 ? 8192 : blocks));
+}
+
 void launch_materialize(const EnvView& e, int what, hipStream_t s) {
     if (e.ray_count <= 0 || !(what & 3)) return;
-    const long long cols = (long long)e.ray_count * (e.B >> 2);
-    long long nb = (cols + 255) / 256;
-    if (nb > 8192) nb = 8192;
-    hipLaunchKernelGGL(materialize_kernel, dim3((int)nb), dim3(256), 0, s, e, what);
+    hipLaunchKernelGGL(materialize_kernel, stride_grid((long long)e.ray_count * (e.B >> 2)), dim3(256), 0, s, e, what);
 }
 
 void launch_normalize(const float* in, float* out, long long count, hipStream_t s) {
     const long long c4 = count / 4;
-    long long blocks = (c4 + 255) / 256;
-    if (blocks > 8192) blocks = 8192;
-    if (blocks < 1) return;
-    hipLaunchKernelGGL(normalize_kernel, dim3((int)blocks), dim3(256), 0, s, reinterpret_cast<const float4*>(in),
+    if (c4 < 1) return;
+    hipLaunchKernelGGL(normalize_kernel, stride_grid(c4), dim3(256), 0, s, reinterpret_cast<const float4*>(in),
                        reinterpret_cast<float4*>(out), c4);
 }
 
 void launch_sparse_obs(const EnvView& e, const int32_t* index, int nb, float* out, hipStream_t s) {
-    const long long total = (long long)e.N * e.F * nb;
-    long long blocks = (total + 255) / 256;
-    if (blocks > 8192) blocks = 8192;
-    hipLaunchKernelGGL(sparse_obs_kernel, dim3((int)blocks), dim3(256), 0, s, e, index, nb, out);
+    hipLaunchKernelGGL(sparse_obs_kernel, stride_grid((long long)e.N * e.F * nb), dim3(256), 0, s, e, index, nb, out);
 }
 
 void launch_newest_obs(const EnvView& e, float* out, hipStream_t s) {
-    const long long cols = (long long)e.N * (e.B >> 2);
-    long long nb = (cols + 255) / 256;
-    if (nb > 8192) nb = 8192;
-    hipLaunchKernelGGL(newest_obs_kernel, dim3((int)nb), dim3(256), 0, s, e, out);
+    hipLaunchKernelGGL(newest_obs_kernel, stride_grid((long long)e.N * (e.B >> 2)), dim3(256), 0, s, e, out);
 }
 
 // the lidar hash of the current poses.  counted = 1: the populations are in bw_lcount already (a tick: bw_finish_kernel)
