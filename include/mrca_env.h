@@ -33,7 +33,8 @@
 extern "C" {
 #endif
 
-/* 6, additive: mrca_lidar_features_bf16 (the bf16 MFMA front end of the opt-in bf16 rollout inference).
+/* 6, additive: mrca_lidar_features_bf16 (the bf16 MFMA front end of the opt-in bf16 rollout inference); the opt-in fused bf16
+ * update's mrca_lidar_features_bf16_rows, mrca_lidar_features_bf16_backward(_rows, _scratch).
  * 6 (round 6): MRCA_F_HIT_BITS -- what a beam hit is a bit plane of its own, MRCA_F_SCAN_RING holds plain ranges (5: the sign
  * bit of a ring entry); mrca_step_many's run-ahead schedule (chains < 0: the chained one).
  * 5 (round 5): mrca_policy_tail takes fc1_b_dev (may be NULL) after h1_dev; added since 4, all additive: mrca_step_worlds,
@@ -360,6 +361,40 @@ int mrca_lidar_features_backward_rows(const float* frames_dev, const int32_t* ro
                                       const float* feat_dev, const float* gfeat_act_dev, const float* gfeat_crt_dev, float* dw1_dev,
                                       float* db1_dev, float* dw2_dev, float* db2_dev, void* scratch_dev, size_t scratch_bytes,
                                       void* stream);
+
+/* The bf16 front end of the opt-in fused bf16 PPO UPDATE (not the reference's precision; fp32 is the default).
+ * Forward: mrca_lidar_features_bf16 with the scans addressed through a row table (see mrca_lidar_features_rows; frames_dev
+ * f32[*,512] NORMALISED, rows_dev i32[n_samples,3]) -- the rounding points (1)-(4) of mrca_lidar_features_bf16 and the same
+ * device code, so with both bf16 flags on the update re-evaluates the policy at the precision the rollout acted with.
+ * Same results bit for bit as mrca_lidar_features_bf16 on the gathered stacks. */
+int mrca_lidar_features_bf16_rows(const float* frames_dev, const int32_t* rows_dev, int32_t n_samples, int32_t frames,
+                                  int32_t beams, const float* w1_dev, const float* b1_dev, const float* w2_dev,
+                                  const float* b2_dev, uint16_t* feat_dev, void* stream);
+/* Backward of the bf16 front end on v_mfma_f32_32x32x16_bf16 (csrc/mrca_policy_bf16_bwd.hip).  Numerical contract -- every
+ * rounding is to nearest even by a plain cast, every accumulation fp32, parameters and gradients fp32, roundings are
+ * straight-through (no gradient term for a rounding):
+ *   in   feat_dev bf16[2,N,4096] the forward's output; gfeat_act_dev / gfeat_crt_dev bf16[N,4096]: fc1's dgrad g * W, formed
+ *        from bf16 operands with fp32 accumulation and STORED as bf16 (the caller's rounding point)
+ *   (1)  g2 = gfeat * (feat > 0): exact
+ *   (2)  h1 is recomputed exactly as the forward forms it (bf16 observation and w1, fp32 b1, relu, rounded to bf16)
+ *   (3)  dw2 = sum g2 * h1 and db2 = sum g2: fp32 sums of exact products
+ *   (4)  dh1 = sum w2 * g2 with w2 rounded to bf16: fp32; g1 = dh1 * (h1 > 0) is rounded to bf16
+ *   (5)  dw1 = sum g1 * x (the bf16 observation) and db1 = sum g1: fp32 sums of exact products
+ *   per-wave partial sums are added in a fixed order in float64: run-to-run bit-identical, no atomics.
+ * obs_dev f32[N,3,512] NORMALISED observations (or frames_dev / rows_dev: the row-table form); w1_dev, b1_dev, w2_dev the fp32
+ * weights the forward ran with; outputs and scratch as mrca_lidar_features_backward (the scratch size is this kernel's own:
+ * mrca_lidar_features_bf16_backward_scratch).  obs, w1, w2, feat and the two gfeat 16-byte aligned, everything else 4-byte
+ * (MRCA_ERR_INVALID); frames 3, beams 512 (MRCA_ERR_UNSUPPORTED).  Arguments are validated before the first HIP call. */
+int mrca_lidar_features_bf16_backward_scratch(size_t* bytes_out);
+int mrca_lidar_features_bf16_backward(const float* obs_dev, int32_t n_robots, int32_t frames, int32_t beams, const float* w1_dev,
+                                      const float* b1_dev, const float* w2_dev, const uint16_t* feat_dev,
+                                      const uint16_t* gfeat_act_dev, const uint16_t* gfeat_crt_dev, float* dw1_dev, float* db1_dev,
+                                      float* dw2_dev, float* db2_dev, void* scratch_dev, size_t scratch_bytes, void* stream);
+int mrca_lidar_features_bf16_backward_rows(const float* frames_dev, const int32_t* rows_dev, int32_t n_samples, int32_t frames,
+                                           int32_t beams, const float* w1_dev, const float* b1_dev, const float* w2_dev,
+                                           const uint16_t* feat_dev, const uint16_t* gfeat_act_dev, const uint16_t* gfeat_crt_dev,
+                                           float* dw1_dev, float* db1_dev, float* dw2_dev, float* db2_dev, void* scratch_dev,
+                                           size_t scratch_bytes, void* stream);
 
 /* The loss tail of the PPO update, values AND gradients, in one launch (model/ppo.py:172-185 / :238-251: importance ratio,
  * clipped surrogate, value loss x value_coef, entropy bonus; log-density of model/utils.py:90-97) -- what PyTorch runs as

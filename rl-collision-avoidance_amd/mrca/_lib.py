@@ -33,7 +33,8 @@ EXPORTS = ["mrca_abi_version", "mrca_last_error", "mrca_arena_bytes", "mrca_crea
            "mrca_relu_cat_backward_bias"]
 # declared in include/mrca_env.h like the names above, listed apart: tests/test_abi.py's header scan reads names of letters
 # and underscores only (tests/test_policy_bf16_host.py checks these against the header and the library)
-EXPORTS_WITH_DIGITS = ["mrca_lidar_features_bf16"]
+EXPORTS_WITH_DIGITS = ["mrca_lidar_features_bf16", "mrca_lidar_features_bf16_rows", "mrca_lidar_features_bf16_backward",
+                       "mrca_lidar_features_bf16_backward_rows", "mrca_lidar_features_bf16_backward_scratch"]
 
 
 class RolloutRows(C.Structure):
@@ -102,6 +103,12 @@ def load(path=None):
     lib.mrca_lidar_features.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.mrca_lidar_features_bf16.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 6
+    lib.mrca_lidar_features_bf16_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 6
+    lib.mrca_lidar_features_bf16_backward_scratch.argtypes = [C.POINTER(C.c_size_t)]
+    lib.mrca_lidar_features_bf16_backward.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 11 + \
+        [C.c_size_t, C.c_void_p]
+    lib.mrca_lidar_features_bf16_backward_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + \
+        [C.c_void_p] * 11 + [C.c_size_t, C.c_void_p]
     lib.mrca_lidar_features_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 6
     lib.mrca_lidar_features_backward_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 11 + \
         [C.c_size_t, C.c_void_p]

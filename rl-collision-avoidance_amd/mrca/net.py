@@ -54,6 +54,24 @@ class CNNPolicy(nn.Module):
     # nn.Conv1d parameters.  Needs a GPU and frames = 3, beams = 512; results differ from the stock layers by
     # summation order only (tests/test_gpu_policy_bwd.py).
     fused_train = False
+    # True (needs fused_train): the opt-in fused bf16 update -- NOT the reference's precision.  mean_value runs the front end
+    # on bf16 MFMAs forward and backward (policy_ops.lidar_features_bf16_fn: the rounding points of the rollout's bf16
+    # inference) and fc1 as bf16 x bf16 GEMMs with fp32 accumulation (policy_ops.fc1_bf16); the parameters, their gradients,
+    # relu_cat, fc2, the heads, the loss and Adam stay fp32.
+    fused_train_bf16 = False
+
+    def _fc1_train_bf16(self):
+        """-> {tower: bf16 copy of fc1.weight [256, 4096]}: persistent buffers, re-cast from the fp32 master weights by every
+        call (one cast per optimiser step: the update's forward runs once per step).  The same values as the rollout cache's
+        ``_rc_bf16`` (both are the RNE cast of the same master weights)."""
+        bufs = getattr(self, "_fc1_bf16_w", None)
+        with torch.no_grad():
+            if bufs is None or any(bufs[tw].device != getattr(self, f"{tw}_fc1").weight.device for tw in self.TOWERS):
+                bufs = self._fc1_bf16_w = {tw: getattr(self, f"{tw}_fc1").weight.detach().to(torch.bfloat16) for tw in self.TOWERS}
+            else:
+                for tw in self.TOWERS:
+                    bufs[tw].copy_(getattr(self, f"{tw}_fc1").weight)
+        return bufs
 
     def _tail(self, tw, h, goal, speed):
         h = torch.relu(getattr(self, f"{tw}_fc1")(h))
@@ -75,9 +93,13 @@ class CNNPolicy(nn.Module):
         table = isinstance(x, policy_ops.FrameTable)
         if table and not self.fused_train:
             x = x.gather()
+        if self.fused_train_bf16 and not self.fused_train:
+            raise ValueError("fused_train_bf16 is a precision of the fused update path: it needs fused_train = True")
         if self.fused_train and x.is_cuda:
             st = lambda a, c: torch.stack((a, c))      # noqa: E731  (its backward hands each tower its slice)
-            fa, fc = policy_ops.lidar_features_fn(
+            bf16 = self.fused_train_bf16
+            wb = self._fc1_train_bf16() if bf16 else None
+            fa, fc = (policy_ops.lidar_features_bf16_fn if bf16 else policy_ops.lidar_features_fn)(
                 x if table else x.float(), st(self.act_fea_cv1.weight, self.crt_fea_cv1.weight), st(self.act_fea_cv1.bias, self.crt_fea_cv1.bias),
                 st(self.act_fea_cv2.weight, self.crt_fea_cv2.weight), st(self.act_fea_cv2.bias, self.crt_fea_cv2.bias))
             # behind the front end the layers are the module's own Linear layers (library GEMMs); what sits BETWEEN them runs
@@ -90,7 +112,11 @@ class CNNPolicy(nn.Module):
             z, zb = [], []
             for tw, f in (("act", fa), ("crt", fc)):
                 fc1, fc2 = getattr(self, f"{tw}_fc1"), getattr(self, f"{tw}_fc2")
-                x2 = policy_ops.relu_cat(F.linear(f, fc1.weight, fc1.bias.detach()), goal, speed, h1_bias=fc1.bias)
+                if bf16:        # bf16 x bf16 -> fp32, the bias added in fp32 (as the rollout's tail adds it)
+                    h1 = policy_ops.fc1_bf16(f, fc1.weight, wb[tw]) + fc1.bias.detach()
+                else:
+                    h1 = F.linear(f, fc1.weight, fc1.bias.detach())
+                x2 = policy_ops.relu_cat(h1, goal, speed, h1_bias=fc1.bias)
                 z.append(F.linear(x2, fc2.weight, fc2.bias.detach()))
                 zb.append(fc2.bias)
             return policy_ops.policy_heads(z[0], z[1], self.actor1.weight, self.actor1.bias, self.actor2.weight,

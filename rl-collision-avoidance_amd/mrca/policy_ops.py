@@ -2,7 +2,8 @@
 fused forward of both towers' Conv1d + ReLU pairs (rollout AND update) and its backward pass, tied together as a
 ``torch.autograd.Function`` (``lidar_features_fn``) so that the PPO update (model/ppo.py:158-192) differentiates through
 hand-written fp32 MFMA kernels instead of MIOpen.  The rest of the policy stays stock PyTorch.
-There is no fallback: without the HIP library these raise."""
+The opt-in fused bf16 update has its own pair (``lidar_features_bf16_fn``, ``fc1_bf16``; csrc/mrca_policy_bf16_rows.hip and
+csrc/mrca_policy_bf16_bwd.hip).  There is no fallback: without the HIP library these raise."""
 import ctypes as C
 
 import numpy as np
@@ -277,6 +278,154 @@ def lidar_features_fn(obs, w1, b1, w2, b2):
     """Differentiable lidar_features: same arguments, returns (actor features, critic features), gradients flow to
     w1 / b1 / w2 / b2 (the scan is data)."""
     return _LidarFeatures.apply(obs, w1, b1, w2, b2)
+
+
+# ------------------------------------------------------------------------------ the opt-in fused bf16 update's front end
+def _check_conv_weights(who, w1, b1, w2, b2=None):
+    for t, shape in ((w1, (2, 32, 3, 5)), (b1, (2, 32)), (w2, (2, 32, 32, 3))) + (() if b2 is None else ((b2, (2, 32)),)):
+        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape):
+            raise ValueError(f"{who}: expected a contiguous cuda float32 tensor of shape {shape}, got "
+                             f"{tuple(t.shape)} {t.dtype} {t.device}")
+
+
+def lidar_features_bf16_rows(table, w1, b1, w2, b2, out=None):
+    """lidar_features_bf16 with the stacks addressed through a ``FrameTable`` (normalised frames; csrc/mrca_policy_bf16_rows.hip):
+    the forward of the fused bf16 update.  Same rounding points and device code as the rollout's kernel; bit for bit what
+    ``lidar_features_bf16(table.gather(), ...)`` returns.  -> bf16[2,N,4096]"""
+    lib = _lib.load()
+    if not isinstance(table, FrameTable) or not table.is_cuda:
+        raise ValueError("lidar_features_bf16_rows: expected a FrameTable on the GPU")
+    _check_conv_weights("lidar_features_bf16_rows", w1, b1, w2, b2)
+    N = table.rows.shape[0]
+    if out is None:
+        out = torch.empty(2, N, 4096, dtype=torch.bfloat16, device=table.device)
+    elif not (out.is_cuda and out.dtype == torch.bfloat16 and out.is_contiguous() and tuple(out.shape) == (2, N, 4096)
+              and out.device == table.device and out.data_ptr() % 16 == 0):
+        raise ValueError("lidar_features_bf16_rows: out must be a contiguous 16-byte aligned cuda bfloat16 tensor [2, N, 4096] "
+                         "on the table's device")
+    with torch.cuda.device(table.device):
+        stream = C.c_void_p(torch.cuda.current_stream(table.device).cuda_stream)
+        _lib.check(lib.mrca_lidar_features_bf16_rows(table.frames.data_ptr(), table.rows.data_ptr(), N, 3, 512, w1.data_ptr(),
+                                                     b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), out.data_ptr(), stream),
+                   "mrca_lidar_features_bf16_rows")
+    return out
+
+
+_scratch_bf16 = {}
+
+
+def _backward_scratch_bf16(device, stream=0):
+    """per (device, stream), as _backward_scratch: the bf16 backward kernel's per-wave partial sums"""
+    key = (device.type, device.index, int(stream))
+    if key not in _scratch_bf16:
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("lidar_features_bf16_backward: first use on this stream inside a graph capture -- call it once "
+                               "before capturing")
+        lib = _lib.load()
+        n = C.c_size_t()
+        with torch.cuda.device(device):
+            _lib.check(lib.mrca_lidar_features_bf16_backward_scratch(C.byref(n)), "mrca_lidar_features_bf16_backward_scratch")
+        _scratch_bf16[key] = torch.empty(n.value, dtype=torch.uint8, device=device)
+    return _scratch_bf16[key]
+
+
+def lidar_features_bf16_backward(obs, w1, b1, w2, feat, gfeat_act, gfeat_crt):
+    """Gradients of the bf16 front end with respect to (w1, b1, w2, b2) on bf16 MFMAs (csrc/mrca_policy_bf16_bwd.hip; the
+    numerical contract: include/mrca_env.h, mrca_lidar_features_bf16_backward).  ``obs`` f32[N,3,512] normalised observations
+    or a ``FrameTable``; fp32 weights (tower-major); ``feat`` bf16[2,N,4096] the bf16 forward's output; ``gfeat_act`` /
+    ``gfeat_crt`` bf16[N,4096].  -> fp32 dw1 [2,32,3,5], db1 [2,32], dw2 [2,32,32,3], db2 [2,32]"""
+    lib = _lib.load()
+    N = obs.shape[0]
+    table = obs if isinstance(obs, FrameTable) else None
+    _check_conv_weights("lidar_features_bf16_backward", w1, b1, w2)
+    if table is None and not (obs.is_cuda and obs.dtype == torch.float32 and obs.is_contiguous() and tuple(obs.shape) == (N, 3, 512)):
+        raise ValueError("lidar_features_bf16_backward: obs must be a contiguous cuda float32 tensor [N, 3, 512] or a FrameTable")
+    for t, shape in ((feat, (2, N, 4096)), (gfeat_act, (N, 4096)), (gfeat_crt, (N, 4096))):
+        if not (t.is_cuda and t.dtype == torch.bfloat16 and t.is_contiguous() and tuple(t.shape) == shape):
+            raise ValueError(f"lidar_features_bf16_backward: expected a contiguous cuda bfloat16 tensor of shape {shape}, got "
+                             f"{tuple(t.shape)} {t.dtype} {t.device}")
+    dev = obs.device
+    dw1, db1 = torch.empty_like(w1), torch.empty_like(b1)
+    dw2, db2 = torch.empty_like(w2), torch.empty(2, 32, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        scratch = _backward_scratch_bf16(dev, stream.value or 0)
+        tail = (N, 3, 512, w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), feat.data_ptr(), gfeat_act.data_ptr(), gfeat_crt.data_ptr(),
+                dw1.data_ptr(), db1.data_ptr(), dw2.data_ptr(), db2.data_ptr(), scratch.data_ptr(), scratch.numel(), stream)
+        if table is None:
+            _lib.check(lib.mrca_lidar_features_bf16_backward(obs.data_ptr(), *tail), "mrca_lidar_features_bf16_backward")
+        else:
+            _lib.check(lib.mrca_lidar_features_bf16_backward_rows(table.frames.data_ptr(), table.rows.data_ptr(), *tail),
+                       "mrca_lidar_features_bf16_backward_rows")
+    return dw1, db1, dw2, db2
+
+
+class _LidarFeaturesBf16(torch.autograd.Function):
+    """_LidarFeatures at bf16: -> (actor features, critic features) bf16[N,4096]; the backward takes the two bf16 fc1
+    gradients as they are.  The roundings are straight-through."""
+
+    @staticmethod
+    def forward(ctx, obs, w1, b1, w2, b2):
+        w1, b1, w2, b2 = (t.detach().contiguous() for t in (w1, b1, w2, b2))
+        table = obs if isinstance(obs, FrameTable) else None
+        if table is None:
+            obs = obs.detach().contiguous()
+            feat = lidar_features_bf16(obs, w1, b1, w2, b2)
+            ctx.save_for_backward(obs, w1, b1, w2, feat)
+        else:
+            feat = lidar_features_bf16_rows(table, w1, b1, w2, b2)
+            ctx.save_for_backward(table.frames, table.rows, w1, b1, w2, feat)
+        ctx.table = table is not None
+        return feat[0], feat[1]
+
+    @staticmethod
+    def backward(ctx, g_act, g_crt):
+        if ctx.table:
+            frames, rows, w1, b1, w2, feat = ctx.saved_tensors
+            obs = FrameTable(frames, rows)
+        else:
+            obs, w1, b1, w2, feat = ctx.saved_tensors
+        g_act = torch.zeros_like(feat[0]) if g_act is None else g_act.to(torch.bfloat16).contiguous()
+        g_crt = torch.zeros_like(feat[1]) if g_crt is None else g_crt.to(torch.bfloat16).contiguous()
+        dw1, db1, dw2, db2 = lidar_features_bf16_backward(obs, w1, b1, w2, feat, g_act, g_crt)
+        return None, dw1, db1, dw2, db2
+
+
+def lidar_features_bf16_fn(obs, w1, b1, w2, b2):
+    """Differentiable bf16 front end of the opt-in fused bf16 update: ``obs`` f32[N,3,512] (normalised) or a ``FrameTable``, fp32
+    weights (tower-major) -> (actor features, critic features), two bf16 matrices [N,4096]; fp32 gradients flow to
+    w1 / b1 / w2 / b2 through csrc/mrca_policy_bf16_bwd.hip (the scan is data).  Not the reference's precision."""
+    return _LidarFeaturesBf16.apply(obs, w1, b1, w2, b2)
+
+
+class _Fc1Bf16(torch.autograd.Function):
+    """fc1 of the fused bf16 update as three library GEMMs with bf16 operands and fp32 accumulation:
+    forward   h = feat x Wb^T                       fp32 result (the bias is the caller's, added in fp32)
+    dgrad     gfeat = bf16(g) x Wb                  stored as bf16 (the front end's backward reads it)
+    wgrad     dW = bf16(g)^T x feat                 fp32 result: the gradient of the fp32 master weight
+    g = the fp32 gradient that reaches fc1's output, rounded to bf16 once; the roundings are straight-through."""
+
+    @staticmethod
+    def forward(ctx, feat, weight, weight_bf16):
+        ctx.save_for_backward(feat, weight_bf16)
+        return torch.mm(feat, weight_bf16.t(), out_dtype=torch.float32)
+
+    @staticmethod
+    def backward(ctx, g):
+        feat, wb = ctx.saved_tensors
+        gb = g.to(torch.bfloat16)
+        gfeat = torch.mm(gb, wb) if ctx.needs_input_grad[0] else None
+        dw = torch.mm(gb.t(), feat, out_dtype=torch.float32) if ctx.needs_input_grad[1] else None
+        return gfeat, dw, None
+
+
+def fc1_bf16(feat, weight, weight_bf16):
+    """``feat`` bf16[N,4096] x fc1's weight -> f32[N,256] (no bias).  ``weight`` f32[256,4096] is the master parameter (it
+    receives the fp32 weight gradient), ``weight_bf16`` its bf16 copy, the operand of the GEMMs."""
+    if not (feat.dtype == torch.bfloat16 and weight_bf16.dtype == torch.bfloat16 and weight.dtype == torch.float32 and
+            weight.shape == weight_bf16.shape):
+        raise ValueError("fc1_bf16: expected bf16 features, the fp32 master weight and its bf16 copy of the same shape")
+    return _Fc1Bf16.apply(feat, weight, weight_bf16)
 
 
 # ------------------------------------------------------------------------------------------------ the PPO loss tail

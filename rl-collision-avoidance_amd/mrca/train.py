@@ -73,6 +73,10 @@ def main(argv=None):
     ap.add_argument("--bf16-inference", action="store_true", help="bf16 autocast in the rollout policy (opt-in)")
     ap.add_argument("--fused-bf16-inference", action="store_true", help="rollout inference through the fused path at bf16: "
                                                                          "the bf16 MFMA front end and a bf16 fc1 (opt-in precision)")
+    ap.add_argument("--fused-bf16-update", action="store_true", help="the fused PPO update at bf16: bf16 MFMA front end forward and "
+                                                                      "backward and a bf16 fc1, fp32 master weights, accumulation, "
+                                                                      "loss tail, heads and Adam (opt-in precision, not the "
+                                                                      "reference's)")
     ap.add_argument("--init", default=None, help="state_dict to start from (overrides the resume file)")
     ap.add_argument("--circle-every", type=int, default=0, help="run the circle test every K updates (rank 0)")
     ap.add_argument("--circle-sizes", default="50:25", help="validation circles as 'robots:radius,...' (50:25 = the reference's "
@@ -110,6 +114,10 @@ def main(argv=None):
     if a.fused_bf16_inference and (a.bf16_inference or a.stock_policy_path):
         ap.error("--fused-bf16-inference runs the fused policy path: it cannot be combined with --bf16-inference or "
                  "--stock-policy-path")
+
+    if a.fused_bf16_update and (a.bf16_update or a.update_path == "stock"):
+        ap.error("--fused-bf16-update is a precision of the fused update path: it cannot be combined with --bf16-update or "
+                 "--update-path stock")
 
     world_size = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -155,6 +163,9 @@ def main(argv=None):
     hp.rollout_bf16 = bool(a.fused_bf16_inference)
     hp.graph_tick = bool(a.graph) and not a.no_graph
     hp.update_fused = a.update_path == "fused" and not a.bf16_update and torch.cuda.is_available()
+    hp.update_bf16 = bool(a.fused_bf16_update)
+    if hp.update_bf16 and not hp.update_fused:
+        raise RuntimeError("--fused-bf16-update needs the fused update path (a GPU)")
     if a.bf16_update:
         hp.update_dtype = torch.bfloat16
     if a.bf16_inference:
@@ -180,6 +191,11 @@ def main(argv=None):
         # world size: 32 minibatches per epoch per rank; the global batch of one optimiser step is world_size x this.
         hp.batch_size = max(hp.batch_size, env.N * hp.horizon // 32)
     tr = Stage1Trainer(env, hp=hp, dist=dist, seed=a.seed, stage2=(a.stage == 2))
+    # which precision this run's update and rollout use (evaluate.py names its inference precision the same way)
+    out.info("update precision: %s; rollout inference precision: %s",
+             "bf16 (fused: bf16 MFMA front end + bf16 fc1, fp32 master weights and accumulation; opt-in, not the reference's)"
+             if hp.update_bf16 else "bf16 autocast (opt-in)" if a.bf16_update else "fp32",
+             "bf16 (fused; opt-in)" if hp.rollout_bf16 else "bf16 autocast (opt-in)" if a.bf16_inference else "fp32")
     out.info("per-rank minibatch %d rows, global batch per optimiser step %d, lr %g, epochs %d, horizon %d",
              hp.batch_size, hp.batch_size * world_size, hp.learning_rate, hp.epoch, hp.horizon)
     os.makedirs(a.policy_dir, exist_ok=True)

@@ -38,6 +38,9 @@ class HParams:
     rollout_bf16: bool = False        # ... with the bf16 MFMA front end and a bf16 fc1 (opt-in precision; needs rollout_fused)
     # the PPO update differentiates the conv front end through the HIP forward / backward kernels (net.CNNPolicy.fused_train)
     update_fused: bool = False
+    # ... at bf16: bf16 MFMA front end forward and backward, bf16 fc1 GEMMs; fp32 master weights, accumulation, loss tail, heads,
+    # Adam and all-reduce (net.CNNPolicy.fused_train_bf16; opt-in precision, not the reference's; needs update_fused)
+    update_bf16: bool = False
     kl_target: float = 0.0            # > 0: KL-adaptive learning rate (ppo.KLAdaptiveLR; opt-in, large-batch regime)
     lr_max: float = 1e-3
     kl_stop: float = 0.0              # > 0: abandon the rest of an update when a minibatch reports KL > kl_stop x kl_target
@@ -71,8 +74,14 @@ class Stage1Trainer:
         self.policy = policy or CNNPolicy(frames=self.hp.laser_hist, action_space=self.hp.act_size,
                                           beams=self.hp.obs_size)
         self.policy.to(dev)
+        if self.hp.update_bf16 and not self.hp.update_fused:
+            raise ValueError("update_bf16 is a precision of the fused update path: it needs update_fused=True")
+        if self.hp.update_bf16 and self.hp.update_dtype is not None:
+            raise ValueError("update_bf16 (the fused bf16 update) and update_dtype (autocast on the stock layers) exclude each other")
         if self.hp.update_fused:
             self.policy.fused_train = True
+        if self.hp.update_bf16:
+            self.policy.fused_train_bf16 = True
         broadcast_parameters(self.policy, dist)
         # the reference's optimiser (ppo_stage1.py:176: Adam, lr 5e-5).  On the GPU the parameters, their gradients and the
         # moment estimates are flat buffers and a step is ONE element-wise launch (ppo.FlatAdam, csrc/mrca_adam.hip;
