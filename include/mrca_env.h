@@ -219,7 +219,13 @@ int mrca_observe_worlds(mrca_env* env, int32_t first_world, int32_t num_worlds, 
  * ray casts of chains = P contiguous world ranges run on P streams (range 0 on `stream`, the others on streams the env created
  * in mrca_create for P <= 2, at first use beyond), tick after tick, each behind the event "tick k's move launch is through".  `stream` waits for
  * all of them before the call's work counts as done, and they for everything queued on `stream` before the call.  What a tick
- * then costs is its ray casts alone.  The host only enqueues (no synchronisation, nothing spins on the
+ * then costs is its ray casts alone.
+ * With lazy_obs = 1, exact-rectangle collisions and world ranges of at most 3072 robots, a range's ray casts go out as launches
+ * of up to `frames` consecutive ticks each (at most 8, at most 6144 workgroups; their ray casts do not depend on each other,
+ * every tick's scan is cast and stored, and the later residency rounds of such a launch start without a launch boundary).  Such a launch reads the ring heads from MRCA_F_RING_HEAD and leaves them in an N-byte
+ * array of the env's own, or the other way round; the last one of a call leaves them in MRCA_F_RING_HEAD.  The environment
+ * variable MRCA_TICKS_PER_LAUNCH, read once in mrca_create, sets the ticks per launch whatever the env's shape (1: a launch per
+ * tick; A/B runs).  The host only enqueues (no synchronisation, nothing spins on the
  * device); the call is capturable into a hipGraph like any other (chains > 2: call it once outside the capture first).
  * Streams: the HIP runtime maps a process's streams onto a few hardware queues, and two streams that share one run their
  * kernels one after the other (tools/queue_alias_probe.hip): the schedule stays correct and silently loses its overlap.  At the

@@ -260,6 +260,12 @@ struct AheadRing {
     int slots = 0;                    // 0: the ring could not be allocated -> the chained schedule
     Stream move_stream;
     std::vector<Event> moved;         // [kAheadTicks] "tick k's move launch is through"
+    // A range's ray casts go out as launches of up to ticks_per_launch consecutive ticks (mrca_raycast_ticks.hip; 1: a launch
+    // per tick).  Such a launch reads the ring heads from one array and leaves them in another -- the env's ring_head field
+    // and head_scratch [N] in turns, so that no workgroup reads what another one of its launch writes.
+    int ticks_per_launch = 1;
+    bool ticks_forced = false;        // MRCA_TICKS_PER_LAUNCH was set: that many wherever such launches are possible at all
+    DeviceBuffer<uint8_t> head_scratch;
 };
 
 // mrca_step_many with chains > 1: world range c >= 1's stream and the events that order it against the caller's -- `moved`:
@@ -305,6 +311,7 @@ struct mrca_env {
 
 constexpr int kAheadTicks = 256;            // most ticks one run-ahead pass covers (a pass ends with every stream joined: ~90 us)
 constexpr size_t kAheadMaxBytes = 256u << 20;
+constexpr int kRayTicksGroups = 3 * 2048;   // most workgroups of a ray-cast launch of several ticks: three residency rounds (run_ahead_pass)
 // World range 1 gets its stream in mrca_create (chains <= 2, bench.py's default, may be captured at once); further ranges get
 // theirs at their first use -- an env does not park streams it may never use (the runtime maps a process's streams onto a
 // few hardware queues, DESIGN.md 5.10 "what the schedule depends on").
@@ -612,6 +619,20 @@ static void init_step_many(mrca_env* env) {
         (void)hipGetLastError();
         r.slots = 0;
     }
+    // ticks per ray-cast launch: as many as the scan ring has frames (every tick of a launch that is not a restart writes a
+    // slot of its own: each tick's row is stored), at most the 8 the kernel's tick index has flags for -- where that was
+    // measured to pay (run_ahead_pass).  MRCA_TICKS_PER_LAUNCH, read once here, sets the number for every pass whatever its
+    // shape, for A/B runs on one box: 1 is a launch per tick, the schedule before there were such launches
+    int ticks = env->view.F < 8 ? env->view.F : 8;
+    if (const char* v = std::getenv("MRCA_TICKS_PER_LAUNCH")) {
+        const int want = std::atoi(v);
+        if (want >= 1) {
+            if (want < ticks) ticks = want;
+            r.ticks_forced = true;
+        }
+    }
+    if (ticks > 1 && r.slots > 0 && device_alloc(&r.head_scratch, N) == hipSuccess) r.ticks_per_launch = ticks;
+    else (void)hipGetLastError();
 }
 
 extern "C" {
@@ -946,20 +967,64 @@ static int run_ahead_pass(mrca_env* env, const float* const* act, int K, int P, 
     hipError_t herr = hipSuccess;
     bool move_forked = false;
     MRCA_LOG_BEGIN();
-    // Ticks are enqueued in BLOCKS -- [0], [1], [2], [3], then fours: a block's move launches, ONE event behind the last of them,
-    // and every range's stream waits for that event once before it takes the block's ray casts.  hipStreamWaitEvent is the
-    // dearest call here (4.6 us of host time against ~3 for a launch: a build with host timers, profiles/r06_ai_*): a wait per
-    // tick and range made the host 15.8 us per tick against the device's 19.1 -- any hiccup starved the queues.
+    // Ticks are enqueued in BLOCKS -- [0], [1], [2], [3], then fours; with T = ticks per ray-cast launch > 1: [0], [1], two,
+    // four times T (T = 2: once), then 2 T each: at no length of a pass more waits than with a launch per tick, and small blocks
+    // while the move launches are not far ahead yet -- a block's ray casts wait for its LAST move launch, and next to launches of
+    // several residency rounds a move launch takes up to 20 us (launch stamps, profiles/multitick/) --: a block's move launches,
+    // ONE event behind the last of them, and every range's stream waits for that event once before it takes the block's ray
+    // casts.  hipStreamWaitEvent is the dearest call here (4.6 us of host time against ~3 for a launch: a build with host timers,
+    // profiles/r06_ai_*): a wait per tick and range made the host 15.8 us per tick against the device's 19.1 -- any hiccup
+    // starved the queues.
     // The HOST ORDER matters as much: the host needs ~13 us per tick, the device ~16.5, so the device is never far behind the
     // host and what is enqueued late starts late.  The move launches of block b + 3 are therefore enqueued BEFORE the ray casts
     // of block b: they have a queue of their own, under load they come ~13 us apart (not 8.5: the launch stamps of the
     // profiling build, MRCA_LAUNCH_STAMPS), and a ray cast waits 10 us beyond the end of the move launch it depends on.
     // Measured (own ticks on the caller's stream x blocks of lead, profiles/r06_ai_*): lead 1 (round 6's first form) 463 us
     // per 20-tick region, lead 2 - 4 with one or two own ticks 436 - 445; tick 0 alone on the caller's stream and lead 3 kept.
+    // Ticks per ray-cast launch.  lazy_obs = 0: the VIEWS epilogue reads the rows earlier ticks stored -- a launch per tick.
+    // Otherwise several, where a range's launch then stays within kRayTicksGroups workgroups and the mode is the exact-rectangle
+    // one: that is where it was measured to pay (Stage-1, 2 x 2048 robots: +5 %).  Next to launches of more residency rounds
+    // the move launches no longer find free CUs between two ray casts and fall behind the ray casts they feed: ranges of 4114
+    // robots (the Stage-2 side figure) lost 2 - 5 % at two ticks per launch, fidelity mode -- whose move launch is the
+    // longer one -- 22 - 27 % with move launches of up to 70 us (profiles/multitick/).
+    int Tm = 1;
+    if (env->cfg.lazy_obs) {
+        Tm = env->ahead.ticks_per_launch;
+        if (!env->ahead.ticks_forced) {
+            const int most = (W + P - 1) / P * R;             // robots of the largest range
+            if (Tm > kRayTicksGroups / most) Tm = kRayTicksGroups / most;
+            if (Tm < 1 || env->view.raster_inv > 0.0f) Tm = 1;
+        }
+    }
     int first_of[kAheadTicks + 2];
     int nb = 0;
-    for (int a = 0; a < K; a += a < 4 ? 1 : 4) first_of[nb++] = a;
+    for (int a = 0; a < K; ++nb) {
+        first_of[nb] = a;
+        a += Tm == 1 ? (a < 4 ? 1 : 4) : (nb < 2 ? 1 : nb == 2 ? 2 : nb < (Tm > 2 ? 7 : 4) ? Tm : 2 * Tm);
+    }
     first_of[nb] = K;
+    // A block's ray casts of one range: launches of up to Tm ticks each, the same cut for every range.  A launch of several
+    // ticks moves the ring heads from one of the two arrays to the other (a launch of one tick, the single-tick kernel, leaves
+    // them where it finds them), and the pass must leave them in the env's field: an odd number of such launches is made
+    // even by sending the first of them tick by tick.
+    int launch_of[kAheadTicks + 2];              // first tick of every ray-cast launch of a range, block after block
+    int nl = 0, several = 0;
+    for (int b = 0; b < nb; ++b)
+        for (int k = first_of[b]; k < first_of[b + 1]; k += Tm) {
+            launch_of[nl++] = k;
+            several += (first_of[b + 1] - k < Tm ? first_of[b + 1] - k : Tm) > 1 ? 1 : 0;
+        }
+    launch_of[nl] = K;
+    if (several & 1) {
+        int i = 0;
+        while (launch_of[i + 1] - launch_of[i] < 2) ++i;
+        const int n = launch_of[i + 1] - launch_of[i];
+        for (int q = nl; q > i; --q) launch_of[q + n - 1] = launch_of[q];
+        for (int q = 1; q < n; ++q) launch_of[i + q] = launch_of[i] + q;
+        nl += n - 1;
+    }
+    std::vector<uint8_t> heads_in_scratch((size_t)P, 0);     // per range: where its ring heads are at this point of its stream
+    int li = 0;                                              // the next launch of launch_of (rays_of takes the blocks in order)
     constexpr int own = 1;                       // ticks below this one: move launches on the caller's stream
     auto moves_of = [&](int b) {
         const int a = first_of[b], e = first_of[b + 1];
@@ -988,17 +1053,44 @@ static int run_ahead_pass(mrca_env* env, const float* const* act, int K, int P, 
                 if (herr != hipSuccess) return;
             }
             const int w0 = range_first_world(W, P, c), wn = range_first_world(W, P, c + 1) - w0;
-            for (int k = a; k < e; ++k) {
-                mrca::EnvView rv = slot_view(env, K - 1 - k);
+            uint8_t* const heads[2] = {env->view.ring_head, env->ahead.head_scratch.get()};
+            for (int l = li; launch_of[l] < e; ++l) {
+                const int k = launch_of[l], n = launch_of[l + 1] - k;
+                mrca::EnvView rv = slot_view(env, n > 1 ? 0 : K - 1 - k);
                 rv.ray_first = w0 * R;
                 rv.ray_count = wn * R;
                 rv.world_first = w0;
                 rv.world_count = wn;
                 rv.eager_views = env->cfg.lazy_obs ? 0 : (MRCA_VIEW_SCAN | MRCA_VIEW_OBS);
-                MRCA_LOG_TAG(rv, "ray", k, c);
-                mrca::launch_raycast(rv, /*only_fresh=*/0, sc);
+                rv.ring_head = heads[heads_in_scratch[(size_t)c]];
+                if (n == 1) {
+                    MRCA_LOG_TAG(rv, "ray", k, c);
+                    mrca::launch_raycast(rv, /*only_fresh=*/0, sc);
+                    continue;
+                }
+                // ticks k .. k + n - 1 read slots K - 1 - k downwards; slot 0, the env's own fields, can only be the last one's
+                const AheadRing& ring = env->ahead;
+                mrca::RayTicks t{};
+                t.ticks = n;
+                t.last_is_env = k + n == K;
+                t.slot0 = ring.mem.get() + (size_t)(K - 2 - k) * ring.slot_bytes + ring.off[0];
+                t.stride = -(int32_t)ring.slot_bytes;
+                t.off_head = (uint32_t)(ring.off[1] - ring.off[0]);
+                t.in.off_goal = (uint32_t)(ring.off[2] - ring.off[0]);
+                t.in.off_fresh = (uint32_t)(ring.off[3] - ring.off[0]);
+                t.in.off_outline = (uint32_t)(ring.off[4] - ring.off[0]);
+                t.in.head_in = rv.ring_head;
+                heads_in_scratch[(size_t)c] ^= 1;
+                t.in.head_out = heads[heads_in_scratch[(size_t)c]];
+                MRCA_LOG_TAG(rv, "rays", k, c);
+#if defined(MRCA_PROFILING)
+                t.in.launch_stamps = rv.launch_stamps;
+                t.in.launch_slot = rv.launch_slot;
+#endif
+                mrca::launch_raycast_ticks(rv, t, sc);
             }
         }
+        while (launch_of[li] < e) ++li;
     };
     constexpr int lead = 3;                      // how many blocks the move launches are enqueued ahead of the ray casts (>= 1)
     for (int b = 0; b < nb && b < lead && herr == hipSuccess; ++b) moves_of(b);
@@ -1006,6 +1098,13 @@ static int run_ahead_pass(mrca_env* env, const float* const* act, int K, int P, 
         if (b + lead < nb) moves_of(b + lead);
         if (herr == hipSuccess) rays_of(b);
     }
+    // an early exit may leave a range's ring heads in the scratch array: back into the env's field, behind the range's launches
+    for (int c = 0; c < P; ++c)
+        if (heads_in_scratch[(size_t)c]) {
+            const int n0 = range_first_world(W, P, c) * R, n1 = range_first_world(W, P, c + 1) * R;
+            (void)hipMemcpyAsync(env->view.ring_head + n0, env->ahead.head_scratch.get() + n0, (size_t)(n1 - n0),
+                                 hipMemcpyDeviceToDevice, range_stream(env, s0, c));
+        }
     // join: the caller's stream continues when every range is through (the move stream is: range 0 waited for its last launch)
     hipError_t jerr = hipSuccess;
     if (K > 0) {

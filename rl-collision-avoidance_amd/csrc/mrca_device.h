@@ -1199,4 +1199,30 @@ MRCA_HD void open_episode(const EpisodeRules& r, float x, float y, float gx, flo
     if (!r.hold_velocity) speed_v = speed_w = 0.0f;
 }
 
+// The scan ring of ONE robot over a ray-cast launch that covers T consecutive ticks (T <= F frames, raycast_ticks_kernel).
+// Tick after tick the rule is: a fresh tick (the robot's episode began in it) writes its scan into all F slots and leaves
+// the head where it is; any other tick advances the head and writes that slot.  The workgroups of one launch run in no
+// particular order, so tick j of the launch STORES exactly the slots it writes tick after tick and no later tick of the
+// launch writes -- what it leaves out are a restart's duplicate copies and a row a restart up to two ticks later overwrites:
+// every slot has at most one writer per launch, and it is the last writer of the sequential order.
+//   h0: the head before the launch's first tick; fresh_bits: bit t = tick t of the launch is fresh for this robot.
+//   -> stores: bit s = tick j stores slot s; head: the head after the launch's last tick.
+struct RingStores {
+    uint32_t stores;
+    int head;
+};
+MRCA_HD RingStores ring_rule(int F, int T, int h0, uint32_t fresh_bits, int j) {
+    const uint32_t all = (1u << F) - 1u;
+    int h = h0;
+    uint32_t mine = 0u, later = 0u;
+    for (int t = 0; t < T; ++t) {
+        const bool fresh = ((fresh_bits >> t) & 1u) != 0u;
+        h = fresh ? h : (h + 1 == F ? 0 : h + 1);
+        const uint32_t w = fresh ? all : 1u << h;
+        mine = t == j ? w : mine;
+        later |= t > j ? w : 0u;
+    }
+    return RingStores{mine & ~later, h};
+}
+
 }  // namespace mrca

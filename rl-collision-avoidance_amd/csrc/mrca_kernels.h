@@ -7,6 +7,8 @@
 
 namespace mrca {
 
+constexpr int kWave = 64;   // lanes of a wavefront
+
 // Everything a kernel needs.  All pointers are device memory inside the env's arena.  Most kernels take it by value (kernarg
 // segment); the two of the tick -- move_kernel, raycast_kernel -- read the env's DEVICE copy of it (`dev`) and take what
 // differs from launch to launch as small arguments of their own (MoveOut / RayIn): a launch costs the host 2.6 us with up
@@ -159,6 +161,29 @@ struct RayIn {
 #endif
 };
 
+// A ray cast of several consecutive ticks of mrca_step_many in one launch (mrca_raycast_ticks.hip): tick j of the launch reads
+// the slot that begins j * stride bytes behind tick 0's -- its pose there, head record / goal / fresh flags / outlines at the
+// four offsets -- or, as the launch's LAST tick when last_is_env is set, the env's own fields.  The ring heads are read from
+// head_in and left in head_out by the launch's last tick: two different arrays, no workgroup reads what another one writes.
+struct RayTicksIn {         // (the kernel's arguments behind the 14 leading dwords)
+    const float4* env_head; // (filled in by launch_raycast_ticks: e.head)
+    const uint8_t* head_in;
+    uint8_t* head_out;
+    uint32_t off_goal, off_fresh, off_outline;
+#if defined(MRCA_PROFILING)
+    unsigned long long* launch_stamps;
+    int32_t launch_slot;
+#endif
+};
+struct RayTicks {
+    int32_t ticks;          // 1 .. min(F, 8)
+    int32_t last_is_env;
+    const char* slot0;
+    int32_t stride;
+    uint32_t off_head;
+    RayTicksIn in;
+};
+
 size_t ray_lds_bytes(const EnvView& e);
 size_t move_lds_bytes(const EnvView& e);
 
@@ -172,6 +197,8 @@ void launch_reset(const EnvView& e, const uint8_t* mask, const float* poses, con
 void launch_head_init(const EnvView& e, hipStream_t s);
 void launch_lidar_grid(const EnvView& e, int counted, hipStream_t s);   // big worlds: hash of the current poses for the ray cast
 void launch_raycast(const EnvView& e, int only_fresh, hipStream_t s, hipEvent_t start = nullptr, hipEvent_t stop = nullptr);
+// e: the env's own view with the range in ray_first / ray_count (small worlds, lazy_obs views only)
+void launch_raycast_ticks(const EnvView& e, const RayTicks& t, hipStream_t s);
 #if defined(MRCA_PROFILING)
 void read_ray_stamps(unsigned long long* host, int blocks);     // profiling build: [2 waves][7 stamps][blocks] of raycast_kernel
 void read_move_stamps(unsigned long long* host, int worlds);   // profiling build: s_memtime stamps of move_kernel's phases

@@ -1,0 +1,454 @@
+// mrca_raycast_body.h -- what one workgroup of a ray cast does for its robot: raycast_body, shared by the single-tick
+// raycast_kernel (mrca_kernels.hip) and raycast_ticks_kernel (mrca_raycast_ticks.hip), which casts several ticks of
+// mrca_step_many in one launch.  Device code only.
+#pragma once
+#include "mrca_kernels.h"
+
+namespace mrca {
+
+namespace {
+
+// the profiling build's phase stamps (mrca_kernels.hip defines them before it includes this file)
+#if !defined(MRCA_RSTAMP)
+#define MRCA_RSTAMP(k) do { } while (0)
+#endif
+
+// A launch of several ticks (raycast_body<..., TICKS = true>): which tick of the launch this workgroup casts and where the
+// fresh flags of all its ticks and the two head arrays are.  The single-tick kernel passes an empty one.
+typedef __attribute__((address_space(1))) uint8_t GlobalByte;
+struct RayTick {
+    int j, T;                       // this workgroup's tick of the launch's T
+    const uint8_t* fresh0;          // tick 0's fresh flags; tick t's lie t * stride bytes on ...
+    long long stride;
+    const uint8_t* fresh_env;       // ... except the last tick's when it is the env's own field (else NULL)
+    const uint8_t* head_in;         // the ring heads before the launch's first tick
+    uint8_t* head_out;              // ... and where its last tick leaves them (never the same array)
+};
+
+// LDS |= without a return value (ds_or_b64): nothing to wait for
+__device__ __forceinline__ void mask_or(unsigned long long* p, unsigned long long v) {
+    (void)__hip_atomic_fetch_or(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+
+// blockIdx -> robot: consecutive robots (one world's robots) share an XCD's L2 (block b runs on
+// XCD b % 8, guide T1); a pure permutation, so correctness never depends on it.
+// (unsigned arithmetic: b and N are never negative, and a signed % 8 and / 8 are eleven scalar instructions where three do)
+__device__ __forceinline__ int block_to_robot(int b, int N) {
+    const uint32_t ub = (uint32_t)b, un = (uint32_t)N;
+    if (un & 7u) return b;
+    return (int)((ub & 7u) * (un >> 3) + (ub >> 3));
+}
+
+// The march reads the free-rectangle field straight from its L1/L2-resident global copy: ~2 dependent
+// lookups per ray.  (Staging a tile of it in LDS per robot was measured slower at every granularity tried,
+// the tile costs more to fill than the few lookups it serves.  So were persistent workgroups
+// walking several robots each -- 39 vs 37 us, profiles/r01/r01_ad_ablation.txt -- and nontemporal stores made
+// no difference.)  Marching the K beams of a thread in LOCK STEP (grid_march_skip_n: K lookups in flight per wait) is
+// implemented and measured too: slower than one after the other (34.7 vs 28.1 us, profiles/r02/r02_c_*), see mrca_abi.hip.
+// RKW > 0: fidelity mode's lidar (the other robots seen through the collision raster; RKW = cells per side of an outline's
+// window, 4 or 8) -- a kernel of its own so that the default one does not carry the code: with the raster path behind a
+// run-time branch the default launch was 0.85 us slower (A/B on one box, profiles/r04_h_ab_raster_path_in_default_kernel.txt:
+// twice the instructions for the same instruction cache).  Since round 5 a beam's return from another robot's outline is a
+// closed form over that robot's 16-byte outline record (ray_outline_entry) instead of a walk through a window of LDS bits.
+// TICKS: the workgroup casts tick mt.j of a launch of mt.T ticks (raycast_ticks_kernel) -- pose_p / head_p / e.goal / e.outline
+// are that tick's; what differs is the ring's bookkeeping (ring_rule, mrca_device.h) and that only the launch's last tick
+// stores local_goal and the head.  ring_head_p is unused then.
+template <int K, bool BIG, bool SEQ, int RKW, bool VIEWS, bool TICKS = false>
+__device__ __forceinline__ void raycast_body(int only_fresh, int ray_first, int ray_count, int R_, const float* __restrict__ pose_p,
+                                             const float4* __restrict__ head_p, const float* __restrict__ bcos_p,
+                                             const float* __restrict__ bsin_p, uint8_t* ring_head_p, const EnvView& e, int views,
+                                             const RayTick& mt = RayTick{}) {
+    // (the leading arguments repeat e.ray_first, e.ray_count, e.R, e.pose, e.head, e.beam_cos, e.beam_sin, e.ring_head: 14
+    // dwords preloaded into SGPRs, see move_kernel)
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+    MRCA_RSTAMP(0);
+    const int n = ray_first + block_to_robot(blockIdx.x, ray_count);
+    const int tid = threadIdx.x;
+    // (A variant of this kernel without the early exit -- so that nothing is waited for before every request of the
+    // workgroup is out -- was measured and changed nothing: 27.96 us either way, profiles/r03/r03_l_bench_env.json.  The
+    // launch uses ~45 % of the VALU issue slots: what it waits for is a workgroup's chain of dependent round trips at full
+    // occupancy, and one early exit less does not shorten that chain -- DESIGN.md 5.2.)
+    if (only_fresh && e.fresh[n] == 0) return;  // block-uniform
+
+    float4* nb = reinterpret_cast<float4*>(lds);
+    int2* nbi = reinterpret_cast<int2*>(nb + kWave);
+    int* nb_count = reinterpret_cast<int*>(nbi + kWave);
+    unsigned long long* nbmask = reinterpret_cast<unsigned long long*>(nb_count + 4);   // [B] neighbours per beam
+    int* nb_more = nb_count + 1;                                      // big worlds: another chunk of neighbours follows
+    // fidelity mode (never in big worlds): the neighbours' outline records
+    constexpr bool raster = RKW > 0 && !BIG;
+    int4* nbo = reinterpret_cast<int4*>(nbmask + e.B);   // [64] OutlineBits as (ax, ay, lo, hi)
+
+    const int T = e.B / K;                    // marching threads
+    const bool extra = (int)blockDim.x > T;   // a dedicated preparation wave sits behind the marching ones
+    const int prep_base = extra ? T : 0;
+    const bool is_prep = tid >= prep_base && tid < prep_base + kWave;   // wave-uniform
+    const bool marches = tid < T;                                       // wave-uniform
+    // n / R without the ~25 scalar instructions of a 32-bit division: small worlds (R <= 64, n < 2^24) take the exact multiply-high
+    // with the host's ceil(2^32 / R) (error n x (m R - 2^32) < 2^24 x 64 < 2^32).  (A scalar instruction costs the launch twice
+    // what a vector one costs -- one scalar unit per CU for 32 waves: profiles/r06_ac_*.)
+    const int world = BIG ? n / R_ : (R_ == 1 ? n : (int)__umulhi((uint32_t)n, e.r_magic));   // (2^32 / 1 does not fit the magic)
+    const int local = n - world * R_;
+    // the robot's own record: pose, sin / cos and the field entry of its cell.  Block-uniform -- but fetched with VECTOR
+    // loads (the index goes through an opaque zero): as scalar loads they shared the out-of-order scalar counter with
+    // the kernel arguments, and the neighbour candidate below could not be requested before they were back.
+    // (Not in big worlds: there the neighbour enumeration hashes the robot's cell per chunk, wave-uniform work that
+    // belongs on the scalar unit -- measured: 513 vs 492 us per 50 000-robot launch, profiles/r03/r03_s_bigworld_shards8.jsonl.)
+    int lane_zero = 0;
+    if constexpr (!BIG) asm volatile("v_mov_b32 %0, 0" : "=v"(lane_zero));
+    const int nv = n + lane_zero;
+    const float x = pose_p[nv * 3 + 0], y = pose_p[nv * 3 + 1];
+    const float4 hd = head_p[nv];
+    const float s = hd.x, c = hd.y;
+    // the preparation wave requests "its" neighbour candidate in the same memory round trip
+    const int pl = tid - prep_base;
+    const bool cand = !BIG && is_prep && (pl < R_) && (pl != local);
+    const int jn = world * R_ + (cand ? pl : local);
+    float xj = 0.0f, yj = 0.0f;
+    float4 hj = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    int4 oj = make_int4(0, 0, 0, 0);
+    if (!BIG && is_prep) {
+        xj = pose_p[jn * 3 + 0];
+        yj = pose_p[jn * 3 + 1];
+        if constexpr (raster) oj = reinterpret_cast<const int4*>(e.outline)[jn];
+        else hj = head_p[jn];
+    }
+    // beam directions in the robot frame for this thread's K beams (tid + k*T)
+    float bc[K], bs[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        const int b = (marches ? tid : 0) + k * T;
+        bc[k] = bcos_p[b];
+        bs[k] = bsin_p[b];
+    }
+    // slot of the newest frame so far (read by every thread BEFORE the first barrier, advanced by thread 0 after it) and
+    // the fresh flag: requested last, used last
+    // (TICKS: lane t of every wave requests tick t's flag -- the T bytes ring_rule wants, in the same round trip -- and the
+    // head comes from the array no workgroup of this launch writes)
+    uint8_t fresh_byte;
+    int ring_slot;
+    if constexpr (TICKS) {
+        // (every lane loads -- lanes T and up tick 0's flag again, masked out at the ballot -- and through a global address:
+        // behind a branch or as a flat load the request would wait for every other one of the prologue)
+        const int lt = tid & (kWave - 1);
+        const int t = lt < mt.T ? lt : 0;
+        const bool own = mt.fresh_env != nullptr && t == mt.T - 1;
+        const unsigned long long fa = own ? (unsigned long long)mt.fresh_env : (unsigned long long)mt.fresh0 + (long long)t * mt.stride;
+        fresh_byte = *reinterpret_cast<const GlobalByte*>(fa + (unsigned long long)n);
+        ring_slot = mt.head_in[nv];
+    } else {
+        fresh_byte = e.fresh[n];
+        ring_slot = ring_head_p[n];
+    }
+    // (The frame stack -- ppo_stage1.py:87-89: popleft / append -- is a ring of raw scans: only the newest one is written,
+    // into the slot behind the previous newest one; see materialize_kernel.)
+    // big worlds: the candidates come from the lidar hash (3 x 3 cells of 6.5 m around the robot's cell) and may
+    // exceed the 64 a chunk holds: the preparation wave walks the nine bucket ranges 64 entries at a time and hands
+    // the marching threads one chunk of <= 64 neighbours per barrier pair (see the chunk loop below).
+    // The nine ranges are ONE list to it: lanes 0..8 fetch "their" cell's range in the same memory round trip, a prefix sum
+    // over those lanes numbers the entries, and a batch of 64 takes entries off.. off + 63 of that list whichever cells they
+    // belong to.  (Rounds 2-3 walked the cells one after the other -- range, entry, pose, head: four dependent round trips
+    // per cell, 36 per workgroup, and a workgroup lived 25 us whatever else the chip was doing:
+    // profiles/r04_o_slice_sweep.txt.  Now it is five.)
+    int big_off = 0;                   // enumeration state of the preparation wave (wave-uniform): entries consumed so far
+    auto big_chunk = [&]() {
+        const int icx = hash_cell_coord(x, kLidarCell), icy = hash_cell_coord(y, kLidarCell);
+        for (int b = pl; b < e.B; b += kWave) nbmask[b] = 0ull;
+        int cell_start = 0, cell_count = 0;
+        if (pl < 9) {
+            const uint32_t h = hash_cell(icx + pl % 3 - 1, icy + pl / 3 - 1, world) & (uint32_t)e.bw_lmask;
+            cell_start = e.bw_lstart[h];
+            cell_count = e.bw_lstart[h + 1] - cell_start;
+        }
+        int cell_end = cell_count;         // inclusive prefix sum over lanes 0..8 (lanes >= 9 hold zeros)
+#pragma unroll
+        for (int d = 1; d < 16; d <<= 1) {
+            const int up = __shfl_up(cell_end, d, kWave);
+            if (pl >= d) cell_end += up;
+        }
+        const int total = __shfl(cell_end, 8, kWave);
+        int cnt = 0;
+        while (big_off < total) {
+            const int entry = big_off + pl;
+            int q = 0;                     // the cell entry falls into: the number of cells ending at or before it
+#pragma unroll
+            for (int t = 0; t < 8; ++t) q += __shfl(cell_end, t, kWave) <= entry ? 1 : 0;
+            const bool valid = entry < total;          // then q <= 8
+            q = valid ? q : 0;
+            const int qx = icx + q % 3 - 1, qy = icy + q / 3 - 1;
+            const int q_end = __shfl(cell_end, q, kWave), q_count = __shfl(cell_count, q, kWave);
+            const int idx = __shfl(cell_start, q, kWave) + (entry - (q_end - q_count));
+            const int j = valid ? e.bw_lsorted[idx] : -1;
+            bool keep = false;
+            float cxj = 0.0f, cyj = 0.0f;
+            float4 chj = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            int lo = 0, hi = -1;
+            if (j >= 0 && j != n && j / R_ == world) {
+                cxj = pose_p[j * 3 + 0];
+                cyj = pose_p[j * 3 + 1];
+                // a bucket may hold other cells too (hash collisions) and the same bucket may serve two of the nine
+                // cells: a robot counts only for the cell it really is in, so nobody is listed twice
+                if (hash_cell_coord(cxj, kLidarCell) == qx && hash_cell_coord(cyj, kLidarCell) == qy) {
+                    const float ddx = cxj - x, ddy = cyj - y;
+                    if (ddx * ddx + ddy * ddy <= kLidarReach2) {
+                        beam_interval(ddx * c + ddy * s, ddy * c - ddx * s, e.B, e.beam_step, e.beam_inv_step, e.lidar_radius,
+                                      e.lidar_near, &lo, &hi);
+                        keep = lo <= hi;
+                        if (keep) chj = head_p[j];
+                    }
+                }
+            }
+            const unsigned long long m = __ballot(keep);
+            const int add = __popcll(m);
+            if (cnt + add > kWave) break;          // this batch opens the next chunk
+            if (keep) {
+                const int idx2 = cnt + __popcll(m & ((1ull << pl) - 1ull));
+                float olx, oly;         // the lidar's origin in the neighbour's frame: once per neighbour, not per beam
+                ray_box_origin(x, y, cxj, cyj, chj.x, chj.y, &olx, &oly);
+                nb[idx2] = make_float4(olx, oly, chj.x, chj.y);
+                nbi[idx2] = make_int2(lo, hi);
+            }
+            cnt += add;
+            big_off += kWave;
+        }
+        if (pl == 0) {
+            *nb_count = MRCA_DBG(e, 1) ? 0 : cnt;
+            *nb_more = big_off < total ? 1 : 0;
+        }
+        for (int k = 0; k < cnt; ++k) {
+            const int2 iv = nbi[k];
+            for (int b = iv.x + pl; b <= iv.y; b += kWave) mask_or(&nbmask[b], 1ull << k);
+        }
+    };
+    MRCA_RSTAMP(1);     // robot record, beam table, neighbour candidate requested (debug flag 64: arrived)
+    if (is_prep) {
+      if constexpr (BIG) {
+        big_chunk();
+      } else {
+        for (int b = pl; b < e.B; b += kWave) nbmask[b] = 0ull;
+        const float ddx = xj - x, ddy = yj - y;
+        // conservative cull: a hit below 6 m needs the centre within 6 + circumradius(0.2907) m (fidelity mode: + one
+        // raster-cell diagonal -- what is tested there are the robot's outline CELLS)
+        bool keep = cand && (ddx * ddx + ddy * ddy <= e.lidar_reach2);
+        int lo = 0, hi = -1;
+        if (keep) {
+            beam_interval(ddx * c + ddy * s, ddy * c - ddx * s, e.B, e.beam_step, e.beam_inv_step, e.lidar_radius, e.lidar_near,
+                          &lo, &hi);
+            keep = lo <= hi;
+        }
+        const unsigned long long m = __ballot(keep);
+        if (keep) {
+            const int idx = __popcll(m & ((1ull << pl) - 1ull));
+            // the slab tests want the lidar's origin in the neighbour's frame (once per neighbour, not per beam); the
+            // fidelity mode's closed form wants the neighbour's outline record
+            if constexpr (raster) {
+                nbo[idx] = oj;
+            } else {
+                float olx, oly;
+                ray_box_origin(x, y, xj, yj, hj.x, hj.y, &olx, &oly);
+                nb[idx] = make_float4(olx, oly, hj.x, hj.y);
+            }
+            nbi[idx] = make_int2(lo, hi);
+        }
+        const int cnt0 = MRCA_DBG(e, 1) ? 0 : __popcll(m);
+        if (pl == 0) *nb_count = cnt0;
+        // scatter: bit k of nbmask[b] = "neighbour k can touch beam b".  ds_or_b64 without a return value: the wave
+        // fires one per neighbour and moves on (as a read-modify-write every neighbour cost an LDS round trip, ~2 000
+        // of the 5 600 ticks wave 0 spent preparing, profiles/r03/r03_k_ablate_raycast_phase_stamps.txt).
+        for (int k = 0; k < cnt0; ++k) {
+            const int2 iv = nbi[k];
+            for (int b = iv.x + pl; b <= iv.y; b += kWave) mask_or(&nbmask[b], 1ull << k);
+        }
+      }
+    }
+    MRCA_RSTAMP(2);     // wave 0: neighbour list and per-beam masks built
+    // --- the march: K beams per thread in lock step
+    float dx[K], dy[K], rng[K];
+    bool from_robot[K];        // the range is a return from another robot (ranger_return 0.5: LaserScan intensity 0)
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        dx[k] = c * bc[k] - s * bs[k];
+        dy[k] = s * bc[k] + c * bs[k];
+        rng[k] = kRangeMax;
+        from_robot[k] = false;
+    }
+    if (marches && !MRCA_DBG(e, 2)) {
+        const FreeRectField field{e.free_rect, e.g.width, e.g.height, e.free_rect_pitch};
+        MarchOrigin org;                       // once per robot: shared by all its beams
+        org.fx = (x - e.g.x0) * e.g.inv_cell;
+        org.fy = (y - e.g.y0) * e.g.inv_cell;
+        org.ix0 = (int)floorf(org.fx);
+        org.iy0 = (int)floorf(org.fy);
+        org.v_lo = __float_as_uint(hd.z);
+        org.v_hi = __float_as_uint(hd.w);
+        // Big worlds are open worlds (scenario.circle_big: the map is a token patch at the origin, the robots stand
+        // kilometres from it), and outside the map the field knows nothing: a ray crawls from cell to cell, one dependent
+        // lookup of the zero border each -- 40 000 of the 54 000 ticks a workgroup of the 50 000-robot circle lived
+        // (profiles/r04_t_bigworld_raycast_phases.txt), to return kRangeMax.  A robot whose 6 m cannot reach the map's
+        // bounding box (two cells of slack for the roundings of fx / fy) has nothing to march through: every beam is
+        // kRangeMax exactly as the march would return it.
+        bool map_in_reach = true;
+        if constexpr (BIG) {
+            const float reach = kRangeMax * e.g.inv_cell + 2.0f;
+            map_in_reach = org.fx + reach >= 0.0f && org.fx - reach <= (float)e.g.width && org.fy + reach >= 0.0f &&
+                           org.fy - reach <= (float)e.g.height;
+        }
+        if (map_in_reach) {
+            if constexpr (K == 1 || SEQ) {   // one ray at a time: the hand-tuned single-ray loop (54 VALU per jump)
+#pragma unroll
+                for (int k = 0; k < K; ++k) rng[k] = grid_march_skip(field, e.g, org, dx[k], dy[k], kRangeMax);
+            } else {                         // K rays in lock step: K lookups in flight per wait
+                grid_march_skip_n<K>(field, e.g, org, dx, dy, kRangeMax, rng);
+            }
+        }
+    }
+    MRCA_RSTAMP(3);     // this wave's beams marched
+    __syncthreads();  // neighbour list ready (the preparation wave built it while the others marched)
+    MRCA_RSTAMP(4);     // through the barrier / past the flag
+    if constexpr (!BIG) {
+        if (!marches) return;  // the dedicated preparation wave is done (whole wave: the barrier below counts live waves)
+    }
+    for (;;) {
+        const int cnt = *nb_count;
+        const int more = BIG ? *nb_more : 0;
+        if (marches) {
+#pragma unroll
+            for (int k = 0; k < K; ++k) {
+                const int b = tid + k * T;
+                float r = rng[k];
+                unsigned long long m = cnt > 0 ? nbmask[b] : 0ull;
+                if constexpr (raster) {
+                    // fidelity mode: the entry time of the first raster cell of each flagged neighbour's outline the beam's
+                    // walk visits -- in closed form, the same times grid_march's walk over the raster would compare
+                    if (m) {
+                        const float fxr = x * e.raster_inv, fyr = y * e.raster_inv;
+                        const int ixr = (int)floorf(fxr), iyr = (int)floorf(fyr);
+                        const float tmax_c = kRangeMax * e.raster_inv;
+                        const float inv_dx = dx[k] != 0.0f ? rcp_exact(dx[k]) : kInf;
+                        const float inv_dy = dy[k] != 0.0f ? rcp_exact(dy[k]) : kInf;
+                        // (the 4 x 4 form: an axis the ray never steps along gets origin -inf, see ray_outline_entry4)
+                        const float fxe = dx[k] != 0.0f ? fxr : -kInf, fye = dy[k] != 0.0f ? fyr : -kInf;
+                        const bool xpos = dx[k] > 0.0f, ypos = dy[k] > 0.0f;
+                        do {
+                            const int q = __ffsll((long long)m) - 1;
+                            m &= m - 1;
+                            const int4 oq = nbo[q];
+                            const OutlineBits ob{oq.x, oq.y, (uint32_t)oq.z, (uint32_t)oq.w};
+                            const float tc = RKW == 4 ? ray_outline_entry4(fxe, fye, ixr, iyr, xpos, ypos, inv_dx, inv_dy, ob)
+                                                      : ray_outline_entry<RKW>(fxr, fyr, ixr, iyr, dx[k], dy[k], inv_dx, inv_dy, ob);
+                            const float t = tc < tmax_c ? tc * e.raster_res : kInf;
+                            from_robot[k] = from_robot[k] || t < r;
+                            r = t < r ? t : r;
+                        } while (m);
+                    }
+                } else {
+                    while (m) {
+                        const int q = __ffsll((long long)m) - 1;
+                        m &= m - 1;
+                        const float4 nbq = nb[q];
+                        const float t = ray_box_local(nbq.x, nbq.y, dx[k], dy[k], nbq.z, nbq.w);
+                        from_robot[k] = from_robot[k] || t < r;
+                        r = t < r ? t : r;
+                    }
+                }
+                rng[k] = r;
+            }
+        }
+        if (!more) break;
+        __syncthreads();          // everybody is through with this chunk ...
+        if (is_prep) big_chunk();
+        __syncthreads();          // ... and the next one is ready
+    }
+    if (!marches) return;
+    MRCA_RSTAMP(5);     // neighbour slab tests done
+    // --- the scan (stageros.cpp:479-516) goes into the ring slot behind the newest one -- ONE store stream: the
+    //     observation x / 6 - 0.5 (stage_world1.py:140) and the deque order (ppo_stage1.py:59-60,87-89) are the readers'
+    //     business (materialize_kernel).  Every thread stores its own beams -- lane l of a wave holds beam base + l, so
+    //     each store instruction of a wave covers 256 contiguous bytes.
+    {
+        // (row = n x F fits 32 bits -- n < 2^24, F <= 8 --: one 32 x 32 -> 64 multiply per address instead of a 64 x 32 chain of ten)
+        const uint32_t row = (uint32_t)n * (uint32_t)e.F;
+        float* ring_row = e.scan_ring + (size_t)row * (uint32_t)e.B;
+        const int words = e.B >> 6;
+        unsigned long long* hit_row = e.hit_bits + (size_t)row * (uint32_t)words;
+        int new_slot;
+        bool fresh;
+        uint32_t stores = 0u;     // TICKS: the slots this tick of the launch stores (ring_rule)
+        int head_after = 0;       // TICKS: the head behind the launch's last tick
+        if constexpr (TICKS) {
+            // (the head stays in a vector register: the rule's few operations per tick go to the vector unit, see the note on
+            // scalar instructions above)
+            const uint32_t fresh_bits = (uint32_t)__ballot(fresh_byte != 0 && (tid & (kWave - 1)) < mt.T);
+            const RingStores rs = ring_rule(e.F, mt.T, ring_slot, fresh_bits, mt.j);
+            stores = (uint32_t)__builtin_amdgcn_readfirstlane((int)rs.stores);
+            head_after = rs.head;
+            fresh = ((fresh_bits >> mt.j) & 1u) != 0u;
+            new_slot = __ffs((int)stores) - 1;      // (a tick that is not fresh writes one slot, or none that survives)
+        } else {
+            new_slot = ring_slot + 1 == e.F ? 0 : ring_slot + 1;
+            fresh = __builtin_amdgcn_readfirstlane((int)fresh_byte) != 0;
+        }
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            const int b = tid + k * T;
+            // (|x|: fidelity mode's closed form may return -0.0 for a beam that starts inside a marked cell)
+            const float r = fabsf(rng[k] < kRangeMax ? rng[k] : kRangeMax);
+            // what the beam hit: one bit per beam beside the ring (MRCA_F_HIT_BITS), set = another robot.  stageros casts
+            // Stage's return value to uint8 for LaserScan.intensities (stageros.cpp:506): 1 floorplan, 0 robot or miss.  A wave
+            // holds 64 consecutive beams (T is a multiple of 64: product_ray_shift), so its ballot IS the row's word b >> 6.
+            // (ABI 4-5 kept the flag in the range's sign bit: a reader that forgot |x| got negative ranges.)
+            const unsigned long long hm = __ballot(from_robot[k] && rng[k] < kRangeMax);
+            const bool word_lane = (tid & (kWave - 1)) == 0;
+            // (nontemporal stores: the launch does not read its rows again.  Measured A/B on one box, round 4: 21.7 us with
+            // them, 22.9 us with plain stores (profiles/r04_g_ab_nontemporal_row_stores.txt) -- although FETCH_SIZE does not
+            // move, 2502 vs 2504 KiB: what they relieve is the write path, not the free-rectangle field's residency)
+            if (fresh) {     // deque([obs] * F), ppo_stage1.py:59-60: every slot, the head stays where it is
+                for (int f = 0; f < e.F; ++f) {
+                    if (TICKS && !((stores >> f) & 1u)) continue;       // a later tick of the launch writes this slot
+                    __builtin_nontemporal_store(r, &ring_row[f * e.B + b]);
+                    if (word_lane) hit_row[f * words + (b >> 6)] = hm;
+                }
+            } else if (!TICKS || stores) {
+                __builtin_nontemporal_store(r, &ring_row[new_slot * e.B + b]);
+                if (word_lane) hit_row[new_slot * words + (b >> 6)] = hm;
+            }
+            // lazy_obs = 0: the two reference-shaped views of this robot, formed here instead of by a materialize_kernel launch
+            // behind every ray cast (get_laser_observation, stage_world1.py:127-141: the newest scan; the stack in deque order,
+            // x / 6 - 0.5) -- the same numbers: norm_obs of the ring's rows, the older ones as earlier launches stored them.  The
+            // launch uses 5 % of HBM: the 8 kB per robot ride along (131 -> ... M agent-steps/s for a reference-shaped caller).
+            if (VIEWS && views) {
+                const float nr = norm_obs(r);
+                // (nontemporal like the ring row: the launch does not read them again)
+                if (views & 1) __builtin_nontemporal_store(r, &e.scan[(size_t)n * (uint32_t)e.B + b]);
+                if (views & 2) {
+                    float* dst = e.obs + (size_t)row * (uint32_t)e.B + b;
+                    if (fresh) {
+                        for (int f = 0; f < e.F; ++f) __builtin_nontemporal_store(nr, &dst[f * e.B]);
+                    } else {
+                        int slot = new_slot;
+                        for (int f = 0; f < e.F - 1; ++f) {        // oldest first: the slot behind the newest, and on round the ring
+                            slot = slot + 1 == e.F ? 0 : slot + 1;
+                            __builtin_nontemporal_store(norm_obs(fabsf(ring_row[slot * e.B + b])), &dst[f * e.B]);
+                        }
+                        __builtin_nontemporal_store(nr, &dst[(e.F - 1) * e.B]);
+                    }
+                }
+            }
+        }
+        if constexpr (TICKS) {
+            if (tid == 0 && mt.j == mt.T - 1) mt.head_out[n] = (uint8_t)head_after;
+        } else {
+            if (tid == 0 && !fresh) ring_head_p[n] = (uint8_t)new_slot;
+        }
+    }
+    if (tid == 0 && (!TICKS || mt.j == mt.T - 1)) {  // get_local_goal (stage_world1.py:155-160)
+        const float gx = e.goal[n * 2 + 0] - x, gy = e.goal[n * 2 + 1] - y;
+        e.local_goal[n * 2 + 0] = gx * c + gy * s;
+        e.local_goal[n * 2 + 1] = gy * c - gx * s;
+    }
+    MRCA_RSTAMP(6);     // stores issued (debug flag 64: acknowledged)
+}
+
+}  // namespace
+
+}  // namespace mrca

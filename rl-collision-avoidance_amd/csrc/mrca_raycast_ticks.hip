@@ -1,0 +1,99 @@
+// mrca_raycast_ticks.hip -- the ray casts of several consecutive ticks of one world range in ONE launch (mrca_step_many's
+// run-ahead schedule).
+//
+// Inside a run-ahead pass the ray casts of ticks k, k + 1, k + 2 do not depend on each other: each reads its own slot of the
+// move ring (pose, head record, goal, fresh flag, outline) and they meet only in the scan ring's slot bookkeeping, which
+// ring_rule (mrca_device.h) settles without any workgroup reading what another one of the launch writes.  A launch of T ticks
+// is a grid of (robots of the range) x T workgroups, tick-major: a tick's workgroups are dispatched before the next tick's, and
+// within a tick the block -> robot map is the single-tick kernel's (workgroup (b, j) has linear id j x robots + b: the same
+// XCD as block b of a single-tick launch whenever the map uses XCDs at all, robots % 8 == 0).  Workgroup (b, j) runs
+// raycast_body for its robot against tick j's slot.  What a launch of several residency rounds buys: its later rounds start
+// as workgroups of the earlier ones retire, not behind a launch boundary.
+//
+// A translation unit and a kernel of its own, so that the single-tick raycast_kernel carries none of this (the project's rule
+// for the VIEWS and raster paths too).  Never big worlds, never the lazy_obs = 0 epilogue (it reads rows earlier ticks stored).
+#include "mrca_kernels.h"
+
+#include <hip/hip_ext.h>
+
+#include "mrca_raycast_body.h"
+
+namespace mrca {
+
+namespace {
+
+// The leading 14 dwords (preloaded into SGPRs) are what the prologue needs first: the launch's range, where tick j's pose and
+// head record are, the beam table, the env's own pose; the env's head record -- the last tick's second load -- comes with the
+// rest.  `ticks`: T | last_is_env << 8.  104 bytes of arguments (a launch costs the host more from 128 bytes on,
+// tools/launch_cost_probe.hip).
+template <int K, bool SEQ, int RKW>
+__global__ __launch_bounds__(1024, (RKW == 4 ? 8 : 1)) void raycast_ticks_kernel(int ray_first, int ray_count, int R_, int ticks,
+                                                       const char* __restrict__ slot0, int stride, uint32_t off_head,
+                                                       const float* __restrict__ bcos_p, const float* __restrict__ bsin_p,
+                                                       const float* __restrict__ env_pose, const EnvView* __restrict__ view_p,
+                                                       RayTicksIn in) {
+    EnvView e = *view_p;        // (the env's view from device memory: its pose / head / goal / fresh / outline are slot 0's)
+    const int T = ticks & 0xff, j = blockIdx.y;
+    const bool last_is_env = (ticks >> 8) != 0;
+    const bool own = last_is_env && j == T - 1;          // workgroup-uniform: this tick reads the env's own fields
+    const char* slot = slot0 + (long long)j * stride;
+    const float* pose_p = own ? env_pose : reinterpret_cast<const float*>(slot);
+    const float4* head_p = own ? in.env_head : reinterpret_cast<const float4*>(slot + off_head);
+    if (!own) {
+        e.goal = reinterpret_cast<float*>(const_cast<char*>(slot + in.off_goal));
+        e.outline = reinterpret_cast<OutlineBits*>(const_cast<char*>(slot + in.off_outline));
+    }
+    e.pose = const_cast<float*>(pose_p);
+    e.head = const_cast<float4*>(head_p);
+    const RayTick mt{j, T, reinterpret_cast<const uint8_t*>(slot0 + in.off_fresh), (long long)stride,
+                     last_is_env ? e.fresh : nullptr, in.head_in, in.head_out};
+#if defined(MRCA_PROFILING)
+    e.launch_stamps = in.launch_stamps;
+    e.launch_slot = in.launch_slot;
+#endif
+    MRCA_LAUNCH_BEGIN(e);
+    raycast_body<K, false, SEQ, RKW, false, true>(0, ray_first, ray_count, R_, pose_p, head_p, bcos_p, bsin_p, nullptr, e, 0, mt);
+    MRCA_LAUNCH_END(e);
+}
+
+}  // namespace
+
+void launch_raycast_ticks(const EnvView& e, const RayTicks& t, hipStream_t s) {
+    if (e.ray_count <= 0 || t.ticks <= 0) return;
+    const bool raster_mode = e.raster_inv > 0.0f;
+    // (the shapes of launch_raycast)
+    const int threads = raster_mode ? (e.B >> (e.ray_shift == 0 ? 0 : 1)) : (e.B >> e.ray_shift) + (e.ray_prep_wave ? kWave : 0);
+    const size_t lds = ray_lds_bytes(e);
+    const dim3 grid(e.ray_count, t.ticks);
+    const bool seq = e.ray_sequential != 0;
+    const int ticks = t.ticks | (t.last_is_env ? 1 << 8 : 0);
+    RayTicksIn in = t.in;
+    in.env_head = e.head;
+#define MRCA_RAYT(K, SEQ, RKWV)                                                                                              \
+    hipLaunchKernelGGL((raycast_ticks_kernel<K, SEQ, RKWV>), grid, dim3(threads), lds, s, e.ray_first, e.ray_count, e.R, ticks,  \
+                       t.slot0, t.stride, t.off_head, e.beam_cos, e.beam_sin, e.pose, e.dev, in)
+    if (raster_mode) {
+        if (e.raster_kw <= 4) {
+            if (e.ray_shift == 0) MRCA_RAYT(1, false, 4);
+            else MRCA_RAYT(2, true, 4);
+        } else {
+            if (e.ray_shift == 0) MRCA_RAYT(1, false, 8);
+            else MRCA_RAYT(2, true, 8);
+        }
+        return;
+    }
+    switch (e.ray_shift) {
+        case 0: MRCA_RAYT(1, false, 0); break;
+        case 1:
+            if (seq) MRCA_RAYT(2, true, 0);
+            else MRCA_RAYT(2, false, 0);
+            break;
+        default:
+            if (seq) MRCA_RAYT(4, true, 0);
+            else MRCA_RAYT(4, false, 0);
+            break;
+    }
+#undef MRCA_RAYT
+}
+
+}  // namespace mrca
