@@ -21,11 +21,24 @@ pytestmark = pytest.mark.gpu
 
 CALLS = (1, 2, 3, 4, 5, 7, 38, 300)
 PASS_TICKS = 256          # csrc/mrca_abi.hip kAheadTicks (these envs are small: the ring has a slot per tick of a pass)
+def _stage1(beams=512, raster=None, **kw):
+    sc = S.stage1(**kw)
+    sc.beams = beams
+    if raster is not None:
+        sc.collision_raster = raster
+    return sc
+
+
 SHAPES = {
     "stage1_4x8": lambda: S.stage1(num_worlds=4, robots_per_world=8, seed=41),
     "stage1_3x5": lambda: S.stage1(num_worlds=3, robots_per_world=5, seed=42),       # 15 robots: no multiple of 8
     "stage2_2x44": lambda: S.stage2(num_worlds=2, seed=43),                          # group restarts: many fresh in one tick
     "stage1_fidelity_4x8": lambda: S.stage1(num_worlds=4, robots_per_world=8, seed=44, stage_resolution=True),
+    # one beam per thread (128 beams: two waves, raycast_ticks_kernel<1, false, 0>)
+    "stage1_k1_3x5": lambda: _stage1(beams=128, num_worlds=3, robots_per_world=5, seed=45),
+    # the raster lidar with the 8-cell outline window on the 0.05 m map (<2, true, 8>; several ticks per launch only under
+    # MRCA_TICKS_PER_LAUNCH=3, like the fidelity shape above)
+    "stage1_raster8_4x8": lambda: _stage1(raster=0.1, num_worlds=4, robots_per_world=8, seed=46),
 }
 EXTRA = ("scan_ring", "ring_head", "hit_bits", "fresh")
 
