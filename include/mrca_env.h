@@ -259,6 +259,28 @@ int mrca_normalize_scans(const float* in_dev, float* out_dev, size_t count, void
  * raw / beam_num per pick and truncates; mrca/vec_env.py:sparse_beam_index restates that loop). */
 int mrca_sparse_obs(mrca_env* env, const int32_t* index_dev, int32_t beam_num, float* out_dev, void* stream);
 
+/* Top-down views of worlds, rendered where the state lives (replaces: Stage's GUI window, `stageros` without -g; the
+ * reference's GIFs under doc/ are captures of it).  View v shows world views[v].world through an image of width x height pixels
+ * centred on (cx, cy) [m] at m_per_px metres per pixel, row 0 = +y, point-sampled at pixel centres (no anti-aliasing):
+ *   ids_dev   u32[V,H,W]   out: per pixel the MAXIMUM of layer << 24 | local robot index over everything that covers it --
+ *                          layers 0 background, 1 map cell occupied, 2 within 0.25 m of a MRCA_F_GOAL, 3 / 4 end of a beam of
+ *                          the newest scan that returned from the floorplan / from a robot (MRCA_F_HIT_BITS), 5 inside a
+ *                          robot's 0.44 x 0.38 footprint, 6 its front quarter; the pixels containing a robot's centre and its
+ *                          goal are always marked.  Independent of the order in which anything runs.
+ *   trail_dev u32[V,H,W]   or NULL; in/out, the caller's and persistent: max(trail, local index + 1) at the pixel containing
+ *                          each robot's centre.  Zero it to start over.
+ *   rgb_dev   u8[V,H,W,3]  or NULL; out: ids + trail through the fixed palette of DESIGN.md 5.11 (bodies coloured by
+ *                          MRCA_F_CRASHED / MRCA_F_FIRST_RESULT / MRCA_F_LIVE); 4-byte aligned.
+ * Asynchronous on `stream`; reads the env's fields as they stand at that point of the stream and writes none of them; any
+ * robots_per_world, any mode.  Three launches per 128 views (the views travel as kernel arguments: nothing is staged).
+ * Everything is validated before the first HIP call (MRCA_ERR_INVALID): num_views 1..256, width / height 1..4096, a finite
+ * centre and a finite positive m_per_px, world in range, ids_dev not NULL, no layer bit outside the enum. */
+typedef struct mrca_render_view { int32_t world; float cx, cy, m_per_px; } mrca_render_view;
+enum mrca_render_layers { MRCA_RENDER_MAP = 1, MRCA_RENDER_GOALS = 2, MRCA_RENDER_BODIES = 4, MRCA_RENDER_BEAMS = 8 };
+int mrca_render(mrca_env* env, const mrca_render_view* views /* host */, int32_t num_views, int32_t width, int32_t height,
+                uint32_t layers, uint32_t* ids_dev /* [V,H,W] */, uint32_t* trail_dev /* [V,H,W] or NULL */,
+                uint8_t* rgb_dev /* [V,H,W,3] or NULL */, void* stream);
+
 /* Synchronises `stream` and reports (then clears) the env's sticky device-side status word: MRCA_OK, or MRCA_ERR_HIP with
  * mrca_last_error() saying what went wrong on the device since the last check.  Today one condition: the ordered
  * collision pass of a world with more than 64 robots ran out of its (very long) bounded wait and left a robot

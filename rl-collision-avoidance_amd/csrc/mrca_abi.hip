@@ -21,6 +21,7 @@
 #include "mrca_host.h"
 #include "mrca_hostutil.h"
 #include "mrca_kernels.h"
+#include "mrca_render.h"
 #include "mrca_rollout_store.h"
 
 namespace {
@@ -725,6 +726,35 @@ int mrca_newest_obs(mrca_env* env, float* out_dev, void* stream) {
     if (reinterpret_cast<uintptr_t>(out_dev) % 16) return fail(MRCA_ERR_INVALID, "out_dev must be 16-byte aligned");
     DeviceGuard guard(env->cfg.device);
     mrca::launch_newest_obs(env->view, out_dev, static_cast<hipStream_t>(stream));
+    HIP_TRY(hipGetLastError());
+    return MRCA_OK;
+}
+
+static_assert(sizeof(mrca_render_view) == sizeof(mrca::RenderView) && offsetof(mrca_render_view, m_per_px) == offsetof(mrca::RenderView, m),
+              "mrca_render_view and mrca::RenderView are one layout");
+
+int mrca_render(mrca_env* env, const mrca_render_view* views, int32_t num_views, int32_t width, int32_t height, uint32_t layers,
+                uint32_t* ids_dev, uint32_t* trail_dev, uint8_t* rgb_dev, void* stream) {
+    // (what can be judged without the env comes first: a caller's mistake is named whatever else is wrong)
+    if (num_views < 1 || num_views > 256) return fail(MRCA_ERR_INVALID, "mrca_render: num_views %d outside 1..256", num_views);
+    if (!views) return fail(MRCA_ERR_INVALID, "mrca_render: views is NULL");
+    if (width < 1 || width > 4096 || height < 1 || height > 4096)
+        return fail(MRCA_ERR_INVALID, "mrca_render: image size %d x %d outside 1..4096", width, height);
+    if (layers & ~(uint32_t)(MRCA_RENDER_MAP | MRCA_RENDER_GOALS | MRCA_RENDER_BODIES | MRCA_RENDER_BEAMS))
+        return fail(MRCA_ERR_INVALID, "mrca_render: unknown layer bits 0x%x", layers);
+    if (!ids_dev) return fail(MRCA_ERR_INVALID, "mrca_render: ids_dev is NULL");
+    if (reinterpret_cast<uintptr_t>(ids_dev) % 4 || reinterpret_cast<uintptr_t>(trail_dev) % 4 || reinterpret_cast<uintptr_t>(rgb_dev) % 4)
+        return fail(MRCA_ERR_INVALID, "mrca_render: ids_dev, trail_dev and rgb_dev must be 4-byte aligned");
+    for (int32_t v = 0; v < num_views; ++v)
+        if (!(views[v].m_per_px > 0.0f) || !std::isfinite(views[v].m_per_px) || !std::isfinite(views[v].cx) || !std::isfinite(views[v].cy))
+            return fail(MRCA_ERR_INVALID, "mrca_render: view %d needs a finite centre and a finite positive m_per_px", v);
+    if (!env) return fail(MRCA_ERR_INVALID, "env is NULL");
+    for (int32_t v = 0; v < num_views; ++v)
+        if (views[v].world < 0 || views[v].world >= env->cfg.num_worlds)
+            return fail(MRCA_ERR_INVALID, "mrca_render: view %d shows world %d of %d", v, views[v].world, env->cfg.num_worlds);
+    DeviceGuard guard(env->cfg.device);
+    mrca::launch_render(env->view, reinterpret_cast<const mrca::RenderView*>(views), num_views, width, height, layers, ids_dev,
+                        trail_dev, rgb_dev, static_cast<hipStream_t>(stream));
     HIP_TRY(hipGetLastError());
     return MRCA_OK;
 }

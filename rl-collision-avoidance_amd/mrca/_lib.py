@@ -11,6 +11,7 @@ LIB_PATH = os.environ.get("MRCA_ENV_LIB") or os.path.join(_HERE, "libmrca_env.so
 
 ABI_VERSION = 6
 VIEW_SCAN, VIEW_OBS = 1, 2        # enum mrca_view
+RENDER_MAP, RENDER_GOALS, RENDER_BODIES, RENDER_BEAMS = 1, 2, 4, 8      # enum mrca_render_layers
 
 FIELDS = [  # order = enum mrca_field
     ("pose", "f32", 3), ("speed", "f32", 2), ("speed_gt", "f32", 2), ("goal", "f32", 2), ("init_pose", "f32", 3),
@@ -30,7 +31,7 @@ EXPORTS = ["mrca_abi_version", "mrca_last_error", "mrca_arena_bytes", "mrca_crea
            "mrca_rollout_store_state", "mrca_rollout_store_outcome",
            "mrca_policy_heads", "mrca_policy_heads_backward_scratch", "mrca_policy_heads_backward", "mrca_relu_cat",
            "mrca_relu_cat_backward", "mrca_policy_heads_backward_bias", "mrca_relu_cat_backward_bias_scratch",
-           "mrca_relu_cat_backward_bias"]
+           "mrca_relu_cat_backward_bias", "mrca_render"]
 # declared in include/mrca_env.h like the names above, listed apart: tests/test_abi.py's header scan reads names of letters
 # and underscores only (tests/test_policy_bf16_host.py checks these against the header and the library)
 EXPORTS_WITH_DIGITS = ["mrca_lidar_features_bf16", "mrca_lidar_features_bf16_rows", "mrca_lidar_features_bf16_backward",
@@ -41,6 +42,11 @@ class RolloutRows(C.Structure):
     """include/mrca_env.h: mrca_rollout_rows"""
     _fields_ = [(k, C.c_void_p) for k in ("frames", "fidx", "cur", "goal", "speed", "action", "logprob", "value", "reward",
                                           "done")] + [("horizon", C.c_int32)]
+
+
+class RenderView(C.Structure):
+    """include/mrca_env.h: mrca_render_view"""
+    _fields_ = [("world", C.c_int32), ("cx", C.c_float), ("cy", C.c_float), ("m_per_px", C.c_float)]
 
 
 class MrcaConfig(C.Structure):
@@ -133,6 +139,8 @@ def load(path=None):
     lib.mrca_relu_cat.argtypes = [C.c_void_p] * 3 + [C.c_int32, C.c_void_p, C.c_void_p]
     lib.mrca_relu_cat_backward.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
     lib.mrca_adam_step.argtypes = [C.c_void_p] * 4 + [C.c_int64] + [C.c_double] * 4 + [C.c_int32, C.c_void_p]
+    lib.mrca_render.argtypes = [C.c_void_p, C.POINTER(RenderView), C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                C.c_void_p, C.c_void_p]
     lib.mrca_enable_timing.argtypes = [C.c_void_p, C.c_int32]
     if hasattr(lib, "mrca_set_debug_flags"):      # profiling build only
         lib.mrca_set_debug_flags.argtypes = [C.c_void_p, C.c_int32]

@@ -9,6 +9,7 @@ successful robots and their mean path length ratio vs the 50 m straight line.
 import argparse
 import json
 import math
+import sys
 
 import torch
 
@@ -84,12 +85,14 @@ def perturbed_start(env, jitter_xy, jitter_th, seed):
     return poses.reshape(W * R, 3).contiguous(), goal.reshape(W * R, 2).contiguous()
 
 
-def circle_test(env, policy_fn, max_ticks=1200, perturb=None, seed=0):
+def circle_test(env, policy_fn, max_ticks=1200, perturb=None, seed=0, recorder=None):
     """Runs the circle scenario on ``env`` (any object with the VecStageWorld surface) and returns
     the metrics dict.  Mirrors circle_test.py:52-80: deterministic action, and a robot whose last
     ``get_reward_and_terminate`` said terminal gets v = 0 (``real_action[0] = 0``, :64-65).
     ``perturb = (jitter_xy, jitter_th)``: every circle starts from its own jittered poses (``perturbed_start``); the
-    metrics then carry the mean success rate over circles with a 95 % interval."""
+    metrics then carry the mean success rate over circles with a 95 % interval.
+    ``recorder``: a ``render.Recorder`` whose ``tick(k)`` is called before tick k (pictures of the run, gathered on the device;
+    it reads the env and writes nothing of it, so the metrics are the same with and without)."""
     if perturb is None:
         env.reset()
     else:
@@ -101,6 +104,8 @@ def circle_test(env, policy_fn, max_ticks=1200, perturb=None, seed=0):
     path = torch.zeros(N, device=dev)
     last_terminal = torch.zeros(N, dtype=torch.bool, device=dev)
     for k in range(max_ticks):
+        if recorder is not None:
+            recorder.tick(k)
         a = policy_fn(env.obs if getattr(policy_fn, "wants_obs", True) else None, env.local_goal, env.speed).float().clone()
         a[:, 0] = torch.where(last_terminal, torch.zeros_like(a[:, 0]), a[:, 0])
         pending = env.first_result == 0
@@ -163,6 +168,12 @@ def main():
     ap.add_argument("--fused", action="store_true", help="policy inference through the fp32 HIP conv front end")
     ap.add_argument("--fused-bf16", action="store_true", help="policy inference through the bf16 MFMA front end and a bf16 "
                                                               "fc1 (opt-in precision, not the reference's; implies --fused)")
+    ap.add_argument("--render", default=None, metavar="PATH", help="write pictures of the run (top-down views with trails, rendered on "
+                                                                    "the device and copied to the host once after the last tick): "
+                                                                    "an animated GIF, or PATH.npz where PIL is missing")
+    ap.add_argument("--render-worlds", default=None, help="the circles to show, e.g. 0,1,7 (default: the first 16)")
+    ap.add_argument("--render-every", type=int, default=10, help="one frame every K ticks")
+    ap.add_argument("--render-size", type=int, default=256, help="pixels per side of one circle's picture")
     a = ap.parse_args()
     if a.fused_bf16:
         a.fused = True
@@ -180,7 +191,15 @@ def main():
     else:
         fn, name = staggered_roundabout_policy(env.N), "staggered-roundabout stand-in (no checkpoint given)"
     perturb = tuple(float(v) for v in a.perturb.split(",")) if a.perturb else None
-    out = circle_test(env, fn, a.max_ticks, perturb=perturb, seed=a.seed)
+    recorder = None
+    if a.render:
+        from .render import Recorder, save_frames
+        worlds = [int(w) for w in a.render_worlds.split(",")] if a.render_worlds else None
+        recorder = Recorder(env, worlds, a.render_every, a.render_size)
+    out = circle_test(env, fn, a.max_ticks, perturb=perturb, seed=a.seed, recorder=recorder)
+    if recorder is not None:      # (reported on stderr: the result line is the same with and without --render)
+        frames = recorder.frames()
+        print(f"{len(frames)} frames -> {save_frames(frames, a.render)}", file=sys.stderr)
     out["policy"] = name
     out["robots_per_circle"], out["radius_m"] = a.robots, a.radius
     out["perturb_xy_th"], out["seed"], out["stage_resolution"] = perturb, a.seed, bool(a.stage_resolution)

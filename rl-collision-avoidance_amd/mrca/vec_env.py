@@ -211,6 +211,51 @@ class VecStageWorld:
                    "mrca_sparse_obs")
         return out
 
+    # ------------------------------------------------------------------ looking at worlds (mrca_render)
+    def default_view(self, size=(256, 256)):
+        """(cx, cy, m_per_px) of the view that fits the map's extent into ``size`` = (width, height) pixels -- or, for an
+        all-free map (``scenario.empty_grid``: the open world of ``circle_big``), the bounding box of the init and goal tables
+        plus 1 m on every side."""
+        g, sc = self.scenario.grid, self.scenario
+        if np.asarray(g.bits).any():
+            lo = np.array([g.x0, g.y0], np.float64)
+            hi = lo + np.array([g.width, g.height], np.float64) * g.cell
+        else:
+            pts = np.concatenate([np.asarray(sc.init_table)[:, :2], np.asarray(sc.goal_table)[:, :2]])
+            lo, hi = pts.min(0) - 1.0, pts.max(0) + 1.0
+        ext = hi - lo
+        return float(0.5 * (lo[0] + hi[0])), float(0.5 * (lo[1] + hi[1])), float(max(ext[0] / size[0], ext[1] / size[1]))
+
+    def render(self, worlds=None, size=(256, 256), centre=None, m_per_px=None,
+               layers=_lib.RENDER_MAP | _lib.RENDER_GOALS | _lib.RENDER_BODIES, trail=None, out=None):
+        """Top-down pictures of ``worlds`` (default: all, at most 256 per call) as a uint8[V,H,W,3] tensor on the env's device,
+        rendered from the env's fields as they stand on the current stream: nothing synchronises, nothing of the env is
+        written.  ``size`` = (width, height); ``centre`` = (cx, cy) or [V,2] and ``m_per_px`` = a number or [V] default to
+        ``default_view``; ``layers``: bits of ``_lib.RENDER_*``; ``trail``: an int32[V,H,W] tensor of the caller's that
+        collects where robots have been (zero it to start over); ``out``: the picture's tensor to reuse.  The ID image of the
+        call (layer << 24 | local robot index per pixel, int32[V,H,W]) stays in ``self.render_ids``."""
+        worlds = list(range(self.W)) if worlds is None else [int(w) for w in worlds]
+        V, (Wp, Hp) = len(worlds), (int(size[0]), int(size[1]))
+        if not (0 < V <= 256 and 0 < Wp <= 4096 and 0 < Hp <= 4096):       # (mrca_render's own limits, before anything is allocated)
+            raise ValueError(f"render: {V} views of {Wp} x {Hp} pixels; a call takes 1..256 views of 1..4096 pixels a side")
+        dcx, dcy, dm = self.default_view((Wp, Hp))
+        cen = np.broadcast_to(np.asarray((dcx, dcy) if centre is None else centre, np.float64), (V, 2))
+        mpp = np.broadcast_to(np.asarray(dm if m_per_px is None else m_per_px, np.float64), (V,))
+        views = (_lib.RenderView * V)(*[_lib.RenderView(w, cen[v, 0], cen[v, 1], mpp[v]) for v, w in enumerate(worlds)])
+        ids = getattr(self, "render_ids", None)
+        if ids is None or tuple(ids.shape) != (V, Hp, Wp):
+            ids = self.render_ids = torch.empty((V, Hp, Wp), dtype=torch.int32, device=self.device)
+        if trail is not None and not (trail.is_cuda and trail.dtype == torch.int32 and trail.is_contiguous()
+                                      and tuple(trail.shape) == (V, Hp, Wp)):
+            raise ValueError(f"render: trail must be a contiguous cuda int32 tensor of shape {(V, Hp, Wp)}")
+        if out is None:
+            out = torch.empty((V, Hp, Wp, 3), dtype=torch.uint8, device=self.device)
+        elif not (out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and tuple(out.shape) == (V, Hp, Wp, 3)):
+            raise ValueError(f"render: out must be a contiguous cuda uint8 tensor of shape {(V, Hp, Wp, 3)}")
+        _lib.check(self.lib.mrca_render(self._h, views, V, Wp, Hp, int(layers), ids.data_ptr(),
+                                        None if trail is None else trail.data_ptr(), out.data_ptr(), self._stream()), "mrca_render")
+        return out
+
     # ------------------------------------------------------------------ lifecycle
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
