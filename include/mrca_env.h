@@ -281,6 +281,39 @@ int mrca_render(mrca_env* env, const mrca_render_view* views /* host */, int32_t
                 uint32_t layers, uint32_t* ids_dev /* [V,H,W] */, uint32_t* trail_dev /* [V,H,W] or NULL */,
                 uint8_t* rgb_dev /* [V,H,W,3] or NULL */, void* stream);
 
+/* A classical baseline controller on the device: ORCA (van den Berg, Guy, Lin, Manocha, "Reciprocal n-body collision
+ * avoidance") for every robot of the env, from the env's own fields.  It stands in for the NH-ORCA baseline of Long et al. 2018,
+ * Sec. V, which the reference does not ship: every success rate of a learned policy can be put next to it, and with `mask_dev`
+ * it drives some robots of a world while a policy drives the others (the paper's mixed and non-cooperative scenarios).
+ * Per robot: poses, headings and MRCA_F_SPEED_GT of its world's robots give one half plane of permitted velocities per kept
+ * neighbour (the max_neighbors nearest within neighbor_dist, crashed and finished ones included: they are still obstacles), the
+ * newest row of MRCA_F_SCAN_RING one per sixteenth of the scan (its nearest return below obst_dist whose MRCA_F_HIT_BITS bit is
+ * clear, as a static point); the velocity closest to the preferred one (v_pref towards MRCA_F_GOAL, zero within 0.5 m of it,
+ * turned by a fixed per-robot angle of at most `jitter` rad) that satisfies them is mapped to a forward-only (v, omega) in
+ * [0, max_speed] x [-1, 1].  The rule is csrc/mrca_orca_device.h, separately rounded fp32 steps in a fixed order: the output
+ * is reproducible bit for bit (tests/orca_ref.py restates it in NumPy).
+ *   params      host; NULL = mrca_orca_default_params: radius 0.35 (the footprint's half diagonal 0.2907 + a margin),
+ *               neighbor_dist 6, max_neighbors 10, time_horizon 2, time_horizon_obst 1.5, obst_dist 3, v_pref 1, max_speed 1,
+ *               responsibility 0.5, k_omega 6, jitter 0 (time_horizon and k_omega tuned on three closed-loop scenarios,
+ *               profiles/orca/defaults.txt)
+ *   mask_dev    u8[N] or NULL = all robots
+ *   actions_dev f32[N,2] out, 8-byte aligned; rows whose mask byte is 0 are not touched
+ *   vel_dev     f32[N,2] or NULL; out: the holonomic velocity chosen (same rows)
+ * Asynchronous on `stream`, ONE launch (the params travel as kernel arguments); reads the env as it stands at that point of the
+ * stream and writes none of it, so mrca_step with actions_dev can follow on the same stream.  Both lazy_obs values, any beams /
+ * frames, exact and raster collision modes.  robots_per_world 1..64: more gives MRCA_ERR_UNSUPPORTED (a world's robots are the
+ * lanes of one wavefront).  Everything is validated before the first HIP call (MRCA_ERR_INVALID): every float finite; radius,
+ * neighbor_dist, time_horizon, time_horizon_obst, max_speed > 0; 0 <= obst_dist <= 6; 0 <= responsibility <= 1; max_neighbors
+ * 0..48; actions_dev not NULL and 8-byte aligned. */
+typedef struct mrca_orca_params {
+    float radius, neighbor_dist, time_horizon, time_horizon_obst, obst_dist, v_pref, max_speed, responsibility, k_omega, jitter;
+    int32_t max_neighbors; /* 0..48 */
+} mrca_orca_params;
+int mrca_orca_default_params(mrca_orca_params* out);
+int mrca_orca_actions(mrca_env* env, const mrca_orca_params* params /* host, NULL = defaults */,
+                      const uint8_t* mask_dev /* u8[N] or NULL = all */, float* actions_dev /* f32[N,2] */,
+                      float* vel_dev /* f32[N,2] or NULL */, void* stream);
+
 /* Synchronises `stream` and reports (then clears) the env's sticky device-side status word: MRCA_OK, or MRCA_ERR_HIP with
  * mrca_last_error() saying what went wrong on the device since the last check.  Today one condition: the ordered
  * collision pass of a world with more than 64 robots ran out of its (very long) bounded wait and left a robot

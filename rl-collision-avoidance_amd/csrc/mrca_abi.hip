@@ -21,6 +21,7 @@
 #include "mrca_host.h"
 #include "mrca_hostutil.h"
 #include "mrca_kernels.h"
+#include "mrca_orca.h"
 #include "mrca_render.h"
 #include "mrca_rollout_store.h"
 
@@ -755,6 +756,61 @@ int mrca_render(mrca_env* env, const mrca_render_view* views, int32_t num_views,
     DeviceGuard guard(env->cfg.device);
     mrca::launch_render(env->view, reinterpret_cast<const mrca::RenderView*>(views), num_views, width, height, layers, ids_dev,
                         trail_dev, rgb_dev, static_cast<hipStream_t>(stream));
+    HIP_TRY(hipGetLastError());
+    return MRCA_OK;
+}
+
+static_assert(sizeof(mrca_orca_params) == sizeof(mrca::OrcaParams) && offsetof(mrca_orca_params, max_neighbors) == offsetof(mrca::OrcaParams, max_neighbors),
+              "mrca_orca_params and mrca::OrcaParams are one layout");
+
+int mrca_orca_default_params(mrca_orca_params* out) {
+    if (!out) return fail(MRCA_ERR_INVALID, "mrca_orca_default_params: out is NULL");
+    out->radius = 0.35f;            // the footprint's half diagonal 0.2907 m + a margin
+    out->neighbor_dist = 6.0f;
+    out->time_horizon = 2.0f;       // (time_horizon, k_omega): tuned on the three closed-loop gates, profiles/orca/defaults.txt
+    out->time_horizon_obst = 1.5f;
+    out->obst_dist = 3.0f;
+    out->v_pref = 1.0f;
+    out->max_speed = 1.0f;
+    out->responsibility = 0.5f;
+    out->k_omega = 6.0f;
+    out->jitter = 0.0f;
+    out->max_neighbors = 10;
+    return MRCA_OK;
+}
+
+int mrca_orca_actions(mrca_env* env, const mrca_orca_params* params, const uint8_t* mask_dev, float* actions_dev, float* vel_dev,
+                      void* stream) {
+    mrca_orca_params p;
+    if (params) p = *params;
+    else mrca_orca_default_params(&p);
+    const float fl[10] = {p.radius, p.neighbor_dist, p.time_horizon, p.time_horizon_obst, p.obst_dist, p.v_pref, p.max_speed,
+                          p.responsibility, p.k_omega, p.jitter};
+    static const char* const names[10] = {"radius", "neighbor_dist", "time_horizon", "time_horizon_obst", "obst_dist", "v_pref",
+                                          "max_speed", "responsibility", "k_omega", "jitter"};
+    for (int i = 0; i < 10; ++i)
+        if (!std::isfinite(fl[i])) return fail(MRCA_ERR_INVALID, "mrca_orca_actions: %s is not finite", names[i]);
+    if (!(p.radius > 0.0f)) return fail(MRCA_ERR_INVALID, "mrca_orca_actions: radius must be > 0");
+    if (!(p.neighbor_dist > 0.0f)) return fail(MRCA_ERR_INVALID, "mrca_orca_actions: neighbor_dist must be > 0");
+    if (!(p.time_horizon > 0.0f)) return fail(MRCA_ERR_INVALID, "mrca_orca_actions: time_horizon must be > 0");
+    if (!(p.time_horizon_obst > 0.0f)) return fail(MRCA_ERR_INVALID, "mrca_orca_actions: time_horizon_obst must be > 0");
+    if (!(p.max_speed > 0.0f)) return fail(MRCA_ERR_INVALID, "mrca_orca_actions: max_speed must be > 0");
+    if (!(p.obst_dist >= 0.0f && p.obst_dist <= 6.0f)) return fail(MRCA_ERR_INVALID, "mrca_orca_actions: obst_dist outside [0, 6]");
+    if (!(p.responsibility >= 0.0f && p.responsibility <= 1.0f))
+        return fail(MRCA_ERR_INVALID, "mrca_orca_actions: responsibility outside [0, 1]");
+    if (p.max_neighbors < 0 || p.max_neighbors > mrca::kOrcaMaxNeighbors)
+        return fail(MRCA_ERR_INVALID, "mrca_orca_actions: max_neighbors %d outside 0..%d", p.max_neighbors, mrca::kOrcaMaxNeighbors);
+    if (!actions_dev) return fail(MRCA_ERR_INVALID, "mrca_orca_actions: actions_dev is NULL");
+    if (reinterpret_cast<uintptr_t>(actions_dev) % 8) return fail(MRCA_ERR_INVALID, "mrca_orca_actions: actions_dev must be 8-byte aligned");
+    if (reinterpret_cast<uintptr_t>(vel_dev) % 4) return fail(MRCA_ERR_INVALID, "mrca_orca_actions: vel_dev must be 4-byte aligned");
+    if (!env) return fail(MRCA_ERR_INVALID, "env is NULL");
+    if (env->cfg.robots_per_world > mrca::kOrcaMaxRobots)
+        return fail(MRCA_ERR_UNSUPPORTED, "mrca_orca_actions: robots_per_world %d > %d", env->cfg.robots_per_world, mrca::kOrcaMaxRobots);
+    DeviceGuard guard(env->cfg.device);
+    mrca::OrcaParams q;
+    static_assert(std::is_trivially_copyable<mrca::OrcaParams>::value, "");
+    memcpy(&q, &p, sizeof q);
+    mrca::launch_orca(env->view, q, mask_dev, actions_dev, vel_dev, static_cast<hipStream_t>(stream));
     HIP_TRY(hipGetLastError());
     return MRCA_OK;
 }

@@ -31,7 +31,7 @@ EXPORTS = ["mrca_abi_version", "mrca_last_error", "mrca_arena_bytes", "mrca_crea
            "mrca_rollout_store_state", "mrca_rollout_store_outcome",
            "mrca_policy_heads", "mrca_policy_heads_backward_scratch", "mrca_policy_heads_backward", "mrca_relu_cat",
            "mrca_relu_cat_backward", "mrca_policy_heads_backward_bias", "mrca_relu_cat_backward_bias_scratch",
-           "mrca_relu_cat_backward_bias", "mrca_render"]
+           "mrca_relu_cat_backward_bias", "mrca_render", "mrca_orca_default_params", "mrca_orca_actions"]
 # declared in include/mrca_env.h like the names above, listed apart: tests/test_abi.py's header scan reads names of letters
 # and underscores only (tests/test_policy_bf16_host.py checks these against the header and the library)
 EXPORTS_WITH_DIGITS = ["mrca_lidar_features_bf16", "mrca_lidar_features_bf16_rows", "mrca_lidar_features_bf16_backward",
@@ -47,6 +47,12 @@ class RolloutRows(C.Structure):
 class RenderView(C.Structure):
     """include/mrca_env.h: mrca_render_view"""
     _fields_ = [("world", C.c_int32), ("cx", C.c_float), ("cy", C.c_float), ("m_per_px", C.c_float)]
+
+
+class OrcaParamsStruct(C.Structure):
+    """include/mrca_env.h: mrca_orca_params"""
+    _fields_ = [(k, C.c_float) for k in ("radius", "neighbor_dist", "time_horizon", "time_horizon_obst", "obst_dist", "v_pref",
+                                         "max_speed", "responsibility", "k_omega", "jitter")] + [("max_neighbors", C.c_int32)]
 
 
 class MrcaConfig(C.Structure):
@@ -141,6 +147,8 @@ def load(path=None):
     lib.mrca_adam_step.argtypes = [C.c_void_p] * 4 + [C.c_int64] + [C.c_double] * 4 + [C.c_int32, C.c_void_p]
     lib.mrca_render.argtypes = [C.c_void_p, C.POINTER(RenderView), C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p,
                                 C.c_void_p, C.c_void_p]
+    lib.mrca_orca_default_params.argtypes = [C.POINTER(OrcaParamsStruct)]
+    lib.mrca_orca_actions.argtypes = [C.c_void_p, C.POINTER(OrcaParamsStruct), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.mrca_enable_timing.argtypes = [C.c_void_p, C.c_int32]
     if hasattr(lib, "mrca_set_debug_flags"):      # profiling build only
         lib.mrca_set_debug_flags.argtypes = [C.c_void_p, C.c_int32]

@@ -65,6 +65,25 @@ def cnn_policy_fn(policy, fused=False, env=None, fused_bf16=False):
     return fn
 
 
+def orca_policy_fn(env, params=None, first=None, other=None):
+    """The ORCA baseline controller on the device (``VecStageWorld.orca_actions``): it reads the env's own fields, so it wants
+    no observation stack.  ``first = K`` with ``other``: robots with local index < K are driven by ORCA (through the mask),
+    the rest by the policy function ``other`` -- the paper's mixed scenarios."""
+    if first is None:
+        def fn(obs, local_goal, speed):
+            return env.orca_actions(params)
+        fn.wants_obs = False
+        return fn
+    mask = (torch.arange(env.N, device=env.device) % env.R < int(first)).to(torch.uint8).contiguous()
+
+    def mixed(obs, local_goal, speed):
+        a = other(obs, local_goal, speed).float().contiguous().clone()
+        return env.orca_actions(params, mask=mask, out=a)
+    mixed.wants_obs = getattr(other, "wants_obs", True)
+    mixed.groups = {"orca": mask.bool(), "policy": ~mask.bool()}
+    return mixed
+
+
 def perturbed_start(env, jitter_xy, jitter_th, seed):
     """Start poses of a circle world with every robot moved off its table pose by U(-jitter_xy, jitter_xy) metres in x
     and y and U(-jitter_th, jitter_th) radians of heading -- drawn from a Philox generator seeded with ``seed``, so that
@@ -137,8 +156,21 @@ def circle_test(env, policy_fn, max_ticks=1200, perturb=None, seed=0, recorder=N
         half = 1.96 * sd / math.sqrt(N // R)
         per_circle = {"circles": N // R, "success_rate_ci95": [max(0.0, float(sr.mean()) - half), min(1.0, float(sr.mean()) + half)],
                       "circles_fully_solved": float((sr == 1.0).float().mean()), "worst_circle": float(sr.min())}
+    by_group = {}
+    for name, sel in (getattr(policy_fn, "groups", None) or {}).items():      # (a mixed run: the same metrics per group)
+        g_reach = reach & sel
+        g_n = int(g_reach.sum())
+        by_group[name] = {
+            "robots": int(sel.sum()), "success_rate": g_n / max(1, int(sel.sum())),
+            "crash_rate": float((fr[sel] == 2).float().mean()), "timeout_rate": float((fr[sel] == 3).float().mean()),
+            "unfinished_rate": float((fr[sel] == 0).float().mean()),
+            "extra_time_s": float((time_s - straight / 1.0)[g_reach].mean()) if g_n else None,
+            "extra_distance_m": float((path - straight)[g_reach].mean()) if g_n else None,
+            "average_speed_mps": float((path / time_s.clamp(min=0.1))[g_reach].mean()) if g_n else None,
+        }
     return {
         **per_circle,
+        **({"groups": by_group} if by_group else {}),
         "robots": N, "ticks_run": k + 1,
         "success_rate": n_reach / N,
         "crash_rate": float((fr == 2).float().mean()),
@@ -168,6 +200,13 @@ def main():
     ap.add_argument("--fused", action="store_true", help="policy inference through the fp32 HIP conv front end")
     ap.add_argument("--fused-bf16", action="store_true", help="policy inference through the bf16 MFMA front end and a bf16 "
                                                               "fc1 (opt-in precision, not the reference's; implies --fused)")
+    ap.add_argument("--orca", action="store_true", help="every robot driven by the ORCA baseline controller on the device "
+                                                        "(mrca_orca_actions); no --policy is needed")
+    ap.add_argument("--orca-param", action="append", default=[], metavar="NAME=VALUE",
+                    help="a field of mrca_orca_params, e.g. radius=0.4 (repeatable)")
+    ap.add_argument("--orca-first", type=int, default=None, metavar="K",
+                    help="robots with local index < K are driven by ORCA, the rest by --policy (or the stand-in); the metrics "
+                         "are reported for both groups")
     ap.add_argument("--render", default=None, metavar="PATH", help="write pictures of the run (top-down views with trails, rendered on "
                                                                     "the device and copied to the host once after the last tick): "
                                                                     "an animated GIF, or PATH.npz where PIL is missing")
@@ -190,6 +229,13 @@ def main():
         fn, name = cnn_policy_fn(pol, fused=a.fused, env=env, fused_bf16=a.fused_bf16), a.policy
     else:
         fn, name = staggered_roundabout_policy(env.N), "staggered-roundabout stand-in (no checkpoint given)"
+    if a.orca or a.orca_first is not None:
+        from .orca import OrcaParams
+        params = OrcaParams.from_assignments(a.orca_param)
+        if a.orca_first is None:
+            fn, name = orca_policy_fn(env, params), "ORCA baseline (mrca_orca_actions)"
+        else:
+            fn, name = orca_policy_fn(env, params, first=a.orca_first, other=fn), f"ORCA for local index < {a.orca_first}, else {name}"
     perturb = tuple(float(v) for v in a.perturb.split(",")) if a.perturb else None
     recorder = None
     if a.render:
@@ -201,6 +247,9 @@ def main():
         frames = recorder.frames()
         print(f"{len(frames)} frames -> {save_frames(frames, a.render)}", file=sys.stderr)
     out["policy"] = name
+    if a.orca or a.orca_first is not None:
+        import dataclasses
+        out["orca_params"] = dataclasses.asdict(params)
     out["robots_per_circle"], out["radius_m"] = a.robots, a.radius
     out["perturb_xy_th"], out["seed"], out["stage_resolution"] = perturb, a.seed, bool(a.stage_resolution)
     out["inference_precision"] = ("bf16 (fused bf16 MFMA front end + bf16 fc1)" if a.fused_bf16 else "fp32") if a.policy else None

@@ -256,6 +256,21 @@ class VecStageWorld:
                                         None if trail is None else trail.data_ptr(), out.data_ptr(), self._stream()), "mrca_render")
         return out
 
+    def orca_actions(self, params=None, mask=None, out=None, vel=None):
+        """(v, omega) of the ORCA baseline controller (mrca_orca_actions) for every robot, as a float32[N,2] tensor on the env's
+        device, from the env's fields as they stand on the current stream: one launch, nothing synchronises, nothing of the
+        env is written -- ``env.step(env.orca_actions())`` is a closed-loop scripted tick.  ``params``: an ``orca.OrcaParams``
+        (default: the library's); ``mask``: a uint8[N] tensor, rows with 0 keep what ``out`` holds (so a policy's actions can
+        be passed as ``out`` and ORCA overwrites its robots' rows); ``vel``: a float32[N,2] tensor that takes the holonomic
+        velocity chosen."""
+        if out is None:
+            out = torch.zeros((self.N, 2), dtype=torch.float32, device=self.device)
+        st = None if params is None else params.struct()
+        _lib.check(self.lib.mrca_orca_actions(self._h, None if st is None else C.byref(st), self._ptr(mask, torch.uint8, self.N),
+                                              self._ptr(out, torch.float32, 2 * self.N), self._ptr(vel, torch.float32, 2 * self.N),
+                                              self._stream()), "mrca_orca_actions")
+        return out
+
     # ------------------------------------------------------------------ lifecycle
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
