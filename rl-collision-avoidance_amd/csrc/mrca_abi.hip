@@ -22,6 +22,7 @@
 #include "mrca_hostutil.h"
 #include "mrca_kernels.h"
 #include "mrca_orca.h"
+#include "mrca_pass_plan.h"
 #include "mrca_render.h"
 #include "mrca_rollout_store.h"
 
@@ -42,6 +43,7 @@ int set_error(int code, const char* fmt, ...) {
 namespace {
 
 using mrca::DeviceGuard;
+using mrca::kAheadTicks;
 #define fail(...) mrca::set_error(__VA_ARGS__)
 
 // log2 of the beams a marching thread of the ray cast owns (EnvView::ray_shift): 2 per thread, 4 in worlds of more than 64
@@ -311,9 +313,7 @@ struct mrca_env {
     Event fork;                           // an early exit's join of the move stream
 };
 
-constexpr int kAheadTicks = 256;            // most ticks one run-ahead pass covers (a pass ends with every stream joined: ~90 us)
 constexpr size_t kAheadMaxBytes = 256u << 20;
-constexpr int kRayTicksGroups = 3 * 2048;   // most workgroups of a ray-cast launch of several ticks: three residency rounds (run_ahead_pass)
 // World range 1 gets its stream in mrca_create (chains <= 2, bench.py's default, may be captured at once); further ranges get
 // theirs at their first use -- an env does not park streams it may never use (the runtime maps a process's streams onto a
 // few hardware queues, DESIGN.md 5.10 "what the schedule depends on").
@@ -331,6 +331,44 @@ static mrca::EnvView slot_view(const mrca_env* env, int b) {
         v.fresh = reinterpret_cast<uint8_t*>(base + r.off[3]);
         if (env->view.outline) v.outline = reinterpret_cast<mrca::OutlineBits*>(base + r.off[4]);
     }
+    return v;
+}
+
+// the ring heads' array: the env's field, or the scratch array a ray cast of several ticks alternates it with
+static uint8_t* ring_heads(const mrca_env* env, int in_scratch) {
+    return in_scratch ? env->ahead.head_scratch.get() : env->view.ring_head;
+}
+
+// the ray cast of `ticks` >= 2 ticks in one launch: its first tick reads slot b >= 1, the ticks behind it slots b - 1, b - 2 ...,
+// and slot 0, the env's own fields, can only be the last one's (last_is_env); the ring heads go from head_in to head_out
+static mrca::RayTicks slot_ticks(const mrca_env* env, int b, int ticks, bool last_is_env, const uint8_t* head_in, uint8_t* head_out) {
+    const AheadRing& r = env->ahead;
+    mrca::RayTicks t{};
+    t.ticks = ticks;
+    t.last_is_env = last_is_env;
+    t.slot0 = r.mem.get() + (size_t)(b - 1) * r.slot_bytes + r.off[0];
+    t.stride = -(int32_t)r.slot_bytes;
+    t.off_head = (uint32_t)(r.off[1] - r.off[0]);
+    t.in.off_goal = (uint32_t)(r.off[2] - r.off[0]);
+    t.in.off_fresh = (uint32_t)(r.off[3] - r.off[0]);
+    t.in.off_outline = (uint32_t)(r.off[4] - r.off[0]);
+    t.in.head_in = head_in;
+    t.in.head_out = head_out;
+    return t;
+}
+
+// `v` for a part of the env: the robots whose lidar outputs (scan, frame stack, local goal) a ray cast produces and the worlds a
+// move launch advances
+static mrca::EnvView range_view(mrca::EnvView v, int32_t first, int32_t count, int32_t world_first, int32_t world_count) {
+    v.ray_first = first;
+    v.ray_count = count;
+    v.world_first = world_first;
+    v.world_count = world_count;
+    return v;
+}
+// `v` for a ray cast (lazy_obs = 0: it forms MRCA_F_SCAN / MRCA_F_OBS of its robots itself -- no materialize launch behind it)
+static mrca::EnvView observing(const mrca_env* env, mrca::EnvView v) {
+    v.eager_views = env->cfg.lazy_obs ? 0 : (MRCA_VIEW_SCAN | MRCA_VIEW_OBS);
     return v;
 }
 
@@ -623,7 +661,7 @@ static void init_step_many(mrca_env* env) {
     }
     // ticks per ray-cast launch: as many as the scan ring has frames (every tick of a launch that is not a restart writes a
     // slot of its own: each tick's row is stored), at most the 8 the kernel's tick index has flags for -- where that was
-    // measured to pay (run_ahead_pass).  MRCA_TICKS_PER_LAUNCH, read once here, sets the number for every pass whatever its
+    // measured to pay (mrca::ticks_per_launch).  MRCA_TICKS_PER_LAUNCH, read once here, sets the number for every pass whatever its
     // shape, for A/B runs on one box: 1 is a launch per tick, the schedule before there were such launches
     int ticks = env->view.F < 8 ? env->view.F : 8;
     if (const char* v = std::getenv("MRCA_TICKS_PER_LAUNCH")) {
@@ -827,20 +865,15 @@ static int step_impl(mrca_env* env, const float* actions_dev, int32_t first, int
     hipStream_t s = static_cast<hipStream_t>(stream);
     const bool rec = phases == (kPhaseMove | kPhaseObserve) && env->timing > 0 && (env->step_count++ % env->timing) == 0 &&
                      env->ev_used + 4 <= (int)env->ev.size();
-    mrca::EnvView v = env->view;
-    v.ray_first = first;      // the robots whose lidar outputs (scan, frame stack, local goal) this call produces
-    v.ray_count = count;
-    v.world_first = world_first;   // the worlds the move launch advances (mrca_step_worlds; otherwise all of them)
-    v.world_count = world_count;
+    // (the worlds: mrca_step_worlds' range, otherwise all of them)
+    const mrca::EnvView v = range_view(env->view, first, count, world_first, world_count);
     env->last_ray_count = count;
     // timing: the launches' own begin / end stamps (hipExtLaunchKernel), not event records around them
     const Event* ev = rec ? &env->ev[env->ev_used] : nullptr;
     if (phases & kPhaseMove) mrca::launch_move(v, actions_dev, s, rec ? ev[0].get() : nullptr, rec ? ev[1].get() : nullptr);
     if (phases & kPhaseObserve) {
         mrca::launch_lidar_grid(v, /*counted=*/1, s);
-        // (lazy_obs = 0: the ray cast forms MRCA_F_SCAN / MRCA_F_OBS of its robots itself -- no materialize launch behind it)
-        v.eager_views = env->cfg.lazy_obs ? 0 : (MRCA_VIEW_SCAN | MRCA_VIEW_OBS);
-        mrca::launch_raycast(v, /*only_fresh=*/0, s, rec ? ev[2].get() : nullptr, rec ? ev[3].get() : nullptr);
+        mrca::launch_raycast(observing(env, v), /*only_fresh=*/0, s, rec ? ev[2].get() : nullptr, rec ? ev[3].get() : nullptr);
     }
     if (rec) env->ev_used += 4;
     HIP_TRY(hipGetLastError());
@@ -1039,135 +1072,71 @@ static void log_end() {
 #endif
 
 
-// One run-ahead pass of mrca_step_many: K <= ahead.slots + 1 ticks.  Tick k's move launch covers ALL worlds and writes slot
-// w(k) = K - 1 - k (slot 0 = the env's own fields: the pass starts from them and its last tick leaves them current), reading
-// slot w(k - 1); tick 0 goes out on the caller's stream, ticks 1 .. K - 1 on the env's move stream, back to back -- a slot per
-// tick, so a move launch waits for no ray cast.  The ray casts of world range c run on the range's stream (range 0: the
-// caller's), tick after tick, each BLOCK of ticks behind the event "the block's last move launch is through" (the blocks and the
-// host order of the enqueues: below).  Nothing else is ordered: the ray casts are what a tick costs (16.4 us for 4096 robots as
-// two ranges -- two residency rounds of a workgroup's lifetime), the move launches (8.5 us) run beside them.
-// Every dependency is a stream order or an event; nothing spins.
-static int run_ahead_pass(mrca_env* env, const float* const* act, int K, int P, hipStream_t s0) {
-    const int W = env->view.W, R = env->view.R;
-    hipStream_t const ms = env->ahead.move_stream.get();
-    hipError_t herr = hipSuccess;
+// mrca_step_many's action pool: tick k of the call takes the actions at (first_tick + k) modulo the pool's size
+struct ActionPool {
+    const float* const* dev;
+    int32_t count, first_tick;
+    const float* operator()(int k) const { return dev[(size_t)((int64_t)first_tick + k) % (size_t)count]; }
+};
+
+// One run-ahead pass of mrca_step_many: ticks k0 .. k0 + K - 1 of the call, K <= ahead.slots + 1.  What goes out, and in which
+// order, is the pass's plan (mrca_pass_plan.h); this is how.  Tick k's move launch covers ALL worlds, writing its slot and
+// reading the tick before's; the first kOwnTicks go out on the caller's stream, the others on the env's move stream, back to
+// back -- a slot per tick, so a move launch waits for no ray cast.  The ray casts of world range c run on the range's stream
+// (range 0: the caller's), tick after tick, each BLOCK of ticks behind the event "the block's last move launch is through".
+// Nothing else is ordered: the ray casts are what a tick costs (16.4 us for 4096 robots as two ranges -- two residency rounds
+// of a workgroup's lifetime), the move launches (8.5 us) run beside them.  Every dependency is a stream order
+// or an event; nothing spins.
+struct AheadPass {
+    mrca_env* env;
+    ActionPool act;
+    int k0, P;
+    hipStream_t s0, ms;                // the caller's stream, the move stream
+    mrca::PassPlan plan;
+    hipError_t herr = hipSuccess;      // the first error: nothing is enqueued behind it
     bool move_forked = false;
-    MRCA_LOG_BEGIN();
-    // Ticks are enqueued in BLOCKS -- [0], [1], [2], [3], then fours; with T = ticks per ray-cast launch > 1: [0], [1], two,
-    // four times T (T = 2: once), then 2 T each: at no length of a pass more waits than with a launch per tick, and small blocks
-    // while the move launches are not far ahead yet -- a block's ray casts wait for its LAST move launch, and next to launches of
-    // several residency rounds a move launch takes up to 20 us (launch stamps, profiles/multitick/) --: a block's move launches,
-    // ONE event behind the last of them, and every range's stream waits for that event once before it takes the block's ray
-    // casts.  hipStreamWaitEvent is the dearest call here (4.6 us of host time against ~3 for a launch: a build with host timers,
-    // profiles/r06_ai_*): a wait per tick and range made the host 15.8 us per tick against the device's 19.1 -- any hiccup
-    // starved the queues.
-    // The HOST ORDER matters as much: the host needs ~13 us per tick, the device ~16.5, so the device is never far behind the
-    // host and what is enqueued late starts late.  The move launches of block b + 3 are therefore enqueued BEFORE the ray casts
-    // of block b: they have a queue of their own, under load they come ~13 us apart (not 8.5: the launch stamps of the
-    // profiling build, MRCA_LAUNCH_STAMPS), and a ray cast waits 10 us beyond the end of the move launch it depends on.
-    // Measured (own ticks on the caller's stream x blocks of lead, profiles/r06_ai_*): lead 1 (round 6's first form) 463 us
-    // per 20-tick region, lead 2 - 4 with one or two own ticks 436 - 445; tick 0 alone on the caller's stream and lead 3 kept.
-    // Ticks per ray-cast launch.  lazy_obs = 0: the VIEWS epilogue reads the rows earlier ticks stored -- a launch per tick.
-    // Otherwise several, where a range's launch then stays within kRayTicksGroups workgroups and the mode is the exact-rectangle
-    // one: that is where it was measured to pay (Stage-1, 2 x 2048 robots: +5 %).  Next to launches of more residency rounds
-    // the move launches no longer find free CUs between two ray casts and fall behind the ray casts they feed: ranges of 4114
-    // robots (the Stage-2 side figure) lost 2 - 5 % at two ticks per launch, fidelity mode -- whose move launch is the
-    // longer one -- 22 - 27 % with move launches of up to 70 us (profiles/multitick/).
-    int Tm = 1;
-    if (env->cfg.lazy_obs) {
-        Tm = env->ahead.ticks_per_launch;
-        if (!env->ahead.ticks_forced) {
-            const int most = (W + P - 1) / P * R;             // robots of the largest range
-            if (Tm > kRayTicksGroups / most) Tm = kRayTicksGroups / most;
-            if (Tm < 1 || env->view.raster_inv > 0.0f) Tm = 1;
-        }
-    }
-    int first_of[kAheadTicks + 2];
-    int nb = 0;
-    for (int a = 0; a < K; ++nb) {
-        first_of[nb] = a;
-        a += Tm == 1 ? (a < 4 ? 1 : 4) : (nb < 2 ? 1 : nb == 2 ? 2 : nb < (Tm > 2 ? 7 : 4) ? Tm : 2 * Tm);
-    }
-    first_of[nb] = K;
-    // A block's ray casts of one range: launches of up to Tm ticks each, the same cut for every range.  A launch of several
-    // ticks moves the ring heads from one of the two arrays to the other (a launch of one tick, the single-tick kernel, leaves
-    // them where it finds them), and the pass must leave them in the env's field: an odd number of such launches is made
-    // even by sending the first of them tick by tick.
-    int launch_of[kAheadTicks + 2];              // first tick of every ray-cast launch of a range, block after block
-    int nl = 0, several = 0;
-    for (int b = 0; b < nb; ++b)
-        for (int k = first_of[b]; k < first_of[b + 1]; k += Tm) {
-            launch_of[nl++] = k;
-            several += (first_of[b + 1] - k < Tm ? first_of[b + 1] - k : Tm) > 1 ? 1 : 0;
-        }
-    launch_of[nl] = K;
-    if (several & 1) {
-        int i = 0;
-        while (launch_of[i + 1] - launch_of[i] < 2) ++i;
-        const int n = launch_of[i + 1] - launch_of[i];
-        for (int q = nl; q > i; --q) launch_of[q + n - 1] = launch_of[q];
-        for (int q = 1; q < n; ++q) launch_of[i + q] = launch_of[i] + q;
-        nl += n - 1;
-    }
-    std::vector<uint8_t> heads_in_scratch((size_t)P, 0);     // per range: where its ring heads are at this point of its stream
-    int li = 0;                                              // the next launch of launch_of (rays_of takes the blocks in order)
-    constexpr int own = 1;                       // ticks below this one: move launches on the caller's stream
-    auto moves_of = [&](int b) {
-        const int a = first_of[b], e = first_of[b + 1];
-        hipStream_t sm = a < own ? s0 : ms;
-        if (a >= own && !move_forked) {       // the move stream starts behind the caller's last move launch (and so behind the caller's work)
+    // every range has the ray casts of blocks below ray_blocks, ranges below ray_ranges those of block ray_blocks as well
+    int ray_blocks = 0, ray_ranges = 0;
+
+    void moves_of(int b) {
+        const int a = plan.first_of[b], e = plan.first_of[b + 1];
+        hipStream_t sm = a < mrca::kOwnTicks ? s0 : ms;
+        if (a >= mrca::kOwnTicks && !move_forked) {       // the move stream starts behind the caller's last move launch (and so behind the caller's work)
             herr = hipStreamWaitEvent(ms, env->ahead.moved[a - 1].get(), 0);
             if (herr != hipSuccess) return;
             move_forked = true;
         }
         for (int k = a; k < e; ++k) {
-            mrca::EnvView mv = slot_view(env, K - 1 - k);
-            const mrca::EnvView in = slot_view(env, k == 0 ? 0 : K - k);
-            mv.world_first = 0;
-            mv.world_count = W;
+            mrca::EnvView mv = slot_view(env, plan.write_slot(k));       // (all worlds, as the env's own view has it)
+            const mrca::EnvView in = slot_view(env, plan.read_slot(k));
             MRCA_LOG_TAG(mv, "move", k, 0);
-            mrca::launch_move(mv, act[k], sm, nullptr, nullptr, &in);
+            mrca::launch_move(mv, act(k0 + k), sm, nullptr, nullptr, &in);
         }
         herr = hipEventRecord(env->ahead.moved[e - 1].get(), sm);
-    };
-    auto rays_of = [&](int b) {
-        const int a = first_of[b], e = first_of[b + 1];
-        for (int c = 0; c < P && herr == hipSuccess; ++c) {
+    }
+
+    void rays_of(int b) {
+        const int W = env->view.W, R = env->view.R;
+        const int a = plan.first_of[b], e = plan.first_of[b + 1];
+        for (int c = 0; c < P; ++c) {
             hipStream_t sc = range_stream(env, s0, c);
-            if (c > 0 || a >= own) {        // (range 0's first ray casts follow their ticks' move launches on the caller's stream itself)
+            if (c > 0 || a >= mrca::kOwnTicks) {        // (range 0's first ray casts follow their ticks' move launches on the caller's stream itself)
                 herr = hipStreamWaitEvent(sc, env->ahead.moved[e - 1].get(), 0);
                 if (herr != hipSuccess) return;
             }
             const int w0 = range_first_world(W, P, c), wn = range_first_world(W, P, c + 1) - w0;
-            uint8_t* const heads[2] = {env->view.ring_head, env->ahead.head_scratch.get()};
-            for (int l = li; launch_of[l] < e; ++l) {
-                const int k = launch_of[l], n = launch_of[l + 1] - k;
-                mrca::EnvView rv = slot_view(env, n > 1 ? 0 : K - 1 - k);
-                rv.ray_first = w0 * R;
-                rv.ray_count = wn * R;
-                rv.world_first = w0;
-                rv.world_count = wn;
-                rv.eager_views = env->cfg.lazy_obs ? 0 : (MRCA_VIEW_SCAN | MRCA_VIEW_OBS);
-                rv.ring_head = heads[heads_in_scratch[(size_t)c]];
-                if (n == 1) {
+            for (int l = plan.launches_of[b]; l < plan.launches_of[b + 1]; ++l) {
+                const mrca::PassPlan::Launch& ln = plan.launch[l];
+                const int k = ln.first, slot = plan.write_slot(k);
+                mrca::EnvView rv = observing(env, range_view(slot_view(env, ln.ticks > 1 ? 0 : slot), w0 * R, wn * R, w0, wn));
+                rv.ring_head = ring_heads(env, ln.heads_in_scratch);
+                if (ln.ticks == 1) {
                     MRCA_LOG_TAG(rv, "ray", k, c);
                     mrca::launch_raycast(rv, /*only_fresh=*/0, sc);
                     continue;
                 }
-                // ticks k .. k + n - 1 read slots K - 1 - k downwards; slot 0, the env's own fields, can only be the last one's
-                const AheadRing& ring = env->ahead;
-                mrca::RayTicks t{};
-                t.ticks = n;
-                t.last_is_env = k + n == K;
-                t.slot0 = ring.mem.get() + (size_t)(K - 2 - k) * ring.slot_bytes + ring.off[0];
-                t.stride = -(int32_t)ring.slot_bytes;
-                t.off_head = (uint32_t)(ring.off[1] - ring.off[0]);
-                t.in.off_goal = (uint32_t)(ring.off[2] - ring.off[0]);
-                t.in.off_fresh = (uint32_t)(ring.off[3] - ring.off[0]);
-                t.in.off_outline = (uint32_t)(ring.off[4] - ring.off[0]);
-                t.in.head_in = rv.ring_head;
-                heads_in_scratch[(size_t)c] ^= 1;
-                t.in.head_out = heads[heads_in_scratch[(size_t)c]];
+                mrca::RayTicks t = slot_ticks(env, slot, ln.ticks, /*last_is_env=*/k + ln.ticks == plan.K, rv.ring_head,
+                                              ring_heads(env, !ln.heads_in_scratch));
                 MRCA_LOG_TAG(rv, "rays", k, c);
 #if defined(MRCA_PROFILING)
                 t.in.launch_stamps = rv.launch_stamps;
@@ -1175,31 +1144,41 @@ static int run_ahead_pass(mrca_env* env, const float* const* act, int K, int P, 
 #endif
                 mrca::launch_raycast_ticks(rv, t, sc);
             }
+            ray_ranges = c + 1;
         }
-        while (launch_of[li] < e) ++li;
-    };
-    constexpr int lead = 3;                      // how many blocks the move launches are enqueued ahead of the ray casts (>= 1)
-    for (int b = 0; b < nb && b < lead && herr == hipSuccess; ++b) moves_of(b);
-    for (int b = 0; b < nb && herr == hipSuccess; ++b) {
-        if (b + lead < nb) moves_of(b + lead);
-        if (herr == hipSuccess) rays_of(b);
+        ray_blocks = b + 1;
+        ray_ranges = 0;
     }
+
+    // where range c's ring heads are behind the launches it has been given
+    int heads_in_scratch(int c) const { return plan.launch[plan.launches_of[ray_blocks + (c < ray_ranges ? 1 : 0)]].heads_in_scratch; }
+};
+
+static int run_ahead_pass(mrca_env* env, const ActionPool& act, int k0, int K, int P, hipStream_t s0) {
+    const int W = env->view.W, R = env->view.R;
+    AheadPass pass{env, act, k0, P, s0, env->ahead.move_stream.get()};
+    MRCA_LOG_BEGIN();
+    mrca::plan_pass(K, mrca::ticks_per_launch(env->cfg.lazy_obs, env->ahead.ticks_per_launch, env->ahead.ticks_forced,
+                                              env->view.raster_inv > 0.0f, W, R, P), &pass.plan);
+    for (int i = 0; i < pass.plan.num_ops && pass.herr == hipSuccess; ++i) {
+        const mrca::PassPlan::Op& op = pass.plan.ops[i];
+        if (op.kind == mrca::PassPlan::kMoves) pass.moves_of(op.block);
+        else pass.rays_of(op.block);
+    }
+    const hipError_t herr = pass.herr;
     // an early exit may leave a range's ring heads in the scratch array: back into the env's field, behind the range's launches
     for (int c = 0; c < P; ++c)
-        if (heads_in_scratch[(size_t)c]) {
+        if (pass.heads_in_scratch(c)) {
             const int n0 = range_first_world(W, P, c) * R, n1 = range_first_world(W, P, c + 1) * R;
             (void)hipMemcpyAsync(env->view.ring_head + n0, env->ahead.head_scratch.get() + n0, (size_t)(n1 - n0),
                                  hipMemcpyDeviceToDevice, range_stream(env, s0, c));
         }
     // join: the caller's stream continues when every range is through (the move stream is: range 0 waited for its last launch)
-    hipError_t jerr = hipSuccess;
-    if (K > 0) {
-        jerr = join_ranges(env, s0, P);
-        if (move_forked && herr != hipSuccess) {     // an early exit: the move stream may still be forked off the caller's
-            hipError_t e1 = hipEventRecord(env->fork.get(), ms);
-            hipError_t e2 = hipStreamWaitEvent(s0, env->fork.get(), 0);
-            if (jerr == hipSuccess) jerr = e1 != hipSuccess ? e1 : e2;
-        }
+    hipError_t jerr = join_ranges(env, s0, P);
+    if (pass.move_forked && herr != hipSuccess) {     // an early exit: the move stream may still be forked off the caller's
+        hipError_t e1 = hipEventRecord(env->fork.get(), pass.ms);
+        hipError_t e2 = hipStreamWaitEvent(s0, env->fork.get(), 0);
+        if (jerr == hipSuccess) jerr = e1 != hipSuccess ? e1 : e2;
     }
     MRCA_LOG_END();
     if (herr != hipSuccess) return fail(MRCA_ERR_HIP, "mrca_step_many: %s", hipGetErrorString(herr));
@@ -1221,7 +1200,7 @@ int mrca_step_many(mrca_env* env, const float* const* actions_dev, int32_t num_a
     if (P < 1) P = 1;
     if (P > W) P = W;
     if (env->view.big) P = 1;
-    auto act = [&](int k) { return actions_dev[(size_t)((int64_t)first_tick + k) % (size_t)num_actions]; };
+    const ActionPool act{actions_dev, num_actions, first_tick};
     DeviceGuard guard(env->cfg.device);
     hipStream_t s0 = static_cast<hipStream_t>(stream);
     // streams and events of ranges beyond the ones mrca_create made: never inside a capture (stream creation is not capturable)
@@ -1239,11 +1218,9 @@ int mrca_step_many(mrca_env* env, const float* const* actions_dev, int32_t num_a
     if (!chained && !env->view.big && env->ahead.slots > 0) {
         // the run-ahead schedule, in passes of at most ahead.slots + 1 ticks (a pass ends with every stream joined)
         const int per = env->ahead.slots + 1 < kAheadTicks ? env->ahead.slots + 1 : kAheadTicks;
-        std::vector<const float*> a((size_t)per);
         for (int k0 = 0; k0 < num_ticks; k0 += per) {
             const int K = num_ticks - k0 < per ? num_ticks - k0 : per;
-            for (int k = 0; k < K; ++k) a[(size_t)k] = act(k0 + k);
-            if (int rc = run_ahead_pass(env, a.data(), K, P, s0)) return rc;
+            if (int rc = run_ahead_pass(env, act, k0, K, P, s0)) return rc;
         }
         return MRCA_OK;
     }

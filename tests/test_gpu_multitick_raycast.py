@@ -5,7 +5,8 @@ Two envs of one seed and one action pool: one is driven by ``step_many`` -- call
 after the other, the last one crossing a pass boundary (a pass is at most 256 ticks) --, the other tick by tick with ``step``.
 After every call every field a caller reads (bench.DUMP_FIELDS), the scan ring, the ring heads and the hit bits must be equal
 bit for bit.  The whole set runs with the library's own choice of ticks per launch (the ring's frame count for these shapes,
-one in fidelity mode), with MRCA_TICKS_PER_LAUNCH=1 and with MRCA_TICKS_PER_LAUNCH=3 (fidelity mode's launches of several ticks).
+one in fidelity mode), with MRCA_TICKS_PER_LAUNCH=1, with 2 (whose blocks follow a rule of their own) and with 3 (fidelity mode's
+launches of several ticks).
 
 A launch of several ticks treats a robot that restarts in its first, a middle or its last tick differently (ring_rule,
 mrca_device.h): the reference run must hold each of them, which the test asserts from the reference's fresh flags -- the seeds
@@ -15,12 +16,12 @@ import pytest
 import torch
 
 import util as U
+from pass_plan_ref import PASS_TICKS, launch_plan
 from util import S
 
 pytestmark = pytest.mark.gpu
 
 CALLS = (1, 2, 3, 4, 5, 7, 38, 300)
-PASS_TICKS = 256          # csrc/mrca_abi.hip kAheadTicks (these envs are small: the ring has a slot per tick of a pass)
 def _stage1(beams=512, raster=None, **kw):
     sc = S.stage1(**kw)
     sc.beams = beams
@@ -41,28 +42,6 @@ SHAPES = {
     "stage1_raster8_4x8": lambda: _stage1(raster=0.1, num_worlds=4, robots_per_world=8, seed=46),
 }
 EXTRA = ("scan_ring", "ring_head", "hit_bits", "fresh")
-
-
-def launch_plan(K, T):
-    """(first tick, ticks) of every ray-cast launch of a world range in a run-ahead pass of K ticks at T ticks per launch:
-    run_ahead_pass's cut (csrc/mrca_abi.hip) -- blocks [0], [1], two, four times T (T = 2: once), then 2 T each, a block in
-    launches of up to T ticks, and an odd number of launches of several ticks made even by sending the first of them tick by
-    tick."""
-    blocks, a = [], 0
-    while a < K:
-        nb = len(blocks)
-        n = (1 if a < 4 else 4) if T == 1 else (1 if nb < 2 else 2 if nb == 2 else T if nb < (7 if T > 2 else 4) else 2 * T)
-        blocks.append((a, min(K, a + n)))
-        a += n
-    launches = []
-    for a, e in blocks:
-        for k in range(a, e, T):
-            launches.append((k, min(T, e - k)))
-    if sum(n > 1 for _k, n in launches) % 2:
-        i = next(i for i, (_k, n) in enumerate(launches) if n > 1)
-        k, n = launches[i]
-        launches[i:i + 1] = [(k + q, 1) for q in range(n)]
-    return launches
 
 
 def restart_positions(fresh, T):
@@ -121,7 +100,7 @@ def hip():
     return vec_env
 
 
-@pytest.mark.parametrize("ticks_per_launch", [None, 1, 3])
+@pytest.mark.parametrize("ticks_per_launch", [None, 1, 2, 3])
 @pytest.mark.parametrize("chains", [1, 2, 3])
 @pytest.mark.parametrize("name", list(SHAPES))
 def test_step_many_equals_tick_by_tick(hip, monkeypatch, name, chains, ticks_per_launch):

@@ -230,8 +230,8 @@ def test_bench_schedule_leaves_the_world_where_the_c_oracle_leaves_it(hip, name,
 @pytest.mark.parametrize("chains", [1, 2, 3])
 def test_step_many_of_every_short_length(hip, chains):
     """The run-ahead pass enqueues its ticks in blocks -- [0], [1], [2], [3], then fours -- with the move launches three blocks
-    ahead of the ray casts (csrc/mrca_abi.hip run_ahead_pass): calls of 1, 2, ... 11 ticks one after the other (every shape of a
-    pass's head and tail, blocks that do not exist included) leave the world where the C oracle's tick-by-tick run leaves it."""
+    ahead of the ray casts (the plan of a pass: csrc/mrca_pass_plan.h; run_ahead_pass in csrc/mrca_abi.hip executes it): calls of
+    1, 2, ... 11 ticks one after the other (every shape of a pass's head and tail, blocks that do not exist included) leave the world where the C oracle's tick-by-tick run leaves it."""
     import bench
     sc = S.stage1(num_worlds=6, robots_per_world=16, seed=77)
     env = hip.VecStageWorld(sc)
