@@ -46,15 +46,6 @@ using mrca::DeviceGuard;
 using mrca::kAheadTicks;
 #define fail(...) mrca::set_error(__VA_ARGS__)
 
-// log2 of the beams a marching thread of the ray cast owns (EnvView::ray_shift): 2 per thread, 4 in worlds of more than 64
-// robots -- as long as that leaves the workgroup two whole wavefronts or more (the measurements: mrca_create)
-// (the marching threads of a workgroup are whole wavefronts -- beams >> shift is a multiple of 64: a wave's ballot is one word of
-// MRCA_F_HIT_BITS)
-inline int32_t product_ray_shift(int32_t beams, int32_t big) {
-    if (big && (beams >> 2) >= 128 && (beams >> 2) % 64 == 0) return 2;
-    return (beams >= 256 && (beams >> 1) % 64 == 0) ? 1 : 0;
-}
-
 #define HIP_TRY(expr)                                                                               \
     do {                                                                                            \
         hipError_t _e = (expr);                                                                     \
@@ -580,8 +571,7 @@ static mrca::EnvView make_view(const mrca_config* cfg, const Layout& L, char* a,
     v.edge_slots = mrca::edge_event_slots(v.g.inv_cell);
     v.raster_inv = cfg->collision_raster > 0.0f ? 1.0f / cfg->collision_raster : 0.0f;
     v.raster_res = cfg->collision_raster;
-    // the ray cast tests 4 x 4 cells of a neighbour's outline window where that covers every outline (Stage's 0.2 m), else 8 x 8
-    v.raster_kw = (cfg->collision_raster > 0.0f && mrca::outline_span(v.raster_inv) <= 4) ? 4 : 8;
+    v.raster_kw = mrca::raster_window(v.raster_inv);
     v.lidar_radius = 0.2917f;
     v.lidar_near = 0.30f;
     v.lidar_reach2 = mrca::kLidarReach2;
@@ -604,21 +594,8 @@ static mrca::EnvView make_view(const mrca_config* cfg, const Layout& L, char* a,
     v.launch_stamps = nullptr;
     v.launch_slot = 0;
 #endif
-    // Launch shape of the ray cast, measured (profiles/r02/r02_c_ablation_launch_shapes.txt, 4096 / 8228 robots, HIP events):
-    //   2 beams per thread one after the other, first wave prepares the neighbours   28.1 / 33.7 us   <- product
-    //   1 beam per thread (512 threads), first wave prepares                           31.6 / 41.1 us
-    //   2 beams per thread in lock step (two lookups in flight), first wave prepares   34.7 / 37.9 us
-    //   the same three with a dedicated fifth preparation wave                          31.5-37.8 / 39.9-48.5 us
-    // i.e. neither more lookups in flight per thread nor taking the preparation off the marching waves pays: the
-    // lock-step loop costs 62 instead of 54 VALU instructions per jump and keeps finished rays idling, the extra
-    // wave costs a resident workgroup per CU.
-    // Worlds of more than 64 robots (the chunked neighbour lists of the big-world path), one circle of 50 000, PROFILING build
-    // (profiles/r04_m_slice_probe*.txt; full launch / one rank's slice of 6 250 robots):
-    //   4 beams per thread one after the other (2 waves per workgroup, 4096 workgroups resident)   445 /  77 us   <- product
-    //   2 beams per thread one after the other                                                      536 /  88 us
-    //   2 / 4 beams per thread in lock step (rounds 2-3)                                      548, 578 / 88, 94 us
-    //   1 beam per thread                                                                           844 / 133 us
-    v.ray_shift = product_ray_shift(cfg->beams, v.big);
+    // the ray cast's launch shape: the product's (mrca_ray_shape.h, with the measurements behind it)
+    v.ray_shift = mrca::product_ray_shift(cfg->beams, v.big);
     v.ray_prep_wave = 0;
     v.ray_sequential = 1;
     return v;
@@ -627,7 +604,7 @@ static mrca::EnvView make_view(const mrca_config* cfg, const Layout& L, char* a,
 // what the move launch and the ray cast need of a CU's LDS
 static int check_lds(mrca_env* env) {
     const mrca::EnvView& v = env->view;
-    env->lds_bytes = mrca::ray_lds_bytes(v);
+    env->lds_bytes = mrca::ray_shape(v).lds_bytes;
     if (!v.big && mrca::move_lds_bytes(v) > 64 * 1024)
         return fail(MRCA_ERR_UNSUPPORTED, "map_cell %.4f m is too fine for the LDS patches: use >= 0.01 m", (double)env->cfg.map_cell);
     if (env->lds_bytes > 160 * 1024)
@@ -1407,12 +1384,11 @@ int mrca_set_debug_flags(mrca_env* env, int32_t flags) {
     const int knob = (flags >> 8) & 7;
     if (knob) {
         const int shift = knob - 1;
-        const int threads = env->cfg.beams >> shift;
-        if (shift > 2 || threads < 64 || threads % 64 || threads < (env->cfg.beams >> 2))
-            return fail(MRCA_ERR_INVALID, "beams-per-thread knob %d out of range", knob);
+        if (!mrca::ray_knob_ok(env->cfg.beams, shift, (flags & 0x800) != 0))
+            return fail(MRCA_ERR_INVALID, "beams-per-thread knob %d out of range, or more than 1024 threads", knob);
         env->view.ray_shift = shift;
     } else {
-        env->view.ray_shift = product_ray_shift(env->cfg.beams, env->view.big);   // the product's launch shape
+        env->view.ray_shift = mrca::product_ray_shift(env->cfg.beams, env->view.big);   // the product's launch shape
     }
     env->view.ray_prep_wave = (flags & 0x800) ? 1 : 0;
     env->view.ray_sequential = (flags & 0x1000) ? 0 : 1;

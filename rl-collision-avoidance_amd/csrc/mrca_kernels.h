@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "mrca_device.h"
+#include "mrca_ray_shape.h"
 
 namespace mrca {
 
@@ -97,9 +98,9 @@ struct EnvView {
     float collide_reach2; // squared centre distance beyond which two robots cannot collide (broad phase)
     int32_t foot_hc;      // half extent (cells) of the move kernel's per-robot mini tile
     int32_t edge_slots;   // crossings per axis a footprint edge can have on this map (mrca_device.h edge_event_slots)
-    int32_t ray_shift;    // raycast_kernel marches 1 << ray_shift beams per thread in lock step
-    int32_t ray_sequential; // 1 (with ray_shift 1): the two beams of a thread are marched one after the other
-    int32_t ray_prep_wave;  // 1: a dedicated wave prepares the neighbour list (blockDim = beams >> ray_shift + 64)
+    int32_t ray_shift;    // a marching thread owns 1 << ray_shift beams (the raster lidar: at most 2); mrca_ray_shape.h has the rules
+    int32_t ray_sequential; // 1, the product: a thread marches its beams one after the other; 0: in lock step (ignored by the raster lidar)
+    int32_t ray_prep_wave;  // 1: a dedicated wave more prepares the neighbour list; 0, the product: the first marching wave does (ignored by the raster lidar)
     uint32_t r_magic;     // ceil(2^32 / R) for R <= 64: n / R == umulhi(n, r_magic) for every robot index n < 2^24
     int32_t debug_flags;  // profiling ablations only (mrca_set_debug_flags, -DMRCA_PROFILING builds)
     uint32_t* status;     // [1] sticky device-side error bits (kStatus*), read and cleared by mrca_check()
@@ -184,7 +185,10 @@ struct RayTicks {
     RayTicksIn in;
 };
 
-size_t ray_lds_bytes(const EnvView& e);
+// the shape of a view's ray cast: which variant, how many threads, how much LDS (mrca_ray_shape.h)
+inline RayShape ray_shape(const EnvView& e) {
+    return ray_shape(e.B, e.big != 0, e.raster_inv, e.raster_kw, e.ray_shift, e.ray_sequential != 0, e.ray_prep_wave != 0);
+}
 size_t move_lds_bytes(const EnvView& e);
 
 // `start` / `stop` (both or neither): events stamped with the BEGIN of the first and the END of the last kernel of the launch

@@ -1084,11 +1084,8 @@ void read_move_stamps(unsigned long long* host, int worlds) {      // [kMoveStam
 #endif
 
 
-size_t ray_lds_bytes(const EnvView& e) {
-    size_t b = kWave * (sizeof(float4) + sizeof(int2)) + 16 + (size_t)e.B * 8;
-    if (e.raster_inv > 0.0f && !e.big) b += kWave * sizeof(OutlineBits);   // fidelity mode: the neighbours' outline records
-    return b;
-}
+// the sizes ray_shape (mrca_ray_shape.h) writes as numbers: a neighbour's float4 + int2, its outline record, a wavefront of them
+static_assert(sizeof(float4) + sizeof(int2) == 16 + 8 && sizeof(OutlineBits) == 16 && kWave == 64, "ray_shape's lds_bytes");
 
 size_t move_lds_bytes(const EnvView& e) {
     const int rows = 2 * e.foot_hc + 1;
@@ -1096,6 +1093,15 @@ size_t move_lds_bytes(const EnvView& e) {
     size_t b = (size_t)kWave * rows * words * 4 + (2 + kMoveWaves) * kWave * sizeof(int);
     if (e.raster_inv > 0.0f) b += (size_t)kWave * sizeof(uint2);   // fidelity mode: the provisional outlines' bitmaps
     return b;
+}
+
+// One launch, either way: with events or flags through hipExtLaunchKernelGGL (the dispatch's own timestamps, mrca_kernels.h),
+// otherwise the plain launch
+template <class Kernel, class... Args>
+static void launch_ext_or_plain(bool ext, Kernel kernel, dim3 grid, dim3 block, size_t lds, hipStream_t s, hipEvent_t start,
+                                hipEvent_t stop, unsigned flags, Args... args) {
+    if (ext) hipExtLaunchKernelGGL(kernel, grid, block, (uint32_t)lds, s, start, stop, flags, args...);
+    else hipLaunchKernelGGL(kernel, grid, block, lds, s, args...);
 }
 
 void launch_move(const EnvView& e, const float* actions, hipStream_t s, hipEvent_t start, hipEvent_t stop, const EnvView* in,
@@ -1108,12 +1114,8 @@ void launch_move(const EnvView& e, const float* actions, hipStream_t s, hipEvent
         out.launch_stamps = e.launch_stamps;
         out.launch_slot = e.launch_slot;
 #endif
-        if (start || stop || flags)
-            hipExtLaunchKernelGGL(move_kernel, dim3(e.world_count), dim3(kWave * kMoveWaves), (uint32_t)move_lds_bytes(e), s, start,
-                                  stop, flags, e.R, e.world_first, r.pose, r.head, actions, e.live, r.goal, r.outline, e.dev, out);
-        else
-            hipLaunchKernelGGL(move_kernel, dim3(e.world_count), dim3(kWave * kMoveWaves), move_lds_bytes(e), s, e.R, e.world_first,
-                               r.pose, r.head, actions, e.live, r.goal, r.outline, e.dev, out);
+        launch_ext_or_plain(start || stop || flags, move_kernel, dim3(e.world_count), dim3(kWave * kMoveWaves), move_lds_bytes(e), s,
+                            start, stop, flags, e.R, e.world_first, r.pose, r.head, actions, e.live, r.goal, r.outline, e.dev, out);
         return;
     }
     // (the collision hash's heads and the lidar hash's counts are left clean by the tick before: bw_finish_kernel /
@@ -1178,70 +1180,23 @@ void launch_head_init(const EnvView& e, hipStream_t s) {
 }
 
 void launch_raycast(const EnvView& e, int only_fresh, hipStream_t s, hipEvent_t start, hipEvent_t stop) {
-    const bool raster_mode = !e.big && e.raster_inv > 0.0f;
-    // fidelity mode launches the product's shapes only (2 beams per thread one after the other, or 1; the first wave prepares)
-    const int threads = raster_mode ? (e.B >> (e.ray_shift == 0 ? 0 : 1)) : (e.B >> e.ray_shift) + (e.ray_prep_wave ? kWave : 0);
-    const size_t lds = ray_lds_bytes(e);
-    const dim3 grid(e.ray_count);
     if (e.ray_count <= 0) return;
-    const bool seq = e.ray_sequential != 0;
+    const RayShape shape = ray_shape(e);
     RayIn rin{e.goal, e.fresh, e.outline, e.eager_views};
 #if defined(MRCA_PROFILING)
     rin.launch_stamps = e.launch_stamps;
     rin.launch_slot = e.launch_slot;
 #endif
-#define MRCA_RAY(K, BIG, SEQ) MRCA_RAY4(K, BIG, SEQ, 0)
-#define MRCA_RAY4(K, BIG, SEQ, RKWV)                                                                                          \
-    do {                                                                                                               \
-        if (rin.views)                                                                                                 \
-            hipExtLaunchKernelGGL((raycast_kernel<K, BIG, SEQ, RKWV, true>), grid, dim3(threads), (uint32_t)lds, s, start, stop, 0, \
-                                  only_fresh, e.ray_first, e.ray_count, e.R, e.pose, e.head, e.beam_cos, e.beam_sin,         \
-                                  e.ring_head, e.dev, rin);                                                              \
-        else if (start || stop)                                                                                        \
-            hipExtLaunchKernelGGL((raycast_kernel<K, BIG, SEQ, RKWV, false>), grid, dim3(threads), (uint32_t)lds, s, start, stop, 0, \
-                                  only_fresh, e.ray_first, e.ray_count, e.R, e.pose, e.head, e.beam_cos, e.beam_sin,         \
-                                  e.ring_head, e.dev, rin);                                                              \
-        else                                                                                                           \
-            hipLaunchKernelGGL((raycast_kernel<K, BIG, SEQ, RKWV, false>), grid, dim3(threads), lds, s, only_fresh, e.ray_first,    \
-                               e.ray_count, e.R, e.pose, e.head, e.beam_cos, e.beam_sin, e.ring_head, e.dev, rin);     \
-    } while (0)
-    if (raster_mode) {
-        if (e.raster_kw <= 4) {
-            if (e.ray_shift == 0) MRCA_RAY4(1, false, false, 4);
-            else MRCA_RAY4(2, false, true, 4);
-        } else {
-            if (e.ray_shift == 0) MRCA_RAY4(1, false, false, 8);
-            else MRCA_RAY4(2, false, true, 8);
-        }
-        return;
-    }
-    if (e.big) {
-        switch (e.ray_shift) {
-            case 0: MRCA_RAY(1, true, false); break;
-            case 1:
-                if (seq) MRCA_RAY(2, true, true);
-                else MRCA_RAY(2, true, false);
-                break;
-            default:
-                if (seq) MRCA_RAY(4, true, true);      // the product's shape for big worlds (mrca_abi.hip)
-                else MRCA_RAY(4, true, false);
-                break;
-        }
-        return;
-    }
-    switch (e.ray_shift) {
-        case 0: MRCA_RAY(1, false, false); break;
-        case 1:
-            if (seq) MRCA_RAY(2, false, true);
-            else MRCA_RAY(2, false, false);
-            break;
-        default:
-            if (seq) MRCA_RAY(4, false, true);      // two waves per workgroup: all 4096 robots resident at once
-            else MRCA_RAY(4, false, false);
-            break;
-    }
-#undef MRCA_RAY
-#undef MRCA_RAY4
+    with_ray_variant(shape, [&](auto v) {
+        using V = decltype(v);
+        const auto launch = [&](bool ext, auto kernel) {
+            launch_ext_or_plain(ext, kernel, dim3(e.ray_count), dim3(shape.threads), shape.lds_bytes, s, start, stop, 0, only_fresh,
+                                e.ray_first, e.ray_count, e.R, e.pose, e.head, e.beam_cos, e.beam_sin, e.ring_head, e.dev, rin);
+        };
+        // the VIEWS epilogue is a kernel of its own, launched the extended way with or without events
+        if (rin.views) launch(true, raycast_kernel<V::K, V::BIG, V::SEQ, V::RKW, true>);
+        else launch(start || stop, raycast_kernel<V::K, V::BIG, V::SEQ, V::RKW, false>);
+    });
 }
 
 void launch_gae(const float* rewards, const float* values, const float* last_value, const uint8_t* dones, float gamma,

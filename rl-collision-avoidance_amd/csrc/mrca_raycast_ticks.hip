@@ -14,6 +14,7 @@
 // for the VIEWS and raster paths too).  Never big worlds, never the lazy_obs = 0 epilogue (it reads rows earlier ticks stored).
 #include "mrca_kernels.h"
 
+#include <assert.h>
 #include <hip/hip_ext.h>
 
 #include "mrca_raycast_body.h"
@@ -60,40 +61,17 @@ __global__ __launch_bounds__(1024, (RKW == 4 ? 8 : 1)) void raycast_ticks_kernel
 
 void launch_raycast_ticks(const EnvView& e, const RayTicks& t, hipStream_t s) {
     if (e.ray_count <= 0 || t.ticks <= 0) return;
-    const bool raster_mode = e.raster_inv > 0.0f;
-    // (the shapes of launch_raycast)
-    const int threads = raster_mode ? (e.B >> (e.ray_shift == 0 ? 0 : 1)) : (e.B >> e.ray_shift) + (e.ray_prep_wave ? kWave : 0);
-    const size_t lds = ray_lds_bytes(e);
-    const dim3 grid(e.ray_count, t.ticks);
-    const bool seq = e.ray_sequential != 0;
+    const RayShape shape = ray_shape(e);
+    assert(!shape.big);
     const int ticks = t.ticks | (t.last_is_env ? 1 << 8 : 0);
     RayTicksIn in = t.in;
     in.env_head = e.head;
-#define MRCA_RAYT(K, SEQ, RKWV)                                                                                              \
-    hipLaunchKernelGGL((raycast_ticks_kernel<K, SEQ, RKWV>), grid, dim3(threads), lds, s, e.ray_first, e.ray_count, e.R, ticks,  \
-                       t.slot0, t.stride, t.off_head, e.beam_cos, e.beam_sin, e.pose, e.dev, in)
-    if (raster_mode) {
-        if (e.raster_kw <= 4) {
-            if (e.ray_shift == 0) MRCA_RAYT(1, false, 4);
-            else MRCA_RAYT(2, true, 4);
-        } else {
-            if (e.ray_shift == 0) MRCA_RAYT(1, false, 8);
-            else MRCA_RAYT(2, true, 8);
-        }
-        return;
-    }
-    switch (e.ray_shift) {
-        case 0: MRCA_RAYT(1, false, 0); break;
-        case 1:
-            if (seq) MRCA_RAYT(2, true, 0);
-            else MRCA_RAYT(2, false, 0);
-            break;
-        default:
-            if (seq) MRCA_RAYT(4, true, 0);
-            else MRCA_RAYT(4, false, 0);
-            break;
-    }
-#undef MRCA_RAYT
+    with_ray_variant(shape, [&](auto v) {
+        using V = decltype(v);
+        hipLaunchKernelGGL((raycast_ticks_kernel<V::K, V::SEQ, V::RKW>), dim3(e.ray_count, t.ticks), dim3(shape.threads),
+                           shape.lds_bytes, s, e.ray_first, e.ray_count, e.R, ticks, t.slot0, t.stride, t.off_head, e.beam_cos,
+                           e.beam_sin, e.pose, e.dev, in);
+    });
 }
 
 }  // namespace mrca

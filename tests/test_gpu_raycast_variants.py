@@ -1,12 +1,13 @@
 """Every ray-cast variant a config can select in the product library, against the C oracle (run with -m gpu on an MI355X).
 
-launch_raycast (csrc/mrca_kernels.hip) picks a raycast_kernel instantiation from three properties of the config: the beams a
-marching thread owns (product_ray_shift, csrc/mrca_abi.hip: 1, 2 or -- big worlds -- 4), the lidar family (exact rectangles, the
-raster lidar with a 4-cell or an 8-cell outline window, worlds of more than 64 robots) and whether the epilogue forms
-MRCA_F_SCAN / MRCA_F_OBS itself (lazy_obs = 0).  Nine families times two epilogues are reachable without a profiling switch;
-SHAPES below holds one small env or more for each, ``selection`` restates the dispatch rules so that a change of them says
-which family lost its shape (test_the_shapes_cover_every_family: no GPU needed), and every shape runs lazy and eager against
-tests/util.COracleEnv, every field bit for bit.  An eager env is read through its RAW fields (``_scan`` / ``_obs``: no
+launch_raycast (csrc/mrca_kernels.hip) picks a raycast_kernel instantiation (ray_shape, csrc/mrca_ray_shape.h) from three
+properties of the config: the beams a marching thread owns (product_ray_shift: 1, 2 or -- big worlds -- 4), the lidar family
+(exact rectangles, the raster lidar with a 4-cell or an 8-cell outline window, worlds of more than 64 robots) and whether the
+epilogue forms MRCA_F_SCAN / MRCA_F_OBS itself (lazy_obs = 0).  Nine families times two epilogues are reachable without a
+profiling switch; SHAPES below holds one small env or more for each, ``selection`` restates the dispatch rules so that a change
+of them says which family lost its shape (test_the_shapes_cover_every_family: no GPU needed; tests/test_ray_shape_host.py holds
+the restatement against the header itself), and every shape runs lazy and eager against tests/util.COracleEnv, every field bit
+for bit.  An eager env is read through its RAW fields (``_scan`` / ``_obs``: no
 mrca_materialize call), so what is compared is what the epilogue stored.
 
 The further tests drive a lazy and an eager HIP env side by side through the calls beyond mrca_step that form the views too:
@@ -66,7 +67,7 @@ def scenario(name):
 
 # ------------------------------------------------------------------------------------------------ the dispatch rules, restated
 def product_ray_shift(beams, big):
-    """csrc/mrca_abi.hip: log2 of the beams per marching thread"""
+    """csrc/mrca_ray_shape.h: log2 of the beams per marching thread"""
     if big and (beams >> 2) >= 128 and (beams >> 2) % 64 == 0:
         return 2
     return 1 if beams >= 256 and (beams >> 1) % 64 == 0 else 0
@@ -79,7 +80,7 @@ def outline_span(inv_res):
 
 
 def selection(sc):
-    """(family, beams per thread) of the raycast_kernel instantiation launch_raycast (csrc/mrca_kernels.hip) picks for ``sc``"""
+    """(family, beams per thread) of the raycast_kernel instantiation ray_shape (csrc/mrca_ray_shape.h) picks for ``sc``"""
     big = sc.robots_per_world > 64
     shift = product_ray_shift(sc.beams, big)
     raster = np.float32(getattr(sc, "collision_raster", 0.0))
