@@ -94,7 +94,8 @@ enum mrca_field {
     MRCA_F_T,             /* i32 [N]     the `step` argument of get_reward_and_terminate (ppo_stage1.py:57,118)          */
     MRCA_F_EPISODE,       /* i32 [N]     episode counter (RNG stream position)                                          */
     MRCA_F_PREV_DIST,     /* f32 [N]     self.distance      stage_world1.py:176-177,185-186                              */
-    MRCA_F_SCAN_RING,     /* f32 [N,F,B] the last F scans of every robot (RAW ranges, 0..6 m, never negative) as a ring (ABI 4): a
+    MRCA_F_SCAN_RING,     /* f32 [N,F,B] the last F scans of every robot (RAW ranges, 0..6 m, never below zero; a zero may be -0.0: a beam
+                           *             that enters a wall at boundary time -0, as in the oracle) as a ring (ABI 4): a
                            *             tick writes ONE row per robot -- the tick's only per-beam store -- logical frame f
                            *             (0 = oldest) of robot n is slot (head[n] + 1 + f) mod F.  (ABI 3 kept a ring of
                            *             NORMALISED frames next to MRCA_F_SCAN: every beam was stored twice.  ABI 4-5 kept

@@ -813,7 +813,10 @@ MRCA_HD float ray_outline_entry(float fx, float fy, int ix0, int iy0, float dx, 
             best = (visited & (t < best)) ? t : best;
         }
     }
-    return best > 0.0f ? best : 0.0f;      // the origin's own cell is entered at "-inf": range 0
+    // the origin's own cell is entered at "-inf": range +0, as grid_march returns for a marked start cell.  Every other entry
+    // time keeps its sign: a cell across a raster line the origin stands on is entered at -0.0 (0 * a negative 1 / d), and so
+    // says the walk
+    return best > -kInf ? best : 0.0f;
 }
 
 // Separating-axis test of two robot rectangles; touching counts as overlap.
@@ -978,7 +981,7 @@ MRCA_HD float ray_outline_entry4(float fxe, float fye, int ix0, int iy0, bool xp
             best = fminf(best, cand);
         }
     }
-    return best > 0.0f ? best : 0.0f;
+    return best > -kInf ? best : 0.0f;      // (as in ray_outline_entry: +0 for the origin's own cell only, -0.0 stays -0.0)
 }
 
 // ------------------------------------------------------------------------------------------

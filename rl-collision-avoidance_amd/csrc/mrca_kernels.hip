@@ -154,7 +154,6 @@ struct MiniGrid {  // the move kernel's per-robot occupancy patch in LDS
 __device__ __forceinline__ float4 norm_obs4(float4 v) {
     return make_float4(norm_obs(fabsf(v.x)), norm_obs(fabsf(v.y)), norm_obs(fabsf(v.z)), norm_obs(fabsf(v.w)));
 }
-__device__ __forceinline__ float4 fabs4(float4 v) { return make_float4(fabsf(v.x), fabsf(v.y), fabsf(v.z), fabsf(v.w)); }
 
 __global__ void materialize_kernel(EnvView e, int what) {
     const int fstride = e.B >> 2;
@@ -169,7 +168,7 @@ __global__ void materialize_kernel(EnvView e, int what) {
         const int hd = e.ring_head[e.ray_first + r];
         const float4* src = ring + r * e.F * fstride + col;
         const float4 newest = src[hd * fstride];
-        if (what & 1) scan[r * fstride + col] = fabs4(newest);
+        if (what & 1) scan[r * fstride + col] = newest;     // (as stored: a zero range keeps the sign the march gave it)
         if (what & 2) {
             float4* dst = out + r * e.F * fstride + col;
             if (e.F == 3) {

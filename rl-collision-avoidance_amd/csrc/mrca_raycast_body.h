@@ -391,8 +391,10 @@ __device__ __forceinline__ void raycast_body(int only_fresh, int ray_first, int 
 #pragma unroll
         for (int k = 0; k < K; ++k) {
             const int b = tid + k * T;
-            // (|x|: fidelity mode's closed form may return -0.0 for a beam that starts inside a marked cell)
-            const float r = fabsf(rng[k] < kRangeMax ? rng[k] : kRangeMax);
+            // (the range as the march returned it, the sign of a zero included: a beam that enters an occupied cell at boundary
+            // time -0 -- a sensor exactly on the face of a wall, looking into it -- has range -0.0 in the oracle, and a caller that
+            // compares scans bit for bit sees it here too.  The readers that normalise take |x|.)
+            const float r = rng[k] < kRangeMax ? rng[k] : kRangeMax;
             // what the beam hit: one bit per beam beside the ring (MRCA_F_HIT_BITS), set = another robot.  stageros casts
             // Stage's return value to uint8 for LaserScan.intensities (stageros.cpp:506): 1 floorplan, 0 robot or miss.  A wave
             // holds 64 consecutive beams (T is a multiple of 64: product_ray_shift), so its ballot IS the row's word b >> 6.

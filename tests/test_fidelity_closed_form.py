@@ -138,9 +138,9 @@ def test_closed_form_return_equals_the_walk_through_marked_cells(res, kw):
     walk = np.zeros(n, np.float32)
     lib.emul_ray_outline(n, kw, res, ox.ctypes.data, oy.ctypes.data, dx.ctypes.data, dy.ctypes.data, ob.ctypes.data, 6.0,
                          closed.ctypes.data, walk.ctypes.data)
-    # (the sign of a zero range is not part of the result: a crossing at time -0.0 -- an origin on a raster line -- makes the
-    # walk return -0.0, and the scan ring keeps |range|)
-    bad = np.nonzero(np.abs(closed).view(np.uint32) != np.abs(walk).view(np.uint32))[0]
+    # (bits: a crossing at time -0.0 -- an origin on a raster line -- makes the walk return -0.0, the closed form too, and the
+    # scan ring keeps the range as it comes; +0.0 is the origin's own cell)
+    bad = np.nonzero(closed.view(np.uint32) != walk.view(np.uint32))[0]
     assert bad.size == 0, (bad[:5], closed[bad[:5]], walk[bad[:5]])
     hits = walk < 6.0
     assert 0.2 * n < hits.sum() < 0.95 * n            # the sample exercises both outcomes ...
