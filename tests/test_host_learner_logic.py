@@ -155,10 +155,12 @@ def test_recorded_gemm_choices_are_a_no_op_without_a_gpu(monkeypatch):
 
 
 def test_one_frame_buffer_row_indices_follow_the_deque_rule():
-    """The rule the one-frame buffer's row indices follow -- and that csrc/mrca_rollout_store.hip restates on the device
-    (tests/test_gpu_trainer.py holds the two bit-identical): the newest frame of tick t lives in row t + F - 1; tick 0 of a
-    horizon sees rows 0 .. F-1; a robot that restarted sees F times its fresh scan (ppo_stage1.py:59-60: the deque is refilled
-    with the first observation); everybody else drops its oldest row and appends the new one (ppo_stage1.py:87-89)."""
+    """The rule the one-frame buffer's row indices follow -- and that csrc/mrca_rollout_store.hip restates on the device: the
+    newest frame of tick t lives in row t + F - 1; tick 0 of a horizon sees rows 0 .. F-1; a robot that restarted sees F times
+    its fresh scan (ppo_stage1.py:59-60: the deque is refilled with the first observation); everybody else drops its oldest row
+    and appends the new one (ppo_stage1.py:87-89).  This test restates the rule by hand; where it meets what the reference
+    does -- a list of whole stacks, stacked (tests/rollout_ref.py) -- is tests/test_rollout_ref_host.py for the torch stores
+    and tests/test_gpu_rollout_store.py for the library's two kernels, both fed from the C oracle."""
     from mrca import ppo
     T, N, F, B = 9, 5, 3, 8
     rng = np.random.default_rng(3)
