@@ -195,17 +195,24 @@ struct HostField {
     std::vector<uint32_t> bits;
     int32_t width, height, wpr;
     std::vector<uint16_t> entries;      // 4 quadrant entries per cell
+    std::vector<uint16_t> octants;      // 8 octant entries per cell (built when first asked for; same pitch)
     int pitch;
 };
-std::shared_ptr<const HostField> host_field(const mrca_config* c) {
+std::shared_ptr<const HostField> host_field(const mrca_config* c, bool octants) {
     static std::mutex mu;
-    static std::vector<std::shared_ptr<const HostField>> cache;
+    static std::vector<std::shared_ptr<HostField>> cache;
     const size_t words = (size_t)c->map_height * c->map_words_per_row;
     std::lock_guard<std::mutex> lock(mu);
+    auto with_octants = [&](const std::shared_ptr<HostField>& f) {
+        int pitch = 0;
+        if (octants && f->octants.empty())
+            mrca::build_octant_rect_field(f->bits.data(), f->width, f->height, f->wpr, &f->octants, &pitch);
+        return f;
+    };
     for (const auto& f : cache)
         if (f->width == c->map_width && f->height == c->map_height && f->wpr == c->map_words_per_row &&
             std::memcmp(f->bits.data(), c->map_bits, words * 4) == 0)
-            return f;
+            return with_octants(f);
     auto f = std::make_shared<HostField>();
     f->bits.assign(c->map_bits, c->map_bits + words);
     f->width = c->map_width;
@@ -214,7 +221,7 @@ std::shared_ptr<const HostField> host_field(const mrca_config* c) {
     mrca::build_free_rect_field(c->map_bits, c->map_width, c->map_height, c->map_words_per_row, &f->entries, &f->pitch);
     if (cache.size() >= 4) cache.erase(cache.begin());
     cache.push_back(f);
-    return f;
+    return with_octants(f);
 }
 
 // Owners of what an env holds beside its arena.  A stream is synchronised before it is destroyed.
@@ -290,6 +297,7 @@ struct mrca_env {
     Layout layout;
     char* arena = nullptr;
     mrca::EnvView view;
+    DeviceBuffer<uint16_t> octant_rect;     // the octant free-rectangle array (outside the arena: the arena's size is ABI), or none
     DeviceBuffer<mrca::EnvView> view_dev;   // `view` in device memory (outside the arena): what move_kernel / raycast_kernel read
     size_t lds_bytes = 0;
     // timing
@@ -465,7 +473,7 @@ static int upload_tables(const mrca_config* cfg, const Layout& L, char* arena, i
     HIP_TRY(hipMemcpy(arena + L.off_map, cfg->map_bits, (size_t)cfg->map_height * cfg->map_words_per_row * 4,
                       hipMemcpyHostToDevice));
     {
-        const std::shared_ptr<const HostField> hf = host_field(cfg);
+        const std::shared_ptr<const HostField> hf = host_field(cfg, false);
         *free_rect_pitch = hf->pitch;
         HIP_TRY(hipMemcpy(arena + L.off_free_rect, hf->entries.data(), hf->entries.size() * sizeof(uint16_t),
                           hipMemcpyHostToDevice));
@@ -483,6 +491,37 @@ static int upload_tables(const mrca_config* cfg, const Layout& L, char* arena, i
         std::vector<int32_t> ones(N, 1);
         HIP_TRY(hipMemcpy(arena + L.field_off[MRCA_F_T], ones.data(), N * 4, hipMemcpyHostToDevice));
     }
+    return MRCA_OK;
+}
+
+// Does the march read the OCTANT free-rectangle array (mrca_host.h: build_octant_rect_field) after a ray's first jump?  It
+// takes fewer trips per wavefront there (Stage-1: 2.88 -> 2.66 per 64 beams, profiles/octant_field/field_probe.txt) from
+// records twice the size: a cache line holds 8 cells instead of 16.  The rule has two sides:
+//   * on where the array fits one XCD's 4 MiB L2 -- the 20 m Stage-1 rink (404 x 402 records of 16 bytes: 2.6 MB) does;
+//     Stage-2's 800 x 800 map (10.3 MB; its quadrant array, 5.1 MB, already does not) does not, and its trips would fall by
+//     1.2 % only (1.543 -> 1.525);
+//   * and only with lazy_obs = 1: the eager epilogue streams 60 MB of frame stacks through that L2 per tick of 4096 robots,
+//     the field does not stay resident, and the sparser records lose more to the misses than the trips save.
+// Measured on an MI355X, the two settings alternated on one box, five pairs, M agent-steps/s at the medians
+// (profiles/octant_field/ab.txt): 4096 Stage-1 robots, lazy_obs = 1, 1000 ticks 257.2 (quadrant array, the parent's library)
+// -> 267.3; the same with lazy_obs = 0: 178.1 (MRCA_FIELD_OCTANTS=0) -> 174.5 (=1).
+// MRCA_FIELD_OCTANTS=0|1, read once per mrca_create, overrides the rule for A/B runs on one box: 0 is the march over the
+// quadrant array for every lookup -- the same code, FreeRectField's uniforms 3 and 0.
+static bool field_octants(const mrca_config* c) {
+    if (const char* v = std::getenv("MRCA_FIELD_OCTANTS")) return std::atoi(v) != 0;
+    const size_t bytes = (size_t)(c->map_width + 2 * mrca::kFieldPadX) * (c->map_height + 2 * mrca::kFieldPadY) * 8 * sizeof(uint16_t);
+    return c->lazy_obs != 0 && bytes <= ((size_t)4 << 20);
+}
+
+// the octant array into a buffer of the env's own, and the march's three uniforms of the view onto it
+static int upload_octants(const mrca_config* cfg, mrca_env* env) {
+    const std::shared_ptr<const HostField> hf = host_field(cfg, true);
+    const size_t bytes = hf->octants.size() * sizeof(uint16_t);
+    HIP_TRY(device_alloc(&env->octant_rect, bytes));
+    HIP_TRY(hipMemcpy(env->octant_rect.get(), hf->octants.data(), bytes, hipMemcpyHostToDevice));
+    env->view.march_rect = env->octant_rect.get();
+    env->view.march_shift = 4;
+    env->view.march_major = 8;
     return MRCA_OK;
 }
 
@@ -529,6 +568,9 @@ static mrca::EnvView make_view(const mrca_config* cfg, const Layout& L, char* a,
     v.map_bits = reinterpret_cast<const uint32_t*>(a + L.off_map);
     v.free_rect = reinterpret_cast<const uint16_t*>(a + L.off_free_rect);
     v.free_rect_pitch = free_rect_pitch;
+    v.march_rect = v.free_rect;      // (mrca_create: upload_octants points the march at the octant array where it is on)
+    v.march_shift = 3;
+    v.march_major = 0;
     v.cellfield = reinterpret_cast<const uint8_t*>(a + L.off_cellfield);
     v.head = reinterpret_cast<float4*>(a + L.off_head);
     v.outline = cfg->collision_raster > 0.0f ? reinterpret_cast<mrca::OutlineBits*>(a + L.off_outline) : nullptr;
@@ -684,10 +726,13 @@ int mrca_create(const mrca_config* cfg, void* arena_dev, size_t arena_bytes, mrc
     if (int rc = attach_arena(env.get(), arena_dev, arena_bytes)) return rc;
     int free_rect_pitch = 0, num_groups = 0;
     if (int rc = upload_tables(cfg, env->layout, env->arena, &free_rect_pitch, &num_groups)) return rc;
+    const bool octants = field_octants(cfg);
     env->cfg.map_bits = nullptr;  // host pointers are not retained
     env->cfg.reset_mode = env->cfg.goal_mode = env->cfg.group_id = nullptr;
     env->cfg.init_table = env->cfg.goal_table = nullptr;
     env->view = make_view(cfg, env->layout, env->arena, free_rect_pitch, num_groups);
+    if (octants)
+        if (int rc = upload_octants(cfg, env.get())) return rc;
     if (int rc = check_lds(env.get())) return rc;
     if (!env->view.big) init_step_many(env.get());
     HIP_TRY(upload_view(env.get()));       // (the view is final from here on)

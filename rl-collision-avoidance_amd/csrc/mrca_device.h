@@ -187,7 +187,10 @@ MRCA_HD float grid_march(const Occ& occ, const GridGeom& g, float ox, float oy, 
 // straight to the face where it leaves the rectangle of the cell it is in and looks again: ~1.2 lookups per lidar ray
 // on the Stage-1 rink, and the cell bitmap is never read.  (Rounds 1-3 stored ONE rectangle per cell, grown on all four
 // sides -- the two extents a ray does not use narrowed the two it does: 1.7 lookups per ray, and 3.0 instead of 2.6 loop
-// iterations per 64-beam wavefront; tools/field_probe.cpp)
+// iterations per 64-beam wavefront; tools/field_probe.cpp)  Where it pays (mrca_abi.hip: field_octants) the
+// lookups AFTER a ray's first jump read a second array of EIGHT rectangles per cell -- each quadrant's grown 2 : 1 toward
+// the ray's major axis (mrca_host.h: build_octant_rect_field): 2.88 -> 2.66 loop trips per wavefront and beam on the Stage-1
+// rink.  The layout is two uniform values of the field object, the instruction stream is one.
 //
 // Exactness: grid_march is a 2-way merge of the x-crossing events tx(b) and the y-crossing events
 // ty(b) (both monotone in b), ties -> y first.  Leaving the rectangle through its x face Bx happens
@@ -248,9 +251,13 @@ MRCA_HD int clamp_from(int x, int hi) {   // clamp(x, LO, hi), LO <= hi
 #endif
 }
 
-struct FreeRectField {   // quadrant free-rectangle field straight from global memory (L1/L2-resident)
-    const uint16_t* d;   // base of the padded array: 4 entries (quadrants 0..3) per cell
+struct FreeRectField {   // free-rectangle field straight from global memory (L1/L2-resident)
+    const uint16_t* d;   // base of the padded array: 4 entries (quadrants 0..3) per cell, or 8 (octants, mrca_host.h)
     int32_t w, h, pitch; // map size in cells, CELLS per padded row
+    // The record layout as UNIFORM VALUES, so that one instruction stream marches over either array: log2 of a cell's
+    // record size, and what a ray with |dx| >= |dy| adds to its quadrant's byte offset.  Quadrant array (the default, what
+    // FreeRectField{d, w, h, pitch} is): 3 and 0; octant array: 4 and 8.
+    uint32_t shift = 3, major = 0;
     // byte offset of cell (ix, iy)'s record from d (cells outside the map clamp into the zero border)
     MRCA_HD uint32_t cell_offset(int ix, int iy) const {
         const int x = clamp_from<-kFieldPadX>(ix, w + kFieldPadX - 1);
@@ -261,13 +268,19 @@ struct FreeRectField {   // quadrant free-rectangle field straight from global m
 #else
         const int idx = y * pitch + x;
 #endif
-        return (uint32_t)(idx + (kFieldPadY * pitch + kFieldPadX)) << 3;
+        return (uint32_t)(idx + (kFieldPadY * pitch + kFieldPadX)) << shift;
     }
-    // the entry of quadrant q (qbytes = 2 * q) of a cell
+    // byte offset of a ray's entry in a cell's record: 2 * quadrant, + `major` for a ray with |dx| >= |dy| (an exactly diagonal
+    // ray takes the x-major entry: the rule is >=; either rectangle is valid for it)
+    MRCA_HD uint32_t entry_bytes(float dx, float dy) const {
+        return (dx > 0.0f ? 2u : 0u) + (dy > 0.0f ? 4u : 0u) + (__builtin_fabsf(dx) >= __builtin_fabsf(dy) ? major : 0u);
+    }
+    // the entry at byte offset qbytes (entry_bytes) of a cell's record
     MRCA_HD uint32_t operator()(int ix, int iy, uint32_t qbytes) const {
         return *reinterpret_cast<const uint16_t*>(reinterpret_cast<const char*>(d) + (cell_offset(ix, iy) + qbytes));
     }
-    // all four entries of a cell: .x = quadrants 0 | 1 << 16, .y = quadrants 2 | 3 << 16 (what a `head` record carries)
+    // all four entries of a cell of the QUADRANT array: .x = quadrants 0 | 1 << 16, .y = quadrants 2 | 3 << 16 (what a `head`
+    // record carries)
     MRCA_HD void cell(int ix, int iy, uint32_t* lo, uint32_t* hi) const {
         const uint32_t* p = reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(d) + cell_offset(ix, iy));
         *lo = p[0];
@@ -325,8 +338,9 @@ MRCA_HD float grid_march_skip(const Field& field, const GridGeom& g, const March
     const float tmax_c = tmax * g.inv_cell;
     const bool xnz = dx != 0.0f, ynz = dy != 0.0f;
     const bool xpos = dx > 0.0f, ypos = dy > 0.0f;
-    // the ray's quadrant picks which of the four rectangles of a cell it reads -- from the origin's cell onwards
-    const uint32_t qbytes = (xpos ? 2u : 0u) + (ypos ? 4u : 0u);
+    // the ray's quadrant picks which of the four rectangles of the origin's cell it starts from (org.v_lo / v_hi: always
+    // quadrant entries), its quadrant and major axis which entry of a cell's record every later lookup reads
+    const uint32_t qbytes = field.entry_bytes(dx, dy);
     const uint32_t vq = ypos ? org.v_hi : org.v_lo;
     uint32_t v = xpos ? vq >> 16 : vq & 0xFFFFu;  // carried: one field lookup per jump
     if (v == kCellOccupied) return 0.0f;
@@ -445,7 +459,7 @@ MRCA_HD void grid_march_skip_n(const Field& field, const GridGeom& g, const Marc
         inv_dy[k] = dy[k] != 0.0f ? rcp_exact(dy[k]) : kInf;
         bx[k] = org.ix0 + (dx[k] > 0.0f ? 1 : 0);
         by[k] = org.iy0 + (dy[k] > 0.0f ? 1 : 0);
-        qb[k] = (dx[k] > 0.0f ? 2u : 0u) + (dy[k] > 0.0f ? 4u : 0u);
+        qb[k] = field.entry_bytes(dx[k], dy[k]);
         const uint32_t vq = dy[k] > 0.0f ? org.v_hi : org.v_lo;
         v[k] = dx[k] > 0.0f ? vq >> 16 : vq & 0xFFFFu;
         t[k] = 0.0f;

@@ -107,6 +107,11 @@ struct EnvView {
     int32_t eager_views;  // HOST side only (travels to the kernel in RayIn): the views the next ray cast forms itself, see RayIn
     const EnvView* dev;   // the env's copy of this struct in device memory (mrca_abi.hip: uploaded by mrca_create, again by the
                           // profiling build's debug switches); a host-side copy with other slots / ranges keeps pointing at it
+    // what the march's lookups AFTER the origin's jump read: the octant array ([..][free_rect_pitch][8], shift 4, major 8) or,
+    // where it is switched off (mrca_abi.hip: field_octants), free_rect itself (shift 3, major 0) -- FreeRectField's uniforms.
+    // (One aligned 16-byte group behind everything else: no other field moves, and only the ray cast loads it.)
+    const uint16_t* march_rect;
+    int32_t march_shift, march_major;
 #if defined(MRCA_PROFILING)
     // profiling build only (MRCA_LAUNCH_STAMPS, mrca_abi.hip): [2 * slots] first start / last end of a launch on the 100 MHz
     // constant clock, by thread 0 of every 64th workgroup and the last (every workgroup: 4096 atomics on one word made a launch five times longer) -- the timeline of a mrca_step_many pass without a profiler attached

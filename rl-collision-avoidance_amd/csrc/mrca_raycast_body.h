@@ -273,8 +273,10 @@ __device__ __forceinline__ void raycast_body(int only_fresh, int ray_first, int 
         from_robot[k] = false;
     }
     if (marches && !MRCA_DBG(e, 2)) {
-        const FreeRectField field{e.free_rect, e.g.width, e.g.height, e.free_rect_pitch};
-        MarchOrigin org;                       // once per robot: shared by all its beams
+        // (the origin's entry is the quadrant one of the head record; every later lookup reads the march's own array)
+        const FreeRectField field{e.march_rect, e.g.width, e.g.height, e.free_rect_pitch, (uint32_t)e.march_shift,
+                                  (uint32_t)e.march_major};
+        MarchOrigin org;                      // once per robot: shared by all its beams
         org.fx = (x - e.g.x0) * e.g.inv_cell;
         org.fy = (y - e.g.y0) * e.g.inv_cell;
         org.ix0 = (int)floorf(org.fx);

@@ -3,11 +3,19 @@
 // only decides the jump count -- which the kernel's VALU-bound half is proportional to.
 //
 //   (a) the round-1..3 field: ONE rectangle per cell, grown greedily on all four sides (a ray only ever uses the two
-//       extents that face its direction of travel; the growth of the other two sides narrows them);
+//       extents that face its direction of travel; the growth of the other two sides narrows them) -- 1.7 lookups per beam
+//       on the Stage-1 rink; the product no longer builds it, the figure is in DESIGN.md 5.2;
 //   (b) QUADRANT fields: four rectangles per cell, each with the cell in the corner the ray ENTERS through (a ray of
-//       quadrant (+,+) looks up the rectangle that extends right and up only), grown greedily on its two sides.
+//       quadrant (+,+) looks up the rectangle that extends right and up only), grown greedily on its two sides: counted
+//       with a float walk of this file's own (policies: alternate growth, largest area, squares);
+//   (c) OCTANT fields (mrca_host.h: build_octant_rect_field): eight per cell, each quadrant's rectangle grown with a bias
+//       toward the ray's major axis -- counted by the product's own march (grid_march_skip over a field that counts its
+//       lookups), trips as the kernel's loop takes them, a wave = 64 consecutive beams: growth 2 : 1, 3 : 2 and 3 : 1, extents
+//       capped at 121 cells, for every jump or for every jump after the first (the origin's jump keeps the quadrant entry a
+//       `head` record carries: the form the product runs).
 //
-//   g++ -O2 -std=c++17 tools/field_probe.cpp -o tools/_build/field_probe && tools/_build/field_probe map.bin [robots]
+//   python tools/field_probe.py          # writes the three shipped maps, builds this file, runs it on each
+//   g++ -O2 -std=c++17 -pthread tools/field_probe.cpp -o tools/_build/field_probe && tools/_build/field_probe map.bin [robots] [half]
 // map.bin = int32 width, height, wpr; float cell, x0, y0; uint32 bits[height*wpr]   (tools/field_probe.py writes it)
 #include <cmath>
 #include <cstdio>
@@ -112,6 +120,57 @@ static int march_count(const Map& m, float ox, float oy, float dx, float dy, flo
     return lookups;
 }
 
+// a field that counts its lookups and remembers the last entry it returned
+struct Counting {
+    FreeRectField f;
+    mutable int lookups = 0;
+    mutable uint32_t last = 0;
+    uint32_t entry_bytes(float dx, float dy) const { return f.entry_bytes(dx, dy); }
+    uint32_t operator()(int ix, int iy, uint32_t qb) const { ++lookups; return last = f(ix, iy, qb); }
+};
+
+// (c): `robots` seeded poses uniform in the free cells of the +-half square, 512 beams each, the product's march.
+// origin_octant: the origin's jump takes the octant entry too (a `head` record of 32 bytes would carry it)
+static void octant_row(const Map& m, const GridGeom& g, const char* label, const FreeRectField& quad, const FreeRectField& later,
+                       bool origin_octant, int robots, float half) {
+    std::mt19937 rng(1);
+    std::uniform_real_distribution<float> U(-1.0f, 1.0f);
+    long long looks = 0, trips = 0, waves = 0, beams = 0, hist[12] = {0};
+    for (int r = 0; r < robots; ++r) {
+        float x, y;
+        do {
+            x = U(rng) * half;
+            y = U(rng) * half;
+        } while (m.occ((int)std::floor((x - m.x0) / m.cell), (int)std::floor((y - m.y0) / m.cell)));
+        const float th = U(rng) * 3.14159265f;
+        const MarchOrigin org0 = march_origin(quad, g, x, y);
+        int wmax = 0;
+        for (int b = 0; b < 512; ++b) {
+            const double a = th - M_PI / 2 + b * M_PI / 511;
+            const float dx = (float)std::cos(a), dy = (float)std::sin(a);
+            MarchOrigin org = org0;
+            if (origin_octant) {
+                const uint32_t e = later(org.ix0, org.iy0, later.entry_bytes(dx, dy));
+                org.v_lo = org.v_hi = e | e << 16;
+            }
+            Counting cf{later};
+            const uint32_t vq = dy > 0.0f ? org.v_hi : org.v_lo;
+            cf.last = dx > 0.0f ? vq >> 16 : vq & 0xFFFFu;
+            (void)grid_march_skip(cf, g, org, dx, dy, 6.0f);
+            // a trip looks up once unless it is the one that finds the beam's end (t >= tmax); a hit ends in a lookup
+            const int t = cf.lookups + (cf.last == kCellOccupied ? 0 : 1);
+            looks += cf.lookups;
+            ++hist[std::min(t, 11)];
+            wmax = std::max(wmax, t);
+            ++beams;
+            if ((b & 63) == 63) { trips += wmax; ++waves; wmax = 0; }
+        }
+    }
+    printf("  %-58s %.3f lookups / beam  %.3f trips / wave   trips per beam:", label, (double)looks / beams, (double)trips / waves);
+    for (int k = 1; k < 10; ++k) printf(" %d:%.3f", k, (double)hist[k] / beams);
+    printf("\n");
+}
+
 int main(int argc, char** argv) {
     if (argc < 2) return 1;
     FILE* f = fopen(argv[1], "rb");
@@ -125,18 +184,12 @@ int main(int argc, char** argv) {
     fclose(f);
     const int robots = argc > 2 ? atoi(argv[2]) : 2000;
     const float rmax = argc > 3 ? (float)atof(argv[3]) : 9.0f;        // robots uniform in a disc of this radius (stage 1)
-    std::vector<uint32_t> field;
+    std::vector<uint16_t> field;
     int pitch = 0;
     build_free_rect_field(m.bits.data(), m.w, m.h, m.wpr, &field, &pitch);
     std::vector<uint16_t> quad[4][4];
     for (int pol = 0; pol < 4; ++pol)
         for (int q = 0; q < 4; ++q) build_quadrant(m, q, &quad[pol][q], pol);
-    auto ext_a = [&](int ix, int iy, int sx, int sy, int* ex, int* ey) {
-        const int x = std::min(std::max(ix, -kFieldPadX), m.w + kFieldPadX - 1), y = std::min(std::max(iy, -kFieldPadY), m.h + kFieldPadY - 1);
-        const uint32_t v = field[(size_t)(y + kFieldPadY) * pitch + x + kFieldPadX];
-        *ex = (v >> (sx > 0 ? 8 : 0)) & 255;
-        *ey = (v >> (sy > 0 ? 24 : 16)) & 255;
-    };
     auto make_q = [&](int pol) {
         return [&, pol](int ix, int iy, int sx, int sy, int* ex, int* ey) {
             if (ix < 0 || iy < 0 || ix >= m.w || iy >= m.h) { *ex = *ey = 0; return; }
@@ -147,9 +200,9 @@ int main(int argc, char** argv) {
     };
     std::mt19937 rng(1);
     std::uniform_real_distribution<float> U(-1.0f, 1.0f);
-    long long la = 0, lq[3] = {0, 0, 0}, beams = 0, mism = 0; long long wave_s = 0; int wmax_s = 0;
-    long long hist_a[16] = {0}, hist_q[16] = {0};
-    long long wave_a = 0, wave_q = 0, waves = 0;      // per 64-beam wavefront: the MAXIMUM over its lanes is what it executes
+    long long lq[3] = {0, 0, 0}, beams = 0, mism = 0; long long wave_s = 0; int wmax_s = 0;
+    long long hist_q[16] = {0};
+    long long wave_q = 0, waves = 0;      // per 64-beam wavefront: the MAXIMUM over its lanes is what it executes
     for (int r = 0; r < robots; ++r) {
         float x, y;
         do {
@@ -158,47 +211,61 @@ int main(int argc, char** argv) {
         } while (x * x + y * y > rmax * rmax ||
                  m.occ((int)std::floor((x - m.x0) / m.cell), (int)std::floor((y - m.y0) / m.cell)));
         const float th = U(rng) * 3.14159265f;
-        int wmax_a = 0, wmax_q = 0;
+        int wmax_q = 0;
         for (int b = 0; b < 512; ++b) {
             const double a = th - 3.14159265358979 / 2 + b * 3.14159265358979 / 511;
             const float dx = (float)std::cos(a), dy = (float)std::sin(a);
-            float ra, rq;
-            const int ca = march_count(m, x, y, dx, dy, 6.0f, ext_a, &ra);
+            float rq;
             const int cq0 = march_count(m, x, y, dx, dy, 6.0f, make_q(0), &rq);
             const int cq1 = march_count(m, x, y, dx, dy, 6.0f, make_q(3), &rq);
             float rs;
             const int cq2 = march_count(m, x, y, dx, dy, 6.0f, make_q(2), &rs);
-            la += ca; lq[0] += cq0; lq[1] += cq1; lq[2] += cq2;
+            lq[0] += cq0; lq[1] += cq1; lq[2] += cq2;
             wmax_s = std::max(wmax_s, cq2 + (rs >= 6.0f ? 1 : 0));
             if ((b & 63) == 63) { wave_s += wmax_s; wmax_s = 0; }
             ++beams;
-            mism += std::fabs(ra - rq) > 1e-4f;
-            ++hist_a[std::min(ca, 15)];
+            mism += std::fabs(rs - rq) > 1e-4f;
             ++hist_q[std::min(cq0, 15)];
             // loop iterations = lookups + 1 unless the beam ended in a hit (the last iteration then found the wall)
-            const int ia = ca + (ra >= 6.0f ? 1 : 0), iq = cq0 + (rq >= 6.0f ? 1 : 0);
-            wmax_a = std::max(wmax_a, ia);
+            const int iq = cq0 + (rq >= 6.0f ? 1 : 0);
             wmax_q = std::max(wmax_q, iq);
             if ((b & 63) == 63) {
-                wave_a += wmax_a; wave_q += wmax_q; ++waves;
-                wmax_a = wmax_q = 0;
+                wave_q += wmax_q; ++waves;
+                wmax_q = 0;
             }
         }
     }
     printf("map %d x %d cells of %.3f m, %d robots x 512 beams\n", m.w, m.h, m.cell, robots);
     printf("lookups per beam after the origin's own entry (jumps = lookups + 1 when the beam ends beyond the last rectangle):\n");
-    printf("  one 4-sided rectangle per cell (product)      %.3f\n", (double)la / beams);
     printf("  quadrant corner rectangles, alternate growth  %.3f\n", (double)lq[0] / beams);
     printf("  quadrant corner rectangles, LARGEST AREA      %.3f\n", (double)lq[1] / beams);
     printf("  quadrant corner SQUARES (one byte per quadrant) %.3f lookups, wavefront iterations %.3f\n", (double)lq[2] / beams,
            (double)wave_s / waves);
-    printf("  loop iterations a 64-beam WAVEFRONT executes per beam pass (max over its lanes): product %.3f, quadrant %.3f\n",
-           (double)wave_a / waves, (double)wave_q / waves);
+    printf("  loop iterations a 64-beam WAVEFRONT executes per beam pass (max over its lanes): quadrant, alternate growth %.3f\n",
+           (double)wave_q / waves);
     printf("  range mismatches between fields (float walk, diagnostics only): %lld of %lld\n", mism, beams);
-    printf("  histogram of lookups   product: ");
-    for (int k = 0; k < 10; ++k) printf("%d:%.3f ", k, (double)hist_a[k] / beams);
-    printf("\n                        quadrant: ");
+    printf("  histogram of lookups  quadrant: ");
     for (int k = 0; k < 10; ++k) printf("%d:%.3f ", k, (double)hist_q[k] / beams);
     printf("\n");
+    // (c) the product's march over the product's builders
+    GridGeom g;
+    g.x0 = m.x0; g.y0 = m.y0; g.cell = m.cell; g.inv_cell = 1.0f / m.cell;
+    g.width = m.w; g.height = m.h; g.wpr = m.wpr;
+    const FreeRectField quad_f{field.data(), m.w, m.h, pitch};
+    printf("the product's march (grid_march_skip), trips as the kernel's loop takes them, waves of 64 consecutive beams:\n");
+    octant_row(m, g, "quadrant array for every lookup (MRCA_FIELD_OCTANTS=0)", quad_f, quad_f, false, robots, rmax);
+    const struct { int rx, ry, cap; const char* name; } pol[] = {{2, 1, 254, "2 : 1"}, {3, 2, 254, "3 : 2"}, {3, 1, 254, "3 : 1"},
+                                                                 {2, 1, 121, "2 : 1, extents <= 121"}, {1, 1, 254, "1 : 1 (major axis first)"}};
+    for (const auto& p : pol) {
+        std::vector<uint16_t> oct;
+        int p2 = 0;
+        build_octant_rect_field(m.bits.data(), m.w, m.h, m.wpr, &oct, &p2, p.rx, p.ry, p.cap);
+        const FreeRectField oct_f{oct.data(), m.w, m.h, p2, 4u, 8u};
+        char label[128];
+        snprintf(label, sizeof label, "octants %s, every jump", p.name);
+        octant_row(m, g, label, quad_f, oct_f, true, robots, rmax);
+        snprintf(label, sizeof label, "octants %s, the origin keeps the quadrant entry", p.name);
+        octant_row(m, g, label, quad_f, oct_f, false, robots, rmax);
+    }
     return 0;
 }

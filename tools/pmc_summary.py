@@ -33,7 +33,7 @@ def traffic_json(root, out, robots, scenario):
             for row in csv.DictReader(fh):
                 kn, cn = row.get("Kernel_Name", ""), row.get("Counter_Name", "")
                 for key in ("raycast_kernel", "move_kernel"):
-                    if key in kn and cn in ("FETCH_SIZE", "WRITE_SIZE"):
+                    if key in kn and cn in ("FETCH_SIZE", "WRITE_SIZE", "SQ_INSTS_VALU", "SQ_WAVES"):
                         acc[(key, cn)][0] += 1
                         acc[(key, cn)][1] += float(row.get("Counter_Value", 0) or 0)
     avg = {k: v[1] / v[0] for k, v in acc.items() if v[0]}
@@ -44,6 +44,10 @@ def traffic_json(root, out, robots, scenario):
          "dispatches": {f"{k[0]}:{k[1]}": acc[k][0] for k in acc},
          "note": "rocprofv3 --kernel-trace --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes), averages per launch in "
                  "KiB; FETCH_SIZE is doubled on gfx950 when converted to bytes (MI355X_MICROARCH.md HBM section)."}
+    # the SQ pair of the ray cast, where a pass of its own collected it (--pmc SQ_INSTS_VALU SQ_WAVES): bench.py's valu_issue
+    if ("raycast_kernel", "SQ_INSTS_VALU") in avg and ("raycast_kernel", "SQ_WAVES") in avg:
+        d["raycast_sq_insts_valu_per_launch"] = avg[("raycast_kernel", "SQ_INSTS_VALU")]
+        d["raycast_sq_waves_per_launch"] = avg[("raycast_kernel", "SQ_WAVES")]
     json.dump(d, open(out, "w"), indent=1)
     print(json.dumps(d))
 
