@@ -33,7 +33,9 @@
 extern "C" {
 #endif
 
-/* 6, additive: mrca_lidar_features_bf16 (the bf16 MFMA front end of the opt-in bf16 rollout inference); the opt-in fused bf16
+/* 6, additive: mrca_orca_actions_any (the ORCA baseline on worlds of any size); mrca_move_worlds / mrca_observe_worlds take the
+ * full range of an env with robots_per_world > 64.
+ * 6, additive: mrca_lidar_features_bf16 (the bf16 MFMA front end of the opt-in bf16 rollout inference); the opt-in fused bf16
  * update's mrca_lidar_features_bf16_rows, mrca_lidar_features_bf16_backward(_rows, _scratch).
  * 6 (round 6): MRCA_F_HIT_BITS -- what a beam hit is a bit plane of its own, MRCA_F_SCAN_RING holds plain ranges (5: the sign
  * bit of a ring entry); mrca_step_many's run-ahead schedule (chains < 0: the chained one).
@@ -205,7 +207,10 @@ int mrca_step_worlds(mrca_env* env, const float* actions_dev, int32_t first_worl
  * poses it left + get_local_goal (stageros.cpp:479-516, stage_world1.py:126-160) (+ the two views with lazy_obs = 0).
  * mrca_step_worlds(r) == mrca_move_worlds(r) then mrca_observe_worlds(r) on one stream.  What the split is for: a caller with
  * two streams and an event can hold two world ranges half a tick apart -- range B's move launch goes out when range A's has
- * finished, i.e. next to A's ray cast, tick after tick (bench.py --chains 2: the schedule, DESIGN.md 5.9: what it buys). */
+ * finished, i.e. next to A's ray cast, tick after tick (bench.py --chains 2: the schedule, DESIGN.md 5.9: what it buys).
+ * robots_per_world > 64: only the full range, and the two must alternate (a second mrca_move_worlds without the
+ * mrca_observe_worlds in between is MRCA_ERR_INVALID: the observe phase builds the lidar hash from what the move phase counted).
+ * Between the two the lidar hash describes the poses BEFORE the move: mrca_orca_actions_any refuses to read it there. */
 int mrca_move_worlds(mrca_env* env, const float* actions_dev, int32_t first_world, int32_t num_worlds, void* stream);
 int mrca_observe_worlds(mrca_env* env, int32_t first_world, int32_t num_worlds, void* stream);
 
@@ -303,7 +308,7 @@ int mrca_render(mrca_env* env, const mrca_render_view* views /* host */, int32_t
  * Asynchronous on `stream`, ONE launch (the params travel as kernel arguments); reads the env as it stands at that point of the
  * stream and writes none of it, so mrca_step with actions_dev can follow on the same stream.  Both lazy_obs values, any beams /
  * frames, exact and raster collision modes.  robots_per_world 1..64: more gives MRCA_ERR_UNSUPPORTED (a world's robots are the
- * lanes of one wavefront).  Everything is validated before the first HIP call (MRCA_ERR_INVALID): every float finite; radius,
+ * lanes of one wavefront); mrca_orca_actions_any below takes worlds of any size.  Everything is validated before the first HIP call (MRCA_ERR_INVALID): every float finite; radius,
  * neighbor_dist, time_horizon, time_horizon_obst, max_speed > 0; 0 <= obst_dist <= 6; 0 <= responsibility <= 1; max_neighbors
  * 0..48; actions_dev not NULL and 8-byte aligned. */
 typedef struct mrca_orca_params {
@@ -314,6 +319,24 @@ int mrca_orca_default_params(mrca_orca_params* out);
 int mrca_orca_actions(mrca_env* env, const mrca_orca_params* params /* host, NULL = defaults */,
                       const uint8_t* mask_dev /* u8[N] or NULL = all */, float* actions_dev /* f32[N,2] */,
                       float* vel_dev /* f32[N,2] or NULL */, void* stream);
+
+/* The same controller for ANY robots_per_world: same arguments, same validation in the same order (the messages name this
+ * call), same asynchronous single launch, same rule -- bit for bit.
+ *   robots_per_world <= 64: the launch of mrca_orca_actions; the results are identical.
+ *   robots_per_world  > 64: a robot's neighbours are found through the env's lidar hash (the counting sort of the robots by
+ *     6.5 m cell that every reset and every observe phase rebuilds for the ray cast): the (2g+1)^2 cells around the robot's
+ *     own, g = 1 for neighbor_dist <= 6.3, 2 for <= 12.8, 3 for <= 19.3; a larger neighbor_dist is MRCA_ERR_UNSUPPORTED (on
+ *     such worlds only).  One wavefront per robot streams the cells' robots through its lanes 64 at a time and keeps the
+ *     max_neighbors nearest by (distance, index), a total order: the result does not depend on the order inside the hash, and
+ *     it is the list mrca_orca_actions' rule would choose among all robots of the world.
+ *     The hash must describe the current poses.  It does after mrca_reset, mrca_step, mrca_step_slice, mrca_step_worlds,
+ *     mrca_step_many and mrca_observe_worlds; it does not between mrca_move_worlds and mrca_observe_worlds (nor before the
+ *     first mrca_reset): there the call returns MRCA_ERR_INVALID and names mrca_observe_worlds.  The env keeps that flag on
+ *     the host in the order of the calls, so calls on several streams must be issued in the order they are meant to run.
+ * Writes nothing of the env: no field, no scratch of the broad phase, no status bit. */
+int mrca_orca_actions_any(mrca_env* env, const mrca_orca_params* params /* host, NULL = defaults */,
+                          const uint8_t* mask_dev /* u8[N] or NULL = all */, float* actions_dev /* f32[N,2] */,
+                          float* vel_dev /* f32[N,2] or NULL */, void* stream);
 
 /* Synchronises `stream` and reports (then clears) the env's sticky device-side status word: MRCA_OK, or MRCA_ERR_HIP with
  * mrca_last_error() saying what went wrong on the device since the last check.  Today one condition: the ordered

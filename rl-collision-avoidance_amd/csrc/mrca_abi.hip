@@ -306,6 +306,11 @@ struct mrca_env {
     std::vector<Event> ev;       // 4 per recorded step: begin / end of the move launch, begin / end of the ray cast
     int ev_used = 0;
     int last_ray_count = 0;   // workgroups of the last ray-cast launch (profiling build: whose stamps are current)
+    // robots_per_world > 64: does the lidar hash (bw_lstart / bw_lsorted) describe the poses as they stand behind everything
+    // enqueued so far?  In enqueue order: false after a move phase without its observe phase, true after launch_lidar_grid
+    // (mrca_reset, the observe phase).  Who reads the hash outside the tick asks here (mrca_orca_actions_any).
+    bool lidar_hash_current = false;
+    bool lidar_counts_pending = false;    // a move phase has left the next hash's bucket populations in bw_lcount
     StreamCheck check;                    // (these four: mrca_step_many)
     AheadRing ahead;
     std::vector<WorldRange> ranges;       // world ranges 1 .. P - 1
@@ -765,7 +770,12 @@ int mrca_reset(mrca_env* env, const uint8_t* mask_dev, const float* poses_dev, c
     DeviceGuard guard(env->cfg.device);
     hipStream_t s = static_cast<hipStream_t>(stream);
     mrca::launch_reset(env->view, mask_dev, poses_dev, goals_dev, s);
+    if (env->view.big && env->lidar_counts_pending) {     // (a move phase whose observe phase never came: its counts are void)
+        HIP_TRY(hipMemsetAsync(env->view.bw_lcount, 0, ((size_t)env->view.bw_lmask + 1) * sizeof(int32_t), s));
+        env->lidar_counts_pending = false;
+    }
     mrca::launch_lidar_grid(env->view, /*counted=*/0, s);
+    env->lidar_hash_current = true;
     mrca::launch_raycast(env->view, /*only_fresh=*/1, s);
     if (!env->cfg.lazy_obs) mrca::launch_materialize(env->view, MRCA_VIEW_SCAN | MRCA_VIEW_OBS, s);
     HIP_TRY(hipGetLastError());
@@ -839,8 +849,10 @@ int mrca_orca_default_params(mrca_orca_params* out) {
     return MRCA_OK;
 }
 
-int mrca_orca_actions(mrca_env* env, const mrca_orca_params* params, const uint8_t* mask_dev, float* actions_dev, float* vel_dev,
-                      void* stream) {
+// What mrca_orca_actions and mrca_orca_actions_any check alike, in one order and with one wording (`fn` names the caller):
+// everything that can be judged without the env, then the env.  -> *out: the params as the kernels take them
+static int orca_validate(const char* fn, const mrca_env* env, const mrca_orca_params* params, const float* actions_dev,
+                         const float* vel_dev, mrca::OrcaParams* out) {
     mrca_orca_params p;
     if (params) p = *params;
     else mrca_orca_default_params(&p);
@@ -849,28 +861,54 @@ int mrca_orca_actions(mrca_env* env, const mrca_orca_params* params, const uint8
     static const char* const names[10] = {"radius", "neighbor_dist", "time_horizon", "time_horizon_obst", "obst_dist", "v_pref",
                                           "max_speed", "responsibility", "k_omega", "jitter"};
     for (int i = 0; i < 10; ++i)
-        if (!std::isfinite(fl[i])) return fail(MRCA_ERR_INVALID, "mrca_orca_actions: %s is not finite", names[i]);
-    if (!(p.radius > 0.0f)) return fail(MRCA_ERR_INVALID, "mrca_orca_actions: radius must be > 0");
-    if (!(p.neighbor_dist > 0.0f)) return fail(MRCA_ERR_INVALID, "mrca_orca_actions: neighbor_dist must be > 0");
-    if (!(p.time_horizon > 0.0f)) return fail(MRCA_ERR_INVALID, "mrca_orca_actions: time_horizon must be > 0");
-    if (!(p.time_horizon_obst > 0.0f)) return fail(MRCA_ERR_INVALID, "mrca_orca_actions: time_horizon_obst must be > 0");
-    if (!(p.max_speed > 0.0f)) return fail(MRCA_ERR_INVALID, "mrca_orca_actions: max_speed must be > 0");
-    if (!(p.obst_dist >= 0.0f && p.obst_dist <= 6.0f)) return fail(MRCA_ERR_INVALID, "mrca_orca_actions: obst_dist outside [0, 6]");
+        if (!std::isfinite(fl[i])) return fail(MRCA_ERR_INVALID, "%s: %s is not finite", fn, names[i]);
+    if (!(p.radius > 0.0f)) return fail(MRCA_ERR_INVALID, "%s: radius must be > 0", fn);
+    if (!(p.neighbor_dist > 0.0f)) return fail(MRCA_ERR_INVALID, "%s: neighbor_dist must be > 0", fn);
+    if (!(p.time_horizon > 0.0f)) return fail(MRCA_ERR_INVALID, "%s: time_horizon must be > 0", fn);
+    if (!(p.time_horizon_obst > 0.0f)) return fail(MRCA_ERR_INVALID, "%s: time_horizon_obst must be > 0", fn);
+    if (!(p.max_speed > 0.0f)) return fail(MRCA_ERR_INVALID, "%s: max_speed must be > 0", fn);
+    if (!(p.obst_dist >= 0.0f && p.obst_dist <= 6.0f)) return fail(MRCA_ERR_INVALID, "%s: obst_dist outside [0, 6]", fn);
     if (!(p.responsibility >= 0.0f && p.responsibility <= 1.0f))
-        return fail(MRCA_ERR_INVALID, "mrca_orca_actions: responsibility outside [0, 1]");
+        return fail(MRCA_ERR_INVALID, "%s: responsibility outside [0, 1]", fn);
     if (p.max_neighbors < 0 || p.max_neighbors > mrca::kOrcaMaxNeighbors)
-        return fail(MRCA_ERR_INVALID, "mrca_orca_actions: max_neighbors %d outside 0..%d", p.max_neighbors, mrca::kOrcaMaxNeighbors);
-    if (!actions_dev) return fail(MRCA_ERR_INVALID, "mrca_orca_actions: actions_dev is NULL");
-    if (reinterpret_cast<uintptr_t>(actions_dev) % 8) return fail(MRCA_ERR_INVALID, "mrca_orca_actions: actions_dev must be 8-byte aligned");
-    if (reinterpret_cast<uintptr_t>(vel_dev) % 4) return fail(MRCA_ERR_INVALID, "mrca_orca_actions: vel_dev must be 4-byte aligned");
+        return fail(MRCA_ERR_INVALID, "%s: max_neighbors %d outside 0..%d", fn, p.max_neighbors, mrca::kOrcaMaxNeighbors);
+    if (!actions_dev) return fail(MRCA_ERR_INVALID, "%s: actions_dev is NULL", fn);
+    if (reinterpret_cast<uintptr_t>(actions_dev) % 8) return fail(MRCA_ERR_INVALID, "%s: actions_dev must be 8-byte aligned", fn);
+    if (reinterpret_cast<uintptr_t>(vel_dev) % 4) return fail(MRCA_ERR_INVALID, "%s: vel_dev must be 4-byte aligned", fn);
     if (!env) return fail(MRCA_ERR_INVALID, "env is NULL");
+    static_assert(std::is_trivially_copyable<mrca::OrcaParams>::value, "");
+    memcpy(out, &p, sizeof *out);
+    return MRCA_OK;
+}
+
+int mrca_orca_actions(mrca_env* env, const mrca_orca_params* params, const uint8_t* mask_dev, float* actions_dev, float* vel_dev,
+                      void* stream) {
+    mrca::OrcaParams q;
+    if (int rc = orca_validate("mrca_orca_actions", env, params, actions_dev, vel_dev, &q)) return rc;
     if (env->cfg.robots_per_world > mrca::kOrcaMaxRobots)
         return fail(MRCA_ERR_UNSUPPORTED, "mrca_orca_actions: robots_per_world %d > %d", env->cfg.robots_per_world, mrca::kOrcaMaxRobots);
     DeviceGuard guard(env->cfg.device);
-    mrca::OrcaParams q;
-    static_assert(std::is_trivially_copyable<mrca::OrcaParams>::value, "");
-    memcpy(&q, &p, sizeof q);
     mrca::launch_orca(env->view, q, mask_dev, actions_dev, vel_dev, static_cast<hipStream_t>(stream));
+    HIP_TRY(hipGetLastError());
+    return MRCA_OK;
+}
+
+int mrca_orca_actions_any(mrca_env* env, const mrca_orca_params* params, const uint8_t* mask_dev, float* actions_dev,
+                          float* vel_dev, void* stream) {
+    mrca::OrcaParams q;
+    if (int rc = orca_validate("mrca_orca_actions_any", env, params, actions_dev, vel_dev, &q)) return rc;
+    const bool big = env->cfg.robots_per_world > mrca::kOrcaMaxRobots;
+    if (big && mrca::orca_rings(q.neighbor_dist) == 0)
+        return fail(MRCA_ERR_UNSUPPORTED, "mrca_orca_actions_any: neighbor_dist %g > 19.3 with robots_per_world %d > %d (the search "
+                                          "looks at three rings of 6.5 m cells at most)",
+                    (double)q.neighbor_dist, env->cfg.robots_per_world, mrca::kOrcaMaxRobots);
+    if (big && !env->lidar_hash_current)
+        return fail(MRCA_ERR_INVALID, "mrca_orca_actions_any: the lidar hash does not describe the current poses -- call "
+                                      "mrca_observe_worlds (after mrca_move_worlds) or mrca_reset first (robots_per_world %d > %d)",
+                    env->cfg.robots_per_world, mrca::kOrcaMaxRobots);
+    DeviceGuard guard(env->cfg.device);
+    if (big) mrca::launch_orca_big(env->view, q, mask_dev, actions_dev, vel_dev, static_cast<hipStream_t>(stream));
+    else mrca::launch_orca(env->view, q, mask_dev, actions_dev, vel_dev, static_cast<hipStream_t>(stream));
     HIP_TRY(hipGetLastError());
     return MRCA_OK;
 }
@@ -880,6 +918,9 @@ static int step_impl(mrca_env* env, const float* actions_dev, int32_t first, int
                      int32_t world_first = 0, int32_t world_count = -1, int phases = kPhaseMove | kPhaseObserve) {
     if (!env) return fail(MRCA_ERR_INVALID, "env is NULL");
     if ((phases & kPhaseMove) && !actions_dev) return fail(MRCA_ERR_INVALID, "actions_dev is NULL");
+    if ((phases & kPhaseMove) && env->view.big && env->lidar_counts_pending)
+        return fail(MRCA_ERR_INVALID, "mrca_move_worlds twice without mrca_observe_worlds in between (robots_per_world > 64: the "
+                                      "observe phase consumes what the move phase counted)");
     if (first < 0 || count < 0 || first + count > env->view.N)
         return fail(MRCA_ERR_INVALID, "ray-cast slice [%d, %d) outside [0, %d)", first, first + count, env->view.N);
     if (world_count < 0) world_count = env->view.W;
@@ -892,9 +933,16 @@ static int step_impl(mrca_env* env, const float* actions_dev, int32_t first, int
     env->last_ray_count = count;
     // timing: the launches' own begin / end stamps (hipExtLaunchKernel), not event records around them
     const Event* ev = rec ? &env->ev[env->ev_used] : nullptr;
-    if (phases & kPhaseMove) mrca::launch_move(v, actions_dev, s, rec ? ev[0].get() : nullptr, rec ? ev[1].get() : nullptr);
+    if (phases & kPhaseMove) {
+        mrca::launch_move(v, actions_dev, s, rec ? ev[0].get() : nullptr, rec ? ev[1].get() : nullptr);
+        env->lidar_hash_current = false;           // (big worlds: the poses have moved on, bw_finish_kernel has counted them)
+        env->lidar_counts_pending = env->view.big;
+    }
     if (phases & kPhaseObserve) {
-        mrca::launch_lidar_grid(v, /*counted=*/1, s);
+        // (an observe phase on its own with no move phase before it counts the robots itself)
+        mrca::launch_lidar_grid(v, /*counted=*/env->view.big && !env->lidar_counts_pending ? 0 : 1, s);
+        env->lidar_hash_current = true;
+        env->lidar_counts_pending = false;
         mrca::launch_raycast(observing(env, v), /*only_fresh=*/0, s, rec ? ev[2].get() : nullptr, rec ? ev[3].get() : nullptr);
     }
     if (rec) env->ev_used += 4;
@@ -914,8 +962,10 @@ static int worlds_impl(mrca_env* env, const float* actions_dev, int32_t first_wo
     if (!env) return fail(MRCA_ERR_INVALID, "env is NULL");
     if (first_world < 0 || num_worlds < 0 || first_world + num_worlds > env->view.W)
         return fail(MRCA_ERR_INVALID, "world range [%d, %d) outside [0, %d)", first_world, first_world + num_worlds, env->view.W);
-    if (env->view.big && (first_world != 0 || num_worlds != env->view.W || phases != (kPhaseMove | kPhaseObserve)))
-        return fail(MRCA_ERR_UNSUPPORTED, "a part of the worlds / of the tick with robots_per_world > 64");
+    // (the two phases one by one are the same launches as the whole tick, for ALL worlds: mrca_orca_actions_any's contract
+    // about the lidar hash is stated and tested between them)
+    if (env->view.big && (first_world != 0 || num_worlds != env->view.W))
+        return fail(MRCA_ERR_UNSUPPORTED, "a part of the worlds with robots_per_world > 64");
     const int32_t R = env->view.R;
     return step_impl(env, actions_dev, first_world * R, num_worlds * R, stream, first_world, num_worlds, phases);
 }

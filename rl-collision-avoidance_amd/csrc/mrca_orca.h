@@ -11,4 +11,9 @@ namespace mrca {
 // robots: a world's robots are the lanes of a wavefront.  Arguments are the ABI's, already validated.
 void launch_orca(const EnvView& e, const OrcaParams& p, const uint8_t* mask, float* actions, float* vel, hipStream_t s);
 
+// The same for worlds of MORE than kOrcaMaxRobots robots (mrca_orca_actions_any): a robot's candidates come from the env's
+// lidar hash (e.bw_lstart / bw_lsorted), which must describe the poses as they stand on `s`, and orca_rings(p.neighbor_dist)
+// must not be 0.  ONE launch, one wavefront per robot; reads e (the hash included), writes none of it.
+void launch_orca_big(const EnvView& e, const OrcaParams& p, const uint8_t* mask, float* actions, float* vel, hipStream_t s);
+
 }  // namespace mrca

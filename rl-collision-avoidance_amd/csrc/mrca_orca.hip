@@ -8,7 +8,14 @@
 // each lane clips by its own line, the interval's ends are a wave maximum / minimum, the two ways to fail are ballots.
 // A lane per robot would serialise about 26 x 26 clips per lane and could not read the scan row coalesced.
 // No atomics, no LDS: every exchange between lanes is a shuffle.
+//
+// Who a robot's neighbours are is the one part that depends on the world's size.  Up to 64 robots: every lane j < R is robot j
+// (orca_kernel<false>).  More (mrca_orca_actions_any, orca_kernel<true>): the candidates come from the env's lidar hash, 64 at a time,
+// and the best max_neighbors keys stay in registers (hashed_neighbours); from "lane 16 + r holds neighbour r" on it is the
+// same code.
 #include "mrca_orca.h"
+
+#include <type_traits>
 
 namespace mrca {
 
@@ -83,8 +90,114 @@ __device__ int lp2_wave(const OrcaLine& line, bool valid, int lane, float max_sp
     }
 }
 
+// Worlds of more than kOrcaMaxRobots robots: the lidar hash of the env (EnvView's bw_lstart / bw_lsorted / bw_lmask, built over
+// the CURRENT poses) and g = orca_rings(neighbor_dist)
+struct OrcaHash {
+    const int32_t* lstart;
+    const int32_t* lsorted;
+    int32_t lmask, rings;
+};
+
+using Key = unsigned long long;
+
+// forward permute: lane dest[l] receives v of lane l (the highest such l where several send to one lane); a lane nobody sends
+// to receives kOrcaNoKey -- the complement travels, and what ds_permute leaves in a lane without a sender is 0.
+// Every lane of the wave takes part.
+__device__ __forceinline__ Key push_key(Key v, int dest) {
+    const Key t = ~v;
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_ds_permute(dest << 2, (int)(uint32_t)t);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_ds_permute(dest << 2, (int)(uint32_t)(t >> 32));
+    return ~(((Key)hi << 32) | lo);
+}
+
+// The kept neighbours of robot n (at (px, py) in `world`) of a world of ANY size, from the lidar hash: on return lane r < the
+// count holds the key of the neighbour of rank r (orca_key: index in the env), every other lane kOrcaNoKey.  What
+// orca_neighbours_hashed (mrca_orca_device.h) states, with the wave doing the work:
+//   lanes 0 .. (2g+1)^2 - 1 fetch the bucket range of "their" cell in one round trip and a prefix sum over the wave makes the
+//   ranges ONE list (the ray cast's big_chunk does this for nine lanes);
+//   the list streams through the wave 64 entries at a time: a lane finds the cell its entry belongs to (a binary search over
+//   the prefix sums), loads the candidate's pose once, applies the cell / world / self / distance filters and forms its key;
+//   the best max_neighbors keys so far stay in registers, sorted, one per lane.  A chunk merges into them BY RANK: a key's
+//   place in the union is the number of keys before it (the chunk's by a loop over its candidates, the kept ones by a binary
+//   search since they are sorted), and every key is pushed to the lane of its rank.  Keys are totally ordered (distinct
+//   indices), so ranks are distinct and the order in which the hash lists the robots cannot show.  A chunk key that is not
+//   before the worst kept key of a full list is dropped before it is ranked: in a jam most chunks add little.
+__device__ __forceinline__ Key hashed_neighbours(const OrcaArgs& a, const OrcaHash hsh, int lane, int n, int world, float px, float py) {
+    const OrcaParams& q = a.p;
+    const int g = hsh.rings, side = 2 * g + 1, K = q.max_neighbors;
+    const int icx = hash_cell_coord(px, kLidarCell), icy = hash_cell_coord(py, kLidarCell);
+    int cell_start = 0, cell_count = 0;
+    if (lane < side * side) {                // (at most 49 cells)
+        const uint32_t h = hash_cell(icx + lane % side - g, icy + lane / side - g, world) & (uint32_t)hsh.lmask;
+        cell_start = hsh.lstart[h];
+        cell_count = hsh.lstart[h + 1] - cell_start;
+    }
+    int cell_end = cell_count;               // inclusive prefix sum (lanes without a cell hold the total)
+#pragma unroll
+    for (int d = 1; d < kWave; d <<= 1) {
+        const int up = __shfl_up(cell_end, d, kWave);
+        if (lane >= d) cell_end += up;
+    }
+    const int total = __shfl(cell_end, kWave - 1);
+    const float nd2 = q.neighbor_dist * q.neighbor_dist;
+    Key best = kOrcaNoKey;
+    for (int off = 0; off < total && K > 0; off += kWave) {
+        const int entry = off + lane;
+        const bool in = entry < total;
+        int cq = 0;                          // the entry's cell: the number of cells that end at or before it (< 64 while `in`)
+#pragma unroll
+        for (int step = kWave / 2; step > 0; step >>= 1) {
+            const int end = __shfl(cell_end, cq + step - 1);
+            if (end <= entry) cq += step;
+        }
+        cq = in ? cq : 0;
+        const int qx = icx + cq % side - g, qy = icy + cq / side - g;
+        const int idx = __shfl(cell_start, cq) + (entry - (__shfl(cell_end, cq) - __shfl(cell_count, cq)));
+        int j = -1;
+        if (in && (unsigned)idx < (unsigned)a.N) j = hsh.lsorted[idx];
+        Key key = kOrcaNoKey;
+        if ((unsigned)j < (unsigned)a.N && j != n && j / a.R == world) {
+            const float xj = a.pose[3 * (size_t)j], yj = a.pose[3 * (size_t)j + 1];
+            // a bucket may hold other cells and other worlds, and may serve two of the cells asked for: a robot counts for
+            // the cell it really is in
+            if (hash_cell_coord(xj, kLidarCell) == qx && hash_cell_coord(yj, kLidarCell) == qy) {
+                const float d2 = orca_dist2(px, py, xj, yj);
+                if (d2 < nd2) key = orca_key(d2, j);
+            }
+        }
+        const Key worst = __shfl(best, K - 1);           // kOrcaNoKey while the list is not full
+        const unsigned long long cands = __ballot(key < worst);
+        if (!cands) continue;
+        if (!(key < worst)) key = kOrcaNoKey;
+        int before_best = 0, before_key = 0;             // chunk keys before this lane's kept key / before its chunk key
+        for (unsigned long long m = cands; m; m &= m - 1) {
+            const Key ck = __shfl(key, __ffsll((long long)m) - 1);
+            before_best += ck < best ? 1 : 0;
+            before_key += ck < key ? 1 : 0;
+        }
+        int pos = 0;                                     // kept keys before this lane's chunk key
+#pragma unroll
+        for (int step = kWave / 2; step > 0; step >>= 1) {
+            const Key bk = __shfl(best, pos + step - 1);
+            if (bk < key) pos += step;
+        }
+        const int to_best = lane + before_best, to_key = pos + before_key;
+        // lane 63 is nobody's place (K <= 48): what falls off the list, and every lane without a key, is sent there
+        const Key kept = push_key(best, best != kOrcaNoKey && to_best < K ? to_best : kWave - 1);
+        const Key came = push_key(key, key != kOrcaNoKey && to_key < K ? to_key : kWave - 1);
+        best = kept < came ? kept : came;                // (a place receives one key: ranks are distinct)
+        if (lane >= K) best = kOrcaNoKey;
+    }
+    return best;
+}
+
+struct OrcaNoHash {};
+
+// BIG: worlds of more than kOrcaMaxRobots robots (`hsh` is their lidar hash); otherwise `hsh` is empty and the kernel is, but for
+// its name, the one that worlds of up to 64 robots have always run
+template <bool BIG>
 __global__ __launch_bounds__(kBlock) void orca_kernel(const OrcaArgs a, const uint8_t* __restrict__ mask, float* __restrict__ actions,
-                                                      float* __restrict__ vel) {
+                                                      float* __restrict__ vel, const std::conditional_t<BIG, OrcaHash, OrcaNoHash> hsh) {
     const int lane = threadIdx.x & (kWave - 1);
     const int n = blockIdx.x * kRobotsPerBlock + (threadIdx.x >> 6);
     if (n >= a.N) return;                    // (wave-uniform, like every branch around a shuffle below)
@@ -93,15 +206,34 @@ __global__ __launch_bounds__(kBlock) void orca_kernel(const OrcaArgs a, const ui
     const int world = n / a.R;
     const int base = world * a.R, local = n - base;
 
-    // ---- every lane j < R: robot j of the world (its own robot among them)
-    const int j = lane < a.R ? lane : local;
-    const float jx = a.pose[3 * (size_t)(base + j)], jy = a.pose[3 * (size_t)(base + j) + 1];
-    const float4 jh = a.head[base + j];      // (sin, cos, ...)
-    const float jsp = a.speed_gt[2 * (size_t)(base + j)];
-    const float jvx = jsp * jh.y, jvy = jsp * jh.x;
-    const float px = __shfl(jx, local), py = __shfl(jy, local);
-    const float s = __shfl(jh.x, local), c = __shfl(jh.y, local);
-    const float vx = __shfl(jvx, local), vy = __shfl(jvy, local);
+    float jx = 0.0f, jy = 0.0f, jvx = 0.0f, jvy = 0.0f;
+    float px, py, s, c, vx, vy;
+    if constexpr (!BIG) {
+        // ---- every lane j < R: robot j of the world (its own robot among them)
+        const int j = lane < a.R ? lane : local;
+        jx = a.pose[3 * (size_t)(base + j)];
+        jy = a.pose[3 * (size_t)(base + j) + 1];
+        const float4 jh = a.head[base + j];      // (sin, cos, ...)
+        const float jsp = a.speed_gt[2 * (size_t)(base + j)];
+        jvx = jsp * jh.y;
+        jvy = jsp * jh.x;
+        px = __shfl(jx, local);
+        py = __shfl(jy, local);
+        s = __shfl(jh.x, local);
+        c = __shfl(jh.y, local);
+        vx = __shfl(jvx, local);
+        vy = __shfl(jvy, local);
+    } else {
+        // ---- the robot's own record, loaded directly (wave-uniform)
+        px = a.pose[3 * (size_t)n];
+        py = a.pose[3 * (size_t)n + 1];
+        const float4 h = a.head[n];
+        const float sp = a.speed_gt[2 * (size_t)n];
+        s = h.x;
+        c = h.y;
+        vx = sp * h.y;
+        vy = sp * h.x;
+    }
 
     float ox, oy;
     orca_pref_velocity(q, (uint32_t)n, a.key0, a.key1, px, py, a.goal[2 * (size_t)n], a.goal[2 * (size_t)n + 1], &ox, &oy);
@@ -134,23 +266,41 @@ __global__ __launch_bounds__(kBlock) void orca_kernel(const OrcaArgs a, const ui
     const float sec_r = __shfl(best_r, (4 * lane) & (kWave - 1));
     const int sec_b = __shfl(best_b, (4 * lane) & (kWave - 1));
 
-    // ---- the neighbours: rank among the candidates by (dist2, index), then lane 16 + rank fetches its neighbour
-    const float ddx = jx - px, ddy = jy - py;
-    const float d2 = dot2(ddx, ddy, ddx, ddy);
-    const bool cand = lane < a.R && lane != local && d2 < q.neighbor_dist * q.neighbor_dist;
-    const unsigned long long cands = __ballot(cand);
-    int rank = 0;
-    for (unsigned long long m = cands; m; m &= m - 1) {
-        const int o = __ffsll((long long)m) - 1;
-        rank += orca_key_before(__shfl(d2, o), o, d2, lane) ? 1 : 0;
-    }
     int src = -1;
-    for (unsigned long long m = __ballot(cand && rank < q.max_neighbors); m; m &= m - 1) {
-        const int o = __ffsll((long long)m) - 1;
-        if (lane == kOrcaSectors + __shfl(rank, o)) src = o;
+    float nbx, nby, nvx, nvy;
+    if constexpr (!BIG) {
+        // ---- the neighbours: rank among the candidates by (dist2, index), then lane 16 + rank fetches its neighbour
+        const float ddx = jx - px, ddy = jy - py;
+        const float d2 = dot2(ddx, ddy, ddx, ddy);
+        const bool cand = lane < a.R && lane != local && d2 < q.neighbor_dist * q.neighbor_dist;
+        const unsigned long long cands = __ballot(cand);
+        int rank = 0;
+        for (unsigned long long m = cands; m; m &= m - 1) {
+            const int o = __ffsll((long long)m) - 1;
+            rank += orca_key_before(__shfl(d2, o), o, d2, lane) ? 1 : 0;
+        }
+        for (unsigned long long m = __ballot(cand && rank < q.max_neighbors); m; m &= m - 1) {
+            const int o = __ffsll((long long)m) - 1;
+            if (lane == kOrcaSectors + __shfl(rank, o)) src = o;
+        }
+        const int from = src < 0 ? 0 : src;
+        nbx = __shfl(jx, from);
+        nby = __shfl(jy, from);
+        nvx = __shfl(jvx, from);
+        nvy = __shfl(jvy, from);
+    } else {
+        // ---- the neighbours from the lidar hash; lane 16 + rank takes the neighbour of that rank and loads its record once
+        const Key best = hashed_neighbours(a, hsh, lane, n, world, px, py);
+        const Key mine = __shfl(best, (lane - kOrcaSectors) & (kWave - 1));
+        if (lane >= kOrcaSectors && mine != kOrcaNoKey) src = orca_key_index(mine);
+        const int from = src < 0 ? n : src;
+        nbx = a.pose[3 * (size_t)from];
+        nby = a.pose[3 * (size_t)from + 1];
+        const float4 h = a.head[from];
+        const float sp = a.speed_gt[2 * (size_t)from];
+        nvx = sp * h.y;
+        nvy = sp * h.x;
     }
-    const int from = src < 0 ? 0 : src;
-    const float nbx = __shfl(jx, from), nby = __shfl(jy, from), nvx = __shfl(jvx, from), nvy = __shfl(jvy, from);
 
     // ---- one constraint per lane
     bool valid;
@@ -209,9 +359,7 @@ __global__ __launch_bounds__(kBlock) void orca_kernel(const OrcaArgs a, const ui
     }
 }
 
-}  // namespace
-
-void launch_orca(const EnvView& e, const OrcaParams& p, const uint8_t* mask, float* actions, float* vel, hipStream_t s) {
+OrcaArgs orca_args(const EnvView& e, const OrcaParams& p) {
     OrcaArgs a;
     a.N = e.N; a.R = e.R; a.B = e.B; a.F = e.F;
     a.key0 = e.key0; a.key1 = e.key1;
@@ -219,7 +367,22 @@ void launch_orca(const EnvView& e, const OrcaParams& p, const uint8_t* mask, flo
     a.scan_ring = e.scan_ring; a.ring_head = e.ring_head; a.hit_bits = e.hit_bits;
     a.beam_cos = e.beam_cos; a.beam_sin = e.beam_sin;
     a.p = p;
-    hipLaunchKernelGGL(orca_kernel, dim3((e.N + kRobotsPerBlock - 1) / kRobotsPerBlock), dim3(kBlock), 0, s, a, mask, actions, vel);
+    return a;
+}
+
+}  // namespace
+
+void launch_orca(const EnvView& e, const OrcaParams& p, const uint8_t* mask, float* actions, float* vel, hipStream_t s) {
+    const OrcaArgs a = orca_args(e, p);
+    hipLaunchKernelGGL(orca_kernel<false>, dim3((e.N + kRobotsPerBlock - 1) / kRobotsPerBlock), dim3(kBlock), 0, s, a, mask, actions, vel,
+                       OrcaNoHash{});
+}
+
+void launch_orca_big(const EnvView& e, const OrcaParams& p, const uint8_t* mask, float* actions, float* vel, hipStream_t s) {
+    const OrcaArgs a = orca_args(e, p);
+    const OrcaHash hsh{e.bw_lstart, e.bw_lsorted, e.bw_lmask, orca_rings(p.neighbor_dist)};
+    hipLaunchKernelGGL(orca_kernel<true>, dim3((e.N + kRobotsPerBlock - 1) / kRobotsPerBlock), dim3(kBlock), 0, s, a, mask, actions, vel,
+                       hsh);
 }
 
 }  // namespace mrca

@@ -28,7 +28,7 @@ struct OrcaParams {
 constexpr int kOrcaSectors = 16;          // static constraints: the nearest wall return of each sixteenth of the scan
 constexpr int kOrcaMaxNeighbors = 48;     // 16 + 48 = 64 constraints: one per lane of a wavefront
 constexpr int kOrcaMaxLines = kOrcaSectors + kOrcaMaxNeighbors;
-constexpr int kOrcaMaxRobots = 64;        // robots per world the controller supports
+constexpr int kOrcaMaxRobots = 64;        // robots per world whose robots are the lanes of ONE wavefront (more: the lidar hash)
 constexpr float kOrcaEps = 1e-5f;
 constexpr float kOrcaStill = 1e-4f;       // a chosen velocity slower than this is the command (0, 0)
 constexpr uint32_t kStreamOrca = 2u;      // Philox stream of the per-robot jitter angle (0 / 1: kStreamPose / kStreamGoal)
@@ -321,23 +321,54 @@ MRCA_HD void orca_sectors(const float* ranges, const unsigned long long* hits, i
     }
 }
 
-// the kept neighbours of robot `local` among the R robots of its world (pose_xy[R][2]), nearest first -> their count
-MRCA_HD int orca_neighbours(const float* pose_xy, int R, int local, float neighbor_dist, int max_neighbors, int* out) {
+// ---- the neighbour selection.  The key of a candidate is (dist2, index) in the order of orca_key_before, packed into one
+// unsigned 64-bit number: dist2 >= 0, and the bits of a non-negative float order as an unsigned integer, so
+// (bits(dist2) << 32) | index compares like the pair in ONE comparison and a tie goes to the lower index by itself.
+// dist2 = dot2(dx, dy, dx, dy) is a sum of two squares: each square is >= +0 and (+0) + (+0) = +0, so -0.0 (whose bits would
+// sort above every positive number) cannot arise; a NaN never passes `dist2 < nd2` and so never gets a key.
+constexpr unsigned long long kOrcaNoKey = ~0ull;     // sorts behind every key (its dist2 half is a NaN pattern)
+
+MRCA_HD unsigned long long orca_key(float d2, int j) {
+    uint32_t b;
+    __builtin_memcpy(&b, &d2, 4);
+    return ((unsigned long long)b << 32) | (uint32_t)j;
+}
+MRCA_HD int orca_key_index(unsigned long long key) { return (int)(uint32_t)key; }
+
+// dist2 of robot j from (px, py): every operation rounded on its own
+MRCA_HD float orca_dist2(float px, float py, float xj, float yj) {
+    const float dx = xj - px, dy = yj - py;
+    return dot2(dx, dy, dx, dy);
+}
+
+// Worlds of more than kOrcaMaxRobots robots find their candidates through the lidar hash (mrca_device.h: kLidarCell = 6.5 m
+// cells): the (2g + 1)^2 cells around the robot's own.  -> g for a neighbor_dist, 0: too large for three rings.
+// Why g * 6.5 - 0.2: two robots whose computed dist2 is below nd^2 are at most nd (1 + 2^-22) apart along x, so their cell
+// quotients x / 6.5 differ by at most nd / 6.5 -- as real numbers.  hash_cell_coord computes x * fl(1 / 6.5): the rounded
+// reciprocal and the rounded product are each off by at most half an ulp of the quotient.  At |x| = 2.5e5 m (the circle of
+// 500 000 robots) the quotient is 38 462, its ulp 2^-8 cell = 0.025 m, so each computed quotient is off by at most 0.025 m
+// and their difference by at most 0.05 m (about 0.03 m for one ulp, as the 6.3 / 6.5 pair of the ray cast allows for).
+// nd <= g * 6.5 - 0.2 keeps the computed quotients within g of each other with 0.15 m to spare, and two numbers at most g
+// apart have floors at most g apart: every neighbour lies in one of the (2g + 1)^2 cells.
+constexpr int kOrcaMaxRings = 3;
+MRCA_HD int orca_rings(float neighbor_dist) {
+    return neighbor_dist <= 6.3f ? 1 : (neighbor_dist <= 12.8f ? 2 : (neighbor_dist <= 19.3f ? 3 : 0));
+}
+
+// the kept neighbours of robot `local` among R robots whose (x, y) are pts[stride * j], pts[stride * j + 1], nearest first
+// -> their count.  Any R: nothing is stored per robot, a candidate's rank is counted against all others.
+MRCA_HD int orca_neighbours_strided(const float* pts, int stride, int R, int local, float neighbor_dist, int max_neighbors, int* out) {
     const float nd2 = neighbor_dist * neighbor_dist;
-    const float px = pose_xy[2 * local], py = pose_xy[2 * local + 1];
-    float d2[kOrcaMaxRobots];
-    bool cand[kOrcaMaxRobots];
-    for (int j = 0; j < R; ++j) {
-        const float dx = pose_xy[2 * j] - px, dy = pose_xy[2 * j + 1] - py;
-        d2[j] = dot2(dx, dy, dx, dy);
-        cand[j] = j != local && d2[j] < nd2;
-    }
+    const float px = pts[stride * local], py = pts[stride * local + 1];
     int n = 0;
     for (int j = 0; j < R; ++j) {
-        if (!cand[j]) continue;
+        const float dj = orca_dist2(px, py, pts[stride * j], pts[stride * j + 1]);
+        if (j == local || !(dj < nd2)) continue;
         int rank = 0;
-        for (int c = 0; c < R; ++c)
-            if (cand[c] && orca_key_before(d2[c], c, d2[j], j)) ++rank;
+        for (int c = 0; c < R && rank < max_neighbors; ++c) {
+            const float dc = orca_dist2(px, py, pts[stride * c], pts[stride * c + 1]);
+            if (c != local && dc < nd2 && orca_key_before(dc, c, dj, j)) ++rank;
+        }
         if (rank < max_neighbors) {
             out[rank] = j;
             ++n;
@@ -346,13 +377,59 @@ MRCA_HD int orca_neighbours(const float* pose_xy, int R, int local, float neighb
     return n;
 }
 
-// The whole rule for robot `local` of one world.  pose[R][3], sincos[R][2] = the head records' (sin, cos), speed_gt[R][2],
-// goal = this robot's, ranges / hits = its newest scan row and hit words, gid = its index in the env.
+// the kept neighbours of robot `local` among the R robots of its world (pose_xy[R][2]), nearest first -> their count
+MRCA_HD int orca_neighbours(const float* pose_xy, int R, int local, float neighbor_dist, int max_neighbors, int* out) {
+    return orca_neighbours_strided(pose_xy, 2, R, local, neighbor_dist, max_neighbors, out);
+}
+
+// The same list from the lidar hash of an env (lstart[lmask + 2], lsorted[N]: the counting sort of the env's robots by
+// hash_bucket(x, y, kLidarCell, world, lmask), in ANY order inside a bucket): robot `n` (index in the env, pose[N][3]) of
+// `world`, whose robots are [world * R, (world + 1) * R).  -> the count; out: indices inside the world, nearest first.
+// It walks the (2g + 1)^2 cells around n's own, g = orca_rings(neighbor_dist) (which must not be 0).  Buckets alias: several
+// cells and several worlds may share one, and one bucket may serve two of the cells asked for -- a robot counts only in the
+// cell and the world it really is in (the ray cast's rule, mrca_raycast_body.h), so nobody is listed twice and nobody is lost.
+// The keys are totally ordered, so the order in which the candidates are met cannot show.  The kernel (mrca_orca.hip) does the
+// same with a wavefront; this is the statement it is held to.
+MRCA_HD int orca_neighbours_hashed(const int32_t* lstart, const int32_t* lsorted, int lmask, const float* pose, int world, int R, int n,
+                                   float neighbor_dist, int max_neighbors, int* out) {
+    const int g = orca_rings(neighbor_dist);
+    const float nd2 = neighbor_dist * neighbor_dist;
+    const float px = pose[3 * (size_t)n], py = pose[3 * (size_t)n + 1];
+    const int icx = hash_cell_coord(px, kLidarCell), icy = hash_cell_coord(py, kLidarCell);
+    unsigned long long best[kOrcaMaxNeighbors];
+    int kept = 0;
+    for (int qy = icy - g; qy <= icy + g; ++qy)
+        for (int qx = icx - g; qx <= icx + g; ++qx) {
+            const uint32_t h = hash_cell(qx, qy, world) & (uint32_t)lmask;
+            for (int k = lstart[h]; k < lstart[h + 1]; ++k) {
+                const int j = lsorted[k];
+                if (j == n || j / R != world) continue;
+                const float xj = pose[3 * (size_t)j], yj = pose[3 * (size_t)j + 1];
+                if (hash_cell_coord(xj, kLidarCell) != qx || hash_cell_coord(yj, kLidarCell) != qy) continue;
+                const float d2 = orca_dist2(px, py, xj, yj);
+                if (!(d2 < nd2)) continue;
+                const unsigned long long key = orca_key(d2, j);
+                int at = kept;                        // insertion into the sorted best-so-far
+                while (at > 0 && key < best[at - 1]) --at;
+                if (at >= max_neighbors) continue;
+                const int last = kept < max_neighbors ? kept : max_neighbors - 1;
+                for (int m = last; m > at; --m) best[m] = best[m - 1];
+                best[at] = key;
+                if (kept < max_neighbors) ++kept;
+            }
+        }
+    for (int k = 0; k < kept; ++k) out[k] = orca_key_index(best[k]) - world * R;
+    return kept;
+}
+
+// The rule for robot `local` of one world GIVEN its kept neighbours nb[0 .. kept) (indices inside the world, nearest first).
+// pose[R][3], sincos[R][2] = the head records' (sin, cos), speed_gt[R][2], goal = this robot's, ranges / hits = its newest scan
+// row and hit words, gid = its index in the env.
 // -> (v, omega) in cmd, the holonomic velocity in vel; lines_out / counts (or nullptr): the constraints, [n, n_static]
-MRCA_HD void orca_robot(const OrcaParams& q, int R, int local, uint32_t gid, uint32_t k0, uint32_t k1, const float* pose,
-                        const float* sincos, const float* speed_gt, const float* goal, const float* ranges,
-                        const unsigned long long* hits, int beams, const float* beam_cos, const float* beam_sin, float* cmd,
-                        float* vel, OrcaLine* lines_out, int* counts, int* diag) {
+MRCA_HD void orca_robot_with(const OrcaParams& q, const int* nb, int kept, int local, uint32_t gid, uint32_t k0, uint32_t k1,
+                             const float* pose, const float* sincos, const float* speed_gt, const float* goal, const float* ranges,
+                             const unsigned long long* hits, int beams, const float* beam_cos, const float* beam_sin, float* cmd,
+                             float* vel, OrcaLine* lines_out, int* counts, int* diag) {
     OrcaLine lines[kOrcaMaxLines];
     const float px = pose[3 * local], py = pose[3 * local + 1];
     const float s = sincos[2 * local], c = sincos[2 * local + 1];
@@ -372,13 +449,6 @@ MRCA_HD void orca_robot(const OrcaParams& q, int R, int local, uint32_t gid, uin
         orca_constraint(rx, ry, vx, vy, vx, vy, q.radius, inv_to, 1.0f, &lines[n++]);
     }
     const int n_static = n;
-    float xy[2 * kOrcaMaxRobots];
-    for (int j = 0; j < R; ++j) {
-        xy[2 * j] = pose[3 * j];
-        xy[2 * j + 1] = pose[3 * j + 1];
-    }
-    int nb[kOrcaMaxNeighbors];
-    const int kept = orca_neighbours(xy, R, local, q.neighbor_dist, q.max_neighbors, nb);
     const float inv_t = 1.0f / q.time_horizon;
     for (int k = 0; k < kept; ++k) {
         const int j = nb[k];
@@ -398,6 +468,17 @@ MRCA_HD void orca_robot(const OrcaParams& q, int R, int local, uint32_t gid, uin
         counts[0] = n;
         counts[1] = n_static;
     }
+}
+
+// The whole rule for robot `local` of one world: its neighbours among the world's R robots, then orca_robot_with.
+MRCA_HD void orca_robot(const OrcaParams& q, int R, int local, uint32_t gid, uint32_t k0, uint32_t k1, const float* pose,
+                        const float* sincos, const float* speed_gt, const float* goal, const float* ranges,
+                        const unsigned long long* hits, int beams, const float* beam_cos, const float* beam_sin, float* cmd,
+                        float* vel, OrcaLine* lines_out, int* counts, int* diag) {
+    int nb[kOrcaMaxNeighbors];
+    const int kept = orca_neighbours_strided(pose, 3, R, local, q.neighbor_dist, q.max_neighbors, nb);
+    orca_robot_with(q, nb, kept, local, gid, k0, k1, pose, sincos, speed_gt, goal, ranges, hits, beams, beam_cos, beam_sin, cmd, vel,
+                    lines_out, counts, diag);
 }
 
 }  // namespace mrca

@@ -192,6 +192,11 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--robots", type=int, default=50, help="robots per circle (50 = the reference's table; others: scenario.circle_n)")
     ap.add_argument("--radius", type=float, default=25.0)
+    ap.add_argument("--one-circle", type=int, default=None, metavar="N",
+                    help="ONE circle of N robots in an open world (scenario.circle_big: the radius grows with N so that the "
+                         "spacing along the circle stays --spacing); excludes --circles / --robots / --radius")
+    ap.add_argument("--spacing", type=float, default=None, metavar="S",
+                    help="with --one-circle: metres between neighbours along the circle (default: the reference's 3.14)")
     ap.add_argument("--perturb", default=None, help="'dxy,dth': start every robot U(-dxy, dxy) m / U(-dth, dth) rad off its table "
                                                      "pose (Philox, seeded by --seed) so that the circles are different scenarios, "
                                                      "e.g. 0.2,0.1; the output carries the mean success rate with a 95 %% interval")
@@ -217,7 +222,17 @@ def main():
     if a.fused_bf16:
         a.fused = True
     from .vec_env import VecStageWorld
-    if a.robots == 50 and a.radius == 25.0:
+    if a.one_circle is None and a.spacing is not None:
+        ap.error("--spacing goes with --one-circle")
+    if a.one_circle is not None:
+        if a.circles != 1 or a.robots != 50 or a.radius != 25.0:
+            ap.error("--one-circle excludes --circles / --robots / --radius")
+        if a.stage_resolution:
+            ap.error("--one-circle runs in an open world: no --stage-resolution")
+        if a.one_circle < 1:
+            ap.error("--one-circle needs at least one robot")
+        sc = scenario.circle_big(a.one_circle, seed=a.seed, spacing=a.spacing)
+    elif a.robots == 50 and a.radius == 25.0:
         sc = scenario.circle(num_worlds=a.circles, seed=a.seed, stage_resolution=a.stage_resolution)
     else:
         grid = scenario.load_map("circle_rink_r0010") if a.stage_resolution else None
@@ -229,11 +244,12 @@ def main():
         fn, name = cnn_policy_fn(pol, fused=a.fused, env=env, fused_bf16=a.fused_bf16), a.policy
     else:
         fn, name = staggered_roundabout_policy(env.N), "staggered-roundabout stand-in (no checkpoint given)"
+    orca_call = "mrca_orca_actions_any" if env.R > 64 else "mrca_orca_actions"
     if a.orca or a.orca_first is not None:
         from .orca import OrcaParams
         params = OrcaParams.from_assignments(a.orca_param)
         if a.orca_first is None:
-            fn, name = orca_policy_fn(env, params), "ORCA baseline (mrca_orca_actions)"
+            fn, name = orca_policy_fn(env, params), f"ORCA baseline ({orca_call})"
         else:
             fn, name = orca_policy_fn(env, params, first=a.orca_first, other=fn), f"ORCA for local index < {a.orca_first}, else {name}"
     perturb = tuple(float(v) for v in a.perturb.split(",")) if a.perturb else None
@@ -251,6 +267,10 @@ def main():
         import dataclasses
         out["orca_params"] = dataclasses.asdict(params)
     out["robots_per_circle"], out["radius_m"] = a.robots, a.radius
+    if a.one_circle is not None:
+        out["one_circle"], out["robots_per_circle"] = a.one_circle, a.one_circle
+        out["radius_m"] = float(max(abs(float(v)) for v in sc.init_table[0][:2]))     # (robot 0 stands at (radius, 0))
+        out["spacing_m"] = 2.0 * math.pi * out["radius_m"] / a.one_circle
     out["perturb_xy_th"], out["seed"], out["stage_resolution"] = perturb, a.seed, bool(a.stage_resolution)
     out["inference_precision"] = ("bf16 (fused bf16 MFMA front end + bf16 fc1)" if a.fused_bf16 else "fp32") if a.policy else None
     print(json.dumps(out))

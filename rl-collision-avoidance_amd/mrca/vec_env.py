@@ -262,13 +262,17 @@ class VecStageWorld:
         env is written -- ``env.step(env.orca_actions())`` is a closed-loop scripted tick.  ``params``: an ``orca.OrcaParams``
         (default: the library's); ``mask``: a uint8[N] tensor, rows with 0 keep what ``out`` holds (so a policy's actions can
         be passed as ``out`` and ORCA overwrites its robots' rows); ``vel``: a float32[N,2] tensor that takes the holonomic
-        velocity chosen."""
+        velocity chosen.
+        Worlds of more than 64 robots (``scenario.circle_big``) go through mrca_orca_actions_any: the same rule with the
+        neighbours found through the env's lidar hash, ``neighbor_dist`` up to 19.3 m; between ``move`` and ``observe`` it
+        raises (the hash describes the poses before the move).  Smaller worlds keep mrca_orca_actions."""
         if out is None:
             out = torch.zeros((self.N, 2), dtype=torch.float32, device=self.device)
         st = None if params is None else params.struct()
-        _lib.check(self.lib.mrca_orca_actions(self._h, None if st is None else C.byref(st), self._ptr(mask, torch.uint8, self.N),
-                                              self._ptr(out, torch.float32, 2 * self.N), self._ptr(vel, torch.float32, 2 * self.N),
-                                              self._stream()), "mrca_orca_actions")
+        name = "mrca_orca_actions_any" if self.R > 64 else "mrca_orca_actions"
+        _lib.check(getattr(self.lib, name)(self._h, None if st is None else C.byref(st), self._ptr(mask, torch.uint8, self.N),
+                                           self._ptr(out, torch.float32, 2 * self.N), self._ptr(vel, torch.float32, 2 * self.N),
+                                           self._stream()), name)
         return out
 
     # ------------------------------------------------------------------ lifecycle
