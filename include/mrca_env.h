@@ -33,7 +33,8 @@
 extern "C" {
 #endif
 
-/* 6, additive: mrca_orca_actions_any (the ORCA baseline on worlds of any size); mrca_move_worlds / mrca_observe_worlds take the
+/* 6, additive: mrca_dwa_actions, mrca_dwa_default_params (a sensor-level DWA baseline beside ORCA).
+ * 6, additive: mrca_orca_actions_any (the ORCA baseline on worlds of any size); mrca_move_worlds / mrca_observe_worlds take the
  * full range of an env with robots_per_world > 64.
  * 6, additive: mrca_lidar_features_bf16 (the bf16 MFMA front end of the opt-in bf16 rollout inference); the opt-in fused bf16
  * update's mrca_lidar_features_bf16_rows, mrca_lidar_features_bf16_backward(_rows, _scratch).
@@ -337,6 +338,46 @@ int mrca_orca_actions(mrca_env* env, const mrca_orca_params* params /* host, NUL
 int mrca_orca_actions_any(mrca_env* env, const mrca_orca_params* params /* host, NULL = defaults */,
                           const uint8_t* mask_dev /* u8[N] or NULL = all */, float* actions_dev /* f32[N,2] */,
                           float* vel_dev /* f32[N,2] or NULL */, void* stream);
+
+/* A second classical baseline on the device, SENSOR-LEVEL where ORCA is agent-level: the dynamic window approach (Fox, Burgard,
+ * Thrun, "The dynamic window approach to collision avoidance", 1997).  Per robot it reads what the policy reads and nothing
+ * else: MRCA_F_LOCAL_GOAL (the goal in the robot's frame), MRCA_F_SPEED (its own command (v0, w0)) and the newest row of
+ * MRCA_F_SCAN_RING (through MRCA_F_RING_HEAD).  MRCA_F_HIT_BITS, poses, MRCA_F_SPEED_GT and the other robots are NOT read: a
+ * return from a robot is an obstacle like a wall, and every obstacle is taken as standing still.
+ *   Within kGoalRadius (0.5 m) of the goal the command is (0, 0), choice -2.  Otherwise the scan is cut into 64 sectors of
+ * beams / 64 beams; a sector's nearest return below min(obst_dist, 6) (the lowest beam among equals, -0.0 counts as 0) is an
+ * obstacle point range * (beam_cos, beam_sin).  The window is v in [max(0, v0 - acc_v dt), min(max_speed, v0 + acc_v dt)] and
+ * omega in [max(-max_omega, w0 - acc_w dt), min(max_omega, w0 + acc_w dt)], dt = 0.1 s (a command outside the rectangle takes
+ * the nearest part of it), sampled nv x nw evenly with both ends (one sample: the upper end); candidate c = i * nw + j.  Each
+ * candidate is rolled out from (0, 0), heading 0, in `steps` explicit Euler sub-steps of horizon / steps (position first, with
+ * the heading at the start of the sub-step, as the env's own move).  clear = sqrt(least squared distance of any sub-step
+ * position to any point) - radius, clear_cap where there is no point; admissible iff clear >= 0.
+ *   score = w_goal (|g| - |g - p_end|) / (max_speed horizon) + w_heading cos(angle between the end heading and g - p_end; 1 at
+ *           the goal itself) + w_clear min(clear, clear_cap) / clear_cap + w_speed v / max_speed.
+ * The admissible candidate of greatest score wins, the lowest c among equals; none admissible: (0, +-max_omega) towards the
+ * goal's side (gy >= 0: +), choice -1.  The rule is csrc/mrca_dwa_device.h, separately rounded fp32 steps in a fixed order: the
+ * output is reproducible bit for bit (tests/dwa_ref.py restates it in NumPy).
+ *   params      host; NULL = mrca_dwa_default_params: radius 0.35, horizon 2, obst_dist 3, clear_cap 1, max_speed 1, max_omega 1,
+ *               acc_v 10, acc_w 20 (the env has no acceleration limit: the window is the whole range), w_goal 1, w_heading 0,
+ *               w_clear 0.2, w_speed 0.3, steps 10, nv 5, nw 21 (profiles/dwa/defaults.txt)
+ *   mask_dev    u8[N] or NULL = all robots
+ *   actions_dev f32[N,2] out, 8-byte aligned; rows whose mask byte is 0 are not touched (nor are their choice / score rows)
+ *   choice_dev  i32[N] or NULL; out: the candidate chosen, -1 (none admissible) or -2 (at the goal)
+ *   score_dev   f32[N] or NULL; out: the chosen candidate's score (0 for choice < 0)
+ * Asynchronous on `stream`, ONE launch (one wavefront per robot, the params travel as kernel arguments); reads the env as it
+ * stands at that point of the stream and writes none of it, so mrca_step with actions_dev can follow on the same stream.  Any
+ * robots_per_world (a robot needs nothing of another: no neighbour search), both lazy_obs values, any beams / frames, exact
+ * and raster collision modes.  Everything is validated before the first HIP call (MRCA_ERR_INVALID): every float finite;
+ * radius, horizon, clear_cap, max_speed, max_omega > 0; max_speed, max_omega <= 1; 0 <= obst_dist <= 6; acc_v, acc_w and the
+ * four weights >= 0; steps 1..64, nv 1..16, nw 1..64; actions_dev not NULL and 8-byte aligned. */
+typedef struct mrca_dwa_params {
+    float radius, horizon, obst_dist, clear_cap, max_speed, max_omega, acc_v, acc_w, w_goal, w_heading, w_clear, w_speed;
+    int32_t steps, nv, nw;
+} mrca_dwa_params;
+int mrca_dwa_default_params(mrca_dwa_params* out);
+int mrca_dwa_actions(mrca_env* env, const mrca_dwa_params* params /* host, NULL = defaults */, const uint8_t* mask_dev,
+                     float* actions_dev /* f32[N,2] */, int32_t* choice_dev /* i32[N] or NULL */,
+                     float* score_dev /* f32[N] or NULL */, void* stream);
 
 /* Synchronises `stream` and reports (then clears) the env's sticky device-side status word: MRCA_OK, or MRCA_ERR_HIP with
  * mrca_last_error() saying what went wrong on the device since the last check.  Today one condition: the ordered

@@ -22,6 +22,7 @@
 #include "mrca_hostutil.h"
 #include "mrca_kernels.h"
 #include "mrca_orca.h"
+#include "mrca_dwa.h"
 #include "mrca_pass_plan.h"
 #include "mrca_render.h"
 #include "mrca_rollout_store.h"
@@ -909,6 +910,67 @@ int mrca_orca_actions_any(mrca_env* env, const mrca_orca_params* params, const u
     DeviceGuard guard(env->cfg.device);
     if (big) mrca::launch_orca_big(env->view, q, mask_dev, actions_dev, vel_dev, static_cast<hipStream_t>(stream));
     else mrca::launch_orca(env->view, q, mask_dev, actions_dev, vel_dev, static_cast<hipStream_t>(stream));
+    HIP_TRY(hipGetLastError());
+    return MRCA_OK;
+}
+
+static_assert(sizeof(mrca_dwa_params) == sizeof(mrca::DwaParams) && offsetof(mrca_dwa_params, steps) == offsetof(mrca::DwaParams, steps) &&
+                  offsetof(mrca_dwa_params, nw) == offsetof(mrca::DwaParams, nw),
+              "mrca_dwa_params and mrca::DwaParams are one layout");
+
+int mrca_dwa_default_params(mrca_dwa_params* out) {
+    if (!out) return fail(MRCA_ERR_INVALID, "mrca_dwa_default_params: out is NULL");
+    out->radius = 0.35f;            // the footprint's half diagonal 0.2907 m + a margin (as the ORCA baseline)
+    out->horizon = 2.0f;            // (horizon, steps, the weights): tuned on the closed-loop gates, profiles/dwa/defaults.txt
+    out->obst_dist = 3.0f;
+    out->clear_cap = 1.0f;
+    out->max_speed = 1.0f;
+    out->max_omega = 1.0f;
+    out->acc_v = 10.0f;             // the env has no acceleration limit: one tick of these reaches the whole range
+    out->acc_w = 20.0f;
+    out->w_goal = 1.0f;
+    out->w_heading = 0.0f;          // (any weight here makes robots that meet head-on stop and face each other)
+    out->w_clear = 0.2f;
+    out->w_speed = 0.3f;
+    out->steps = 10;
+    out->nv = 5;
+    out->nw = 21;
+    return MRCA_OK;
+}
+
+int mrca_dwa_actions(mrca_env* env, const mrca_dwa_params* params, const uint8_t* mask_dev, float* actions_dev, int32_t* choice_dev,
+                     float* score_dev, void* stream) {
+    // everything that can be judged without the env, then the env
+    mrca_dwa_params p;
+    if (params) p = *params;
+    else mrca_dwa_default_params(&p);
+    const float fl[12] = {p.radius, p.horizon, p.obst_dist, p.clear_cap, p.max_speed, p.max_omega, p.acc_v, p.acc_w, p.w_goal, p.w_heading,
+                          p.w_clear, p.w_speed};
+    static const char* const names[12] = {"radius", "horizon", "obst_dist", "clear_cap", "max_speed", "max_omega", "acc_v", "acc_w",
+                                          "w_goal", "w_heading", "w_clear", "w_speed"};
+    for (int i = 0; i < 12; ++i)
+        if (!std::isfinite(fl[i])) return fail(MRCA_ERR_INVALID, "mrca_dwa_actions: %s is not finite", names[i]);
+    for (int i : {0, 1, 3, 4, 5})
+        if (!(fl[i] > 0.0f)) return fail(MRCA_ERR_INVALID, "mrca_dwa_actions: %s must be > 0", names[i]);
+    if (!(p.max_speed <= 1.0f)) return fail(MRCA_ERR_INVALID, "mrca_dwa_actions: max_speed must be <= 1");
+    if (!(p.max_omega <= 1.0f)) return fail(MRCA_ERR_INVALID, "mrca_dwa_actions: max_omega must be <= 1");
+    if (!(p.obst_dist >= 0.0f && p.obst_dist <= 6.0f)) return fail(MRCA_ERR_INVALID, "mrca_dwa_actions: obst_dist outside [0, 6]");
+    for (int i = 6; i < 12; ++i)
+        if (!(fl[i] >= 0.0f)) return fail(MRCA_ERR_INVALID, "mrca_dwa_actions: %s must be >= 0", names[i]);
+    if (p.steps < 1 || p.steps > mrca::kDwaMaxSteps)
+        return fail(MRCA_ERR_INVALID, "mrca_dwa_actions: steps %d outside 1..%d", p.steps, mrca::kDwaMaxSteps);
+    if (p.nv < 1 || p.nv > mrca::kDwaMaxNv) return fail(MRCA_ERR_INVALID, "mrca_dwa_actions: nv %d outside 1..%d", p.nv, mrca::kDwaMaxNv);
+    if (p.nw < 1 || p.nw > mrca::kDwaMaxNw) return fail(MRCA_ERR_INVALID, "mrca_dwa_actions: nw %d outside 1..%d", p.nw, mrca::kDwaMaxNw);
+    if (!actions_dev) return fail(MRCA_ERR_INVALID, "mrca_dwa_actions: actions_dev is NULL");
+    if (reinterpret_cast<uintptr_t>(actions_dev) % 8) return fail(MRCA_ERR_INVALID, "mrca_dwa_actions: actions_dev must be 8-byte aligned");
+    if (reinterpret_cast<uintptr_t>(choice_dev) % 4) return fail(MRCA_ERR_INVALID, "mrca_dwa_actions: choice_dev must be 4-byte aligned");
+    if (reinterpret_cast<uintptr_t>(score_dev) % 4) return fail(MRCA_ERR_INVALID, "mrca_dwa_actions: score_dev must be 4-byte aligned");
+    if (!env) return fail(MRCA_ERR_INVALID, "env is NULL");
+    mrca::DwaParams q;
+    static_assert(std::is_trivially_copyable<mrca::DwaParams>::value, "");
+    memcpy(&q, &p, sizeof q);
+    DeviceGuard guard(env->cfg.device);
+    mrca::launch_dwa(env->view, q, mask_dev, actions_dev, choice_dev, score_dev, static_cast<hipStream_t>(stream));
     HIP_TRY(hipGetLastError());
     return MRCA_OK;
 }

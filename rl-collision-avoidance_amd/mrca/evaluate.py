@@ -84,6 +84,27 @@ def orca_policy_fn(env, params=None, first=None, other=None):
     return mixed
 
 
+def dwa_policy_fn(env, params=None, first=None, other=None, other_name="policy"):
+    """The DWA baseline controller on the device (``VecStageWorld.dwa_actions``): it reads the env's own fields (each robot's
+    scan, local goal and speed), so it wants no observation stack.  ``first = K`` with ``other``: robots with local index < K
+    are driven by DWA (through the mask), the rest by the policy function ``other`` (a checkpoint, the stand-in or ORCA), whose
+    group is reported as ``other_name`` -- or, where ``other`` is itself a mixed run, as its own groups without DWA's robots."""
+    if first is None:
+        def fn(obs, local_goal, speed):
+            return env.dwa_actions(params)
+        fn.wants_obs = False
+        return fn
+    mask = (torch.arange(env.N, device=env.device) % env.R < int(first)).to(torch.uint8).contiguous()
+
+    def mixed(obs, local_goal, speed):
+        a = other(obs, local_goal, speed).float().contiguous().clone()
+        return env.dwa_actions(params, mask=mask, out=a)
+    mixed.wants_obs = getattr(other, "wants_obs", True)
+    rest = getattr(other, "groups", None) or {other_name: torch.ones(env.N, dtype=torch.bool, device=env.device)}
+    mixed.groups = {"dwa": mask.bool(), **{k: v & ~mask.bool() for k, v in rest.items()}}
+    return mixed
+
+
 def perturbed_start(env, jitter_xy, jitter_th, seed):
     """Start poses of a circle world with every robot moved off its table pose by U(-jitter_xy, jitter_xy) metres in x
     and y and U(-jitter_th, jitter_th) radians of heading -- drawn from a Philox generator seeded with ``seed``, so that
@@ -212,6 +233,13 @@ def main():
     ap.add_argument("--orca-first", type=int, default=None, metavar="K",
                     help="robots with local index < K are driven by ORCA, the rest by --policy (or the stand-in); the metrics "
                          "are reported for both groups")
+    ap.add_argument("--dwa", action="store_true", help="every robot driven by the DWA baseline controller on the device "
+                                                       "(mrca_dwa_actions: sensor-level, worlds of any size); no --policy is needed")
+    ap.add_argument("--dwa-param", action="append", default=[], metavar="NAME=VALUE",
+                    help="a field of mrca_dwa_params, e.g. horizon=1.5 (repeatable)")
+    ap.add_argument("--dwa-first", type=int, default=None, metavar="K",
+                    help="robots with local index < K are driven by DWA, the rest by --policy, --orca or the stand-in; the "
+                         "metrics are reported for both groups")
     ap.add_argument("--render", default=None, metavar="PATH", help="write pictures of the run (top-down views with trails, rendered on "
                                                                     "the device and copied to the host once after the last tick): "
                                                                     "an animated GIF, or PATH.npz where PIL is missing")
@@ -252,6 +280,16 @@ def main():
             fn, name = orca_policy_fn(env, params), f"ORCA baseline ({orca_call})"
         else:
             fn, name = orca_policy_fn(env, params, first=a.orca_first, other=fn), f"ORCA for local index < {a.orca_first}, else {name}"
+    if a.dwa and (a.orca or a.orca_first is not None):
+        ap.error("--dwa drives every robot: with --orca use --dwa-first K")
+    if a.dwa or a.dwa_first is not None:
+        from .dwa import DwaParams
+        dwa_params = DwaParams.from_assignments(a.dwa_param)
+        if a.dwa_first is None:
+            fn, name = dwa_policy_fn(env, dwa_params), "DWA baseline (mrca_dwa_actions)"
+        else:
+            fn = dwa_policy_fn(env, dwa_params, first=a.dwa_first, other=fn, other_name="orca" if a.orca else "policy")
+            name = f"DWA for local index < {a.dwa_first}, else {name}"
     perturb = tuple(float(v) for v in a.perturb.split(",")) if a.perturb else None
     recorder = None
     if a.render:
@@ -266,6 +304,9 @@ def main():
     if a.orca or a.orca_first is not None:
         import dataclasses
         out["orca_params"] = dataclasses.asdict(params)
+    if a.dwa or a.dwa_first is not None:
+        import dataclasses
+        out["dwa_params"] = dataclasses.asdict(dwa_params)
     out["robots_per_circle"], out["radius_m"] = a.robots, a.radius
     if a.one_circle is not None:
         out["one_circle"], out["robots_per_circle"] = a.one_circle, a.one_circle

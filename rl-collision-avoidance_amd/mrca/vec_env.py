@@ -275,6 +275,22 @@ class VecStageWorld:
                                            self._stream()), name)
         return out
 
+    def dwa_actions(self, params=None, mask=None, out=None, choice=None, score=None):
+        """(v, omega) of the DWA baseline controller (mrca_dwa_actions) for every robot, as a float32[N,2] tensor on the env's
+        device: the sensor-level counterpart of ``orca_actions`` -- it reads each robot's newest scan, local goal and own speed
+        and nothing of any other robot, so it takes worlds of any size.  One launch on the current stream, nothing
+        synchronises, nothing of the env is written: ``env.step(env.dwa_actions())`` is a closed-loop scripted tick.
+        ``params``: a ``dwa.DwaParams`` (default: the library's); ``mask``: a uint8[N] tensor, rows with 0 keep what ``out``
+        (and ``choice`` / ``score``) hold; ``choice``: an int32[N] tensor that takes the candidate chosen (-1: none was
+        admissible, -2: at the goal); ``score``: a float32[N] tensor that takes its score."""
+        if out is None:
+            out = torch.zeros((self.N, 2), dtype=torch.float32, device=self.device)
+        st = None if params is None else params.struct()
+        _lib.check(self.lib.mrca_dwa_actions(self._h, None if st is None else C.byref(st), self._ptr(mask, torch.uint8, self.N),
+                                             self._ptr(out, torch.float32, 2 * self.N), self._ptr(choice, torch.int32, self.N),
+                                             self._ptr(score, torch.float32, self.N), self._stream()), "mrca_dwa_actions")
+        return out
+
     # ------------------------------------------------------------------ lifecycle
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
