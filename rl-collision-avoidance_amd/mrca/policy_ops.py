@@ -2,14 +2,67 @@
 fused forward of both towers' Conv1d + ReLU pairs (rollout AND update) and its backward pass, tied together as a
 ``torch.autograd.Function`` (``lidar_features_fn``) so that the PPO update (model/ppo.py:158-192) differentiates through
 hand-written fp32 MFMA kernels instead of MIOpen.  The rest of the policy stays stock PyTorch.
-The opt-in fused bf16 update has its own pair (``lidar_features_bf16_fn``, ``fc1_bf16``; csrc/mrca_policy_bf16_rows.hip and
-csrc/mrca_policy_bf16_bwd.hip).  There is no fallback: without the HIP library these raise."""
+The opt-in fused bf16 update is the same function at the other precision (``lidar_features_bf16_fn``; csrc/mrca_policy_bf16_rows.hip
+and csrc/mrca_policy_bf16_bwd.hip) with an fc1 of its own (``fc1_bf16``).  There is no fallback: without the HIP library these
+raise."""
 import ctypes as C
 
 import numpy as np
 import torch
 
 from . import _lib
+
+
+def _check(who, dtype, *expected, device=None):
+    """Raise a ``ValueError`` in ``who``'s name unless every ``(tensor, shape)`` of ``expected`` is a contiguous CUDA tensor of
+    ``dtype`` and of that shape -- an int: of that many elements, whatever their shape -- on ``device`` where one is given."""
+    for t, shape in expected:
+        if not (t.is_cuda and t.dtype == dtype and t.is_contiguous() and (device is None or t.device == device) and
+                (t.numel() == shape if isinstance(shape, int) else tuple(t.shape) == shape)):
+            raise ValueError(f"{who}: expected a contiguous cuda {dtype} tensor of shape {shape}"
+                             f"{'' if device is None else f' on {device}'}, got {tuple(t.shape)} {t.dtype} {t.device}")
+
+
+class _stream_on(torch.cuda.device):
+    """``with _stream_on(device) as stream``: selects ``device`` as ``torch.cuda.device`` does and hands out its current stream
+    as the ``c_void_p`` the library's entry points take.  (A class, not a generator: this runs twice per eager rollout tick.)"""
+
+    def __init__(self, device):
+        super().__init__(device)
+        self.device = device
+
+    def __enter__(self):
+        super().__enter__()
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+
+# The ops that keep partial results between two launches: display name -> (the library's size query, buffer starts zeroed).
+# The loss kernel's buffer holds a ticket, which its first launch expects at zero; the others are written before they are read.
+_SCRATCH_OPS = {
+    "lidar_features_backward": ("mrca_lidar_features_backward_scratch", False),
+    "lidar_features_bf16_backward": ("mrca_lidar_features_bf16_backward_scratch", False),
+    "ppo_loss": ("mrca_ppo_loss_scratch", True),
+    "policy_heads backward": ("mrca_policy_heads_backward_scratch", False),
+    "relu_cat backward": ("mrca_relu_cat_backward_bias_scratch", False),
+}
+_scratch = {}
+
+
+def _scratch_of(op, device, stream):
+    """``op``'s scratch bytes, one buffer per (op, device, STREAM): the partial sums (and the loss kernel's ticket) live between
+    a kernel and its finalize launch on one stream, and two trainers, rank threads or side streams of one process must not
+    overwrite each other's.  Allocated outside any graph capture: a buffer first created inside a capture would live in that
+    graph's private pool."""
+    key = (op, device.type, device.index, stream.value or 0)
+    if key not in _scratch:
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(f"{op}: first use on this stream inside a graph capture -- call it once before capturing")
+        size_fn, zeroed = _SCRATCH_OPS[op]
+        n = C.c_size_t()
+        with torch.cuda.device(device):
+            _lib.check(getattr(_lib.load(), size_fn)(C.byref(n)), size_fn)
+        _scratch[key] = (torch.zeros if zeroed else torch.empty)(n.value, dtype=torch.uint8, device=device)
+    return _scratch[key]
 
 
 class RingHead:
@@ -44,8 +97,7 @@ def normalize_scans(scans):
     if x.dtype != torch.float32 or x.numel() % 4:
         raise ValueError("normalize_scans: expected a float32 tensor with a multiple of 4 elements")
     out = torch.empty_like(x)
-    with torch.cuda.device(x.device):
-        stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+    with _stream_on(x.device) as stream:
         _lib.check(_lib.load().mrca_normalize_scans(x.data_ptr(), out.data_ptr(), x.numel(), stream), "mrca_normalize_scans")
     return out
 
@@ -85,6 +137,45 @@ class FrameTable:
             self.rows.record_stream(stream)
 
 
+# the conv front end's two precisions, ``bf16`` -> (dtype of the features and of their gradients, stem of the entry points'
+# names: mrca_<stem>[_rows], mrca_<stem>_backward[_rows])
+_FRONT_END = {False: (torch.float32, "lidar_features"), True: (torch.bfloat16, "lidar_features_bf16")}
+_CONV_SHAPES = ((2, 32, 3, 5), (2, 32), (2, 32, 32, 3), (2, 32))        # w1, b1, w2, b2, tower-major
+
+
+def _front_end_forward(who, bf16, obs, w1, b1, w2, b2, out, head):
+    """The forward of the conv front end at either precision, for a stack tensor (with or without ring heads) or a
+    ``FrameTable`` -> features [2, N, 4096].  The weights are fp32 either way."""
+    lib = _lib.load()
+    dtype, stem = _FRONT_END[bf16]
+    _check(who, torch.float32, *zip((w1, b1, w2, b2), _CONV_SHAPES))
+    if isinstance(obs, FrameTable):
+        if head is not None:
+            raise ValueError(f"{who}: a FrameTable is in deque order already (no head)")
+        if not obs.is_cuda:
+            raise ValueError(f"{who}: the FrameTable must live on the GPU")
+        entry, source = f"mrca_{stem}_rows", (obs.frames.data_ptr(), obs.rows.data_ptr())
+    else:
+        head, raw = unwrap_head(head)
+        if obs.dim() != 3:
+            raise ValueError(f"{who}: expected obs of shape [N, 3, 512], got {tuple(obs.shape)}")
+        _check(who, torch.float32, (obs, (obs.shape[0], 3, 512)))
+        if head is not None:        # one entry per robot
+            _check(who, torch.uint8, (head, obs.shape[0]))
+        entry, source = f"mrca_{stem}", (obs.data_ptr(), None if head is None else head.data_ptr(), int(raw))
+    N = obs.shape[0]
+    if out is None:
+        out = torch.empty(2, N, 4096, dtype=dtype, device=obs.device)
+    elif bf16:      # (the kernel stores 16 bytes at a time; an fp32 buffer is the caller's to get right)
+        _check(who, dtype, (out, (2, N, 4096)), device=obs.device)
+        if out.data_ptr() % 16:
+            raise ValueError(f"{who}: out must be 16-byte aligned")
+    with _stream_on(obs.device) as stream:
+        _lib.check(getattr(lib, entry)(*source, N, 3, 512, w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(),
+                                       out.data_ptr(), stream), entry)
+    return out
+
+
 def lidar_features(obs, w1, b1, w2, b2, out=None, head=None):
     """relu(conv2(relu(conv1(obs)))) of the actor and the critic tower in one launch.
     obs f32[N,3,512]; w1 f32[2,32,3,5], b1 f32[2,32], w2 f32[2,32,32,3], b2 f32[2,32] (tower-major: actor, critic)
@@ -92,41 +183,7 @@ def lidar_features(obs, w1, b1, w2, b2, out=None, head=None):
     ``head`` u8[N] or a ``RingHead``: ``obs`` is a frame RING (VecStageWorld.policy_obs()) and head[n] the slot of
     robot n's newest frame; the kernel reads the frames in deque order while staging -- and, for a ring of RAW scans,
     forms the observation x / 6 - 0.5 on the way.  None: ``obs`` is in deque order."""
-    lib = _lib.load()
-    if isinstance(obs, FrameTable):
-        if head is not None:
-            raise ValueError("lidar_features: a FrameTable is in deque order already (no head)")
-        N = obs.rows.shape[0]
-        if not obs.is_cuda:
-            raise ValueError("lidar_features: the FrameTable must live on the GPU")
-        for t, shape in ((w1, (2, 32, 3, 5)), (b1, (2, 32)), (w2, (2, 32, 32, 3)), (b2, (2, 32))):
-            if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape):
-                raise ValueError(f"lidar_features: expected a contiguous cuda float32 tensor of shape {shape}, got "
-                                 f"{tuple(t.shape)} {t.dtype} {t.device}")
-        if out is None:
-            out = torch.empty(2, N, 4096, dtype=torch.float32, device=obs.device)
-        with torch.cuda.device(obs.device):
-            stream = C.c_void_p(torch.cuda.current_stream(obs.device).cuda_stream)
-            _lib.check(lib.mrca_lidar_features_rows(obs.frames.data_ptr(), obs.rows.data_ptr(), N, 3, 512, w1.data_ptr(),
-                                                    b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), out.data_ptr(), stream),
-                       "mrca_lidar_features_rows")
-        return out
-    head, raw = unwrap_head(head)
-    N, F, B = obs.shape
-    for t, shape in ((obs, (N, 3, 512)), (w1, (2, 32, 3, 5)), (b1, (2, 32)), (w2, (2, 32, 32, 3)), (b2, (2, 32))):
-        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape):
-            raise ValueError(f"lidar_features: expected a contiguous cuda float32 tensor of shape {shape}, got "
-                             f"{tuple(t.shape)} {t.dtype} {t.device}")
-    if head is not None and not (head.is_cuda and head.dtype == torch.uint8 and head.is_contiguous() and head.numel() == N):
-        raise ValueError("lidar_features: head must be a contiguous cuda uint8 tensor with one entry per robot")
-    if out is None:
-        out = torch.empty(2, N, 4096, dtype=torch.float32, device=obs.device)
-    with torch.cuda.device(obs.device):
-        stream = C.c_void_p(torch.cuda.current_stream(obs.device).cuda_stream)
-        _lib.check(lib.mrca_lidar_features(obs.data_ptr(), None if head is None else head.data_ptr(), int(raw), N, F, B,
-                                           w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), out.data_ptr(),
-                                           stream), "mrca_lidar_features")
-    return out
+    return _front_end_forward("lidar_features", False, obs, w1, b1, w2, b2, out, head)
 
 
 def lidar_features_bf16(obs, w1, b1, w2, b2, out=None, head=None):
@@ -134,31 +191,18 @@ def lidar_features_bf16(obs, w1, b1, w2, b2, out=None, head=None):
     bf16[2,N,4096].  Rounding points (include/mrca_env.h: mrca_lidar_features_bf16): the observation, w1, w2, h1 and the
     output are rounded to bf16 (nearest even); the biases are added in fp32.  Rollout inference only: a FrameTable (the
     update's row-table form) is refused."""
-    lib = _lib.load()
     if isinstance(obs, FrameTable):
         raise ValueError("lidar_features_bf16: inference only -- a FrameTable (the update path) is not supported")
-    head, raw = unwrap_head(head)
-    if obs.dim() != 3:
-        raise ValueError(f"lidar_features_bf16: expected obs of shape [N, 3, 512], got {tuple(obs.shape)}")
-    N, F, B = obs.shape
-    for t, shape in ((obs, (N, 3, 512)), (w1, (2, 32, 3, 5)), (b1, (2, 32)), (w2, (2, 32, 32, 3)), (b2, (2, 32))):
-        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape):
-            raise ValueError(f"lidar_features_bf16: expected a contiguous cuda float32 tensor of shape {shape}, got "
-                             f"{tuple(t.shape)} {t.dtype} {t.device}")
-    if head is not None and not (head.is_cuda and head.dtype == torch.uint8 and head.is_contiguous() and head.numel() == N):
-        raise ValueError("lidar_features_bf16: head must be a contiguous cuda uint8 tensor with one entry per robot")
-    if out is None:
-        out = torch.empty(2, N, 4096, dtype=torch.bfloat16, device=obs.device)
-    elif not (out.is_cuda and out.dtype == torch.bfloat16 and out.is_contiguous() and tuple(out.shape) == (2, N, 4096)
-              and out.device == obs.device and out.data_ptr() % 16 == 0):
-        raise ValueError("lidar_features_bf16: out must be a contiguous 16-byte aligned cuda bfloat16 tensor [2, N, 4096] "
-                         "on obs' device")
-    with torch.cuda.device(obs.device):
-        stream = C.c_void_p(torch.cuda.current_stream(obs.device).cuda_stream)
-        _lib.check(lib.mrca_lidar_features_bf16(obs.data_ptr(), None if head is None else head.data_ptr(), int(raw), N, F, B,
-                                                w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), out.data_ptr(),
-                                                stream), "mrca_lidar_features_bf16")
-    return out
+    return _front_end_forward("lidar_features_bf16", True, obs, w1, b1, w2, b2, out, head)
+
+
+def lidar_features_bf16_rows(table, w1, b1, w2, b2, out=None):
+    """lidar_features_bf16 with the stacks addressed through a ``FrameTable`` (normalised frames; csrc/mrca_policy_bf16_rows.hip):
+    the forward of the fused bf16 update.  Same rounding points and device code as the rollout's kernel; bit for bit what
+    ``lidar_features_bf16(table.gather(), ...)`` returns.  -> bf16[2,N,4096]"""
+    if not isinstance(table, FrameTable):
+        raise ValueError("lidar_features_bf16_rows: expected a FrameTable on the GPU")
+    return _front_end_forward("lidar_features_bf16_rows", True, table, w1, b1, w2, b2, out, None)
 
 
 def policy_tail(h1, goal, speed, fc2_w, fc2_b, head_w, head_b, critic_w, critic_b, logstd, noise, lo, hi, fc1_b=None):
@@ -169,23 +213,17 @@ def policy_tail(h1, goal, speed, fc2_w, fc2_b, head_w, head_b, critic_w, critic_
     lib = _lib.load()
     N = h1.shape[1]
     dev = h1.device
-    tensors = [h1, goal, speed, fc2_w, fc2_b, head_w, head_b, critic_w, critic_b, logstd, lo, hi] + ([] if noise is None else [noise])
-    shapes = [(2, N, 256), (N, 2), (N, 2), (2, 260, 128), None, (128, 2), (2,), None, None, (2,), (2,), (2,)] + ([] if noise is None else [(N, 2)])
-    for t, shp in zip(tensors, shapes):
-        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and (shp is None or tuple(t.shape) == shp)):
-            raise ValueError(f"policy_tail: expected a contiguous cuda float32 tensor of shape {shp}, got {tuple(t.shape)} {t.dtype}")
-    if fc2_b.numel() != 256 or critic_w.numel() != 128 or critic_b.numel() != 1:
-        raise ValueError("policy_tail: fc2_b / critic_w / critic_b sizes")
-    if fc1_b is not None and not (fc1_b.is_cuda and fc1_b.dtype == torch.float32 and fc1_b.is_contiguous() and fc1_b.numel() == 512
-                                  and fc1_b.device == dev):
-        raise ValueError("policy_tail: fc1_b must be a contiguous cuda float32 tensor of 2 x 256 elements on h1's device")
+    _check("policy_tail", torch.float32, (h1, (2, N, 256)), (goal, (N, 2)), (speed, (N, 2)), (fc2_w, (2, 260, 128)), (fc2_b, 256),
+           (head_w, (128, 2)), (head_b, (2,)), (critic_w, 128), (critic_b, 1), (logstd, (2,)), (lo, (2,)), (hi, (2,)),
+           *(() if noise is None else ((noise, (N, 2)),)))
+    if fc1_b is not None:       # 2 x 256 elements in any shape, on h1's device
+        _check("policy_tail", torch.float32, (fc1_b, 512), device=dev)
     value = torch.empty(N, 1, dtype=torch.float32, device=dev)
     action = torch.empty(N, 2, dtype=torch.float32, device=dev)
     logprob = torch.empty(N, 1, dtype=torch.float32, device=dev)
     scaled = torch.empty(N, 2, dtype=torch.float32, device=dev)
     mean = torch.empty(N, 2, dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    with _stream_on(dev) as stream:
         _lib.check(lib.mrca_policy_tail(h1.data_ptr(), None if fc1_b is None else fc1_b.data_ptr(), goal.data_ptr(), speed.data_ptr(), N, fc2_w.data_ptr(), fc2_b.data_ptr(),
                                         head_w.data_ptr(), head_b.data_ptr(), critic_w.data_ptr(), critic_b.data_ptr(),
                                         logstd.data_ptr(), None if noise is None else noise.data_ptr(), lo.data_ptr(),
@@ -194,139 +232,34 @@ def policy_tail(h1, goal, speed, fc2_w, fc2_b, head_w, head_b, critic_w, critic_
     return value, action, logprob, scaled, mean
 
 
-_scratch = {}
-
-
-def _backward_scratch(device, stream=0):
-    """Scratch of the backward kernel's per-wave partial sums, one buffer per (device, STREAM) like the loss kernel's and the
-    heads': the partials live between the kernel and its finalize launch on one stream, and two trainers, rank threads or side
-    streams of one process must not overwrite each other's."""
-    key = (device.type, device.index, int(stream))
-    if key not in _scratch:
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("lidar_features_backward: first use on this stream inside a graph capture -- call it once before capturing")
-        lib = _lib.load()
-        n = C.c_size_t()
-        with torch.cuda.device(device):
-            _lib.check(lib.mrca_lidar_features_backward_scratch(C.byref(n)), "mrca_lidar_features_backward_scratch")
-        _scratch[key] = torch.empty(n.value, dtype=torch.uint8, device=device)
-    return _scratch[key]
+def _front_end_backward(bf16, obs, w1, b1, w2, feat, gfeat_act, gfeat_crt):
+    """The backward of the conv front end at either precision: ``feat`` and the two gradients are of the precision's dtype,
+    everything else -- and the four gradients returned -- fp32."""
+    lib = _lib.load()
+    dtype, stem = _FRONT_END[bf16]
+    who = stem + "_backward"
+    N = obs.shape[0]
+    table = isinstance(obs, FrameTable)
+    _check(who, torch.float32, *zip((w1, b1, w2), _CONV_SHAPES), *(() if table else ((obs, (N, 3, 512)),)))
+    _check(who, dtype, (feat, (2, N, 4096)), (gfeat_act, (N, 4096)), (gfeat_crt, (N, 4096)))
+    dev = obs.device
+    dw1, db1 = torch.empty_like(w1), torch.empty_like(b1)
+    dw2, db2 = torch.empty_like(w2), torch.empty(2, 32, dtype=torch.float32, device=dev)
+    entry = f"mrca_{who}_rows" if table else f"mrca_{who}"
+    source = (obs.frames.data_ptr(), obs.rows.data_ptr()) if table else (obs.data_ptr(),)
+    with _stream_on(dev) as stream:
+        scratch = _scratch_of(who, dev, stream)
+        _lib.check(getattr(lib, entry)(*source, N, 3, 512, w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), feat.data_ptr(),
+                                       gfeat_act.data_ptr(), gfeat_crt.data_ptr(), dw1.data_ptr(), db1.data_ptr(), dw2.data_ptr(),
+                                       db2.data_ptr(), scratch.data_ptr(), scratch.numel(), stream), entry)
+    return dw1, db1, dw2, db2
 
 
 def lidar_features_backward(obs, w1, b1, w2, feat, gfeat_act, gfeat_crt):
     """Gradients of lidar_features with respect to (w1, b1, w2, b2) given dLoss/dfeat of the two towers (two [N,4096]
     buffers: they come out of two independent fc1 backward GEMMs); see include/mrca_env.h.
     -> dw1 f32[2,32,3,5], db1 f32[2,32], dw2 f32[2,32,32,3], db2 f32[2,32]"""
-    lib = _lib.load()
-    N = obs.shape[0]
-    table = obs if isinstance(obs, FrameTable) else None
-    for t, shape in (((obs, (N, 3, 512)),) if table is None else ()) + (
-                     (w1, (2, 32, 3, 5)), (b1, (2, 32)), (w2, (2, 32, 32, 3)), (feat, (2, N, 4096)),
-                     (gfeat_act, (N, 4096)), (gfeat_crt, (N, 4096))):
-        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape):
-            raise ValueError(f"lidar_features_backward: expected a contiguous cuda float32 tensor of shape {shape}, got "
-                             f"{tuple(t.shape)} {t.dtype} {t.device}")
-    dev = obs.device
-    dw1, db1 = torch.empty_like(w1), torch.empty_like(b1)
-    dw2, db2 = torch.empty_like(w2), torch.empty(2, 32, dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        scratch = _backward_scratch(dev, stream.value or 0)
-        tail = (N, 3, 512, w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), feat.data_ptr(), gfeat_act.data_ptr(), gfeat_crt.data_ptr(),
-                dw1.data_ptr(), db1.data_ptr(), dw2.data_ptr(), db2.data_ptr(), scratch.data_ptr(), scratch.numel(), stream)
-        if table is None:
-            _lib.check(lib.mrca_lidar_features_backward(obs.data_ptr(), *tail), "mrca_lidar_features_backward")
-        else:
-            _lib.check(lib.mrca_lidar_features_backward_rows(table.frames.data_ptr(), table.rows.data_ptr(), *tail),
-                       "mrca_lidar_features_backward_rows")
-    return dw1, db1, dw2, db2
-
-
-class _LidarFeatures(torch.autograd.Function):
-    """-> (actor features [N,4096], critic features [N,4096]): two outputs, so that autograd hands the backward kernel
-    the two fc1 gradients as they are (one stacked output cost a zero-fill + two copies + an add of [2,N,4096] per
-    minibatch: profiles/r03a_update_bench.txt)."""
-
-    @staticmethod
-    def forward(ctx, obs, w1, b1, w2, b2):
-        w1, b1, w2, b2 = (t.detach().contiguous() for t in (w1, b1, w2, b2))
-        table = obs if isinstance(obs, FrameTable) else None
-        if table is None:
-            obs = obs.detach().contiguous()
-        feat = lidar_features(obs, w1, b1, w2, b2)
-        if table is None:
-            ctx.save_for_backward(obs, w1, b1, w2, feat)
-        else:       # (the frame store and the row table are data: kept by reference, like a saved tensor)
-            ctx.save_for_backward(table.frames, table.rows, w1, b1, w2, feat)
-        ctx.table = table is not None
-        return feat[0], feat[1]
-
-    @staticmethod
-    def backward(ctx, g_act, g_crt):
-        if ctx.table:
-            frames, rows, w1, b1, w2, feat = ctx.saved_tensors
-            obs = FrameTable(frames, rows)
-        else:
-            obs, w1, b1, w2, feat = ctx.saved_tensors
-        g_act = torch.zeros_like(feat[0]) if g_act is None else g_act.contiguous()
-        g_crt = torch.zeros_like(feat[1]) if g_crt is None else g_crt.contiguous()
-        dw1, db1, dw2, db2 = lidar_features_backward(obs, w1, b1, w2, feat, g_act, g_crt)
-        return None, dw1, db1, dw2, db2
-
-
-def lidar_features_fn(obs, w1, b1, w2, b2):
-    """Differentiable lidar_features: same arguments, returns (actor features, critic features), gradients flow to
-    w1 / b1 / w2 / b2 (the scan is data)."""
-    return _LidarFeatures.apply(obs, w1, b1, w2, b2)
-
-
-# ------------------------------------------------------------------------------ the opt-in fused bf16 update's front end
-def _check_conv_weights(who, w1, b1, w2, b2=None):
-    for t, shape in ((w1, (2, 32, 3, 5)), (b1, (2, 32)), (w2, (2, 32, 32, 3))) + (() if b2 is None else ((b2, (2, 32)),)):
-        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape):
-            raise ValueError(f"{who}: expected a contiguous cuda float32 tensor of shape {shape}, got "
-                             f"{tuple(t.shape)} {t.dtype} {t.device}")
-
-
-def lidar_features_bf16_rows(table, w1, b1, w2, b2, out=None):
-    """lidar_features_bf16 with the stacks addressed through a ``FrameTable`` (normalised frames; csrc/mrca_policy_bf16_rows.hip):
-    the forward of the fused bf16 update.  Same rounding points and device code as the rollout's kernel; bit for bit what
-    ``lidar_features_bf16(table.gather(), ...)`` returns.  -> bf16[2,N,4096]"""
-    lib = _lib.load()
-    if not isinstance(table, FrameTable) or not table.is_cuda:
-        raise ValueError("lidar_features_bf16_rows: expected a FrameTable on the GPU")
-    _check_conv_weights("lidar_features_bf16_rows", w1, b1, w2, b2)
-    N = table.rows.shape[0]
-    if out is None:
-        out = torch.empty(2, N, 4096, dtype=torch.bfloat16, device=table.device)
-    elif not (out.is_cuda and out.dtype == torch.bfloat16 and out.is_contiguous() and tuple(out.shape) == (2, N, 4096)
-              and out.device == table.device and out.data_ptr() % 16 == 0):
-        raise ValueError("lidar_features_bf16_rows: out must be a contiguous 16-byte aligned cuda bfloat16 tensor [2, N, 4096] "
-                         "on the table's device")
-    with torch.cuda.device(table.device):
-        stream = C.c_void_p(torch.cuda.current_stream(table.device).cuda_stream)
-        _lib.check(lib.mrca_lidar_features_bf16_rows(table.frames.data_ptr(), table.rows.data_ptr(), N, 3, 512, w1.data_ptr(),
-                                                     b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), out.data_ptr(), stream),
-                   "mrca_lidar_features_bf16_rows")
-    return out
-
-
-_scratch_bf16 = {}
-
-
-def _backward_scratch_bf16(device, stream=0):
-    """per (device, stream), as _backward_scratch: the bf16 backward kernel's per-wave partial sums"""
-    key = (device.type, device.index, int(stream))
-    if key not in _scratch_bf16:
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("lidar_features_bf16_backward: first use on this stream inside a graph capture -- call it once "
-                               "before capturing")
-        lib = _lib.load()
-        n = C.c_size_t()
-        with torch.cuda.device(device):
-            _lib.check(lib.mrca_lidar_features_bf16_backward_scratch(C.byref(n)), "mrca_lidar_features_bf16_backward_scratch")
-        _scratch_bf16[key] = torch.empty(n.value, dtype=torch.uint8, device=device)
-    return _scratch_bf16[key]
+    return _front_end_backward(False, obs, w1, b1, w2, feat, gfeat_act, gfeat_crt)
 
 
 def lidar_features_bf16_backward(obs, w1, b1, w2, feat, gfeat_act, gfeat_crt):
@@ -334,48 +267,26 @@ def lidar_features_bf16_backward(obs, w1, b1, w2, feat, gfeat_act, gfeat_crt):
     numerical contract: include/mrca_env.h, mrca_lidar_features_bf16_backward).  ``obs`` f32[N,3,512] normalised observations
     or a ``FrameTable``; fp32 weights (tower-major); ``feat`` bf16[2,N,4096] the bf16 forward's output; ``gfeat_act`` /
     ``gfeat_crt`` bf16[N,4096].  -> fp32 dw1 [2,32,3,5], db1 [2,32], dw2 [2,32,32,3], db2 [2,32]"""
-    lib = _lib.load()
-    N = obs.shape[0]
-    table = obs if isinstance(obs, FrameTable) else None
-    _check_conv_weights("lidar_features_bf16_backward", w1, b1, w2)
-    if table is None and not (obs.is_cuda and obs.dtype == torch.float32 and obs.is_contiguous() and tuple(obs.shape) == (N, 3, 512)):
-        raise ValueError("lidar_features_bf16_backward: obs must be a contiguous cuda float32 tensor [N, 3, 512] or a FrameTable")
-    for t, shape in ((feat, (2, N, 4096)), (gfeat_act, (N, 4096)), (gfeat_crt, (N, 4096))):
-        if not (t.is_cuda and t.dtype == torch.bfloat16 and t.is_contiguous() and tuple(t.shape) == shape):
-            raise ValueError(f"lidar_features_bf16_backward: expected a contiguous cuda bfloat16 tensor of shape {shape}, got "
-                             f"{tuple(t.shape)} {t.dtype} {t.device}")
-    dev = obs.device
-    dw1, db1 = torch.empty_like(w1), torch.empty_like(b1)
-    dw2, db2 = torch.empty_like(w2), torch.empty(2, 32, dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        scratch = _backward_scratch_bf16(dev, stream.value or 0)
-        tail = (N, 3, 512, w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), feat.data_ptr(), gfeat_act.data_ptr(), gfeat_crt.data_ptr(),
-                dw1.data_ptr(), db1.data_ptr(), dw2.data_ptr(), db2.data_ptr(), scratch.data_ptr(), scratch.numel(), stream)
-        if table is None:
-            _lib.check(lib.mrca_lidar_features_bf16_backward(obs.data_ptr(), *tail), "mrca_lidar_features_bf16_backward")
-        else:
-            _lib.check(lib.mrca_lidar_features_bf16_backward_rows(table.frames.data_ptr(), table.rows.data_ptr(), *tail),
-                       "mrca_lidar_features_bf16_backward_rows")
-    return dw1, db1, dw2, db2
+    return _front_end_backward(True, obs, w1, b1, w2, feat, gfeat_act, gfeat_crt)
 
 
-class _LidarFeaturesBf16(torch.autograd.Function):
-    """_LidarFeatures at bf16: -> (actor features, critic features) bf16[N,4096]; the backward takes the two bf16 fc1
-    gradients as they are.  The roundings are straight-through."""
+class _LidarFeatures(torch.autograd.Function):
+    """-> (actor features [N,4096], critic features [N,4096]) at the precision ``bf16`` selects: two outputs, so that autograd
+    hands the backward kernel the two fc1 gradients as they are (one stacked output cost a zero-fill + two copies + an add of
+    [2,N,4096] per minibatch: profiles/r03a_update_bench.txt).  Under bf16 the roundings are straight-through."""
 
     @staticmethod
-    def forward(ctx, obs, w1, b1, w2, b2):
+    def forward(ctx, bf16, obs, w1, b1, w2, b2):
         w1, b1, w2, b2 = (t.detach().contiguous() for t in (w1, b1, w2, b2))
         table = obs if isinstance(obs, FrameTable) else None
         if table is None:
             obs = obs.detach().contiguous()
-            feat = lidar_features_bf16(obs, w1, b1, w2, b2)
+        feat = _front_end_forward(_FRONT_END[bf16][1] + "_fn", bf16, obs, w1, b1, w2, b2, None, None)
+        if table is None:
             ctx.save_for_backward(obs, w1, b1, w2, feat)
-        else:
-            feat = lidar_features_bf16_rows(table, w1, b1, w2, b2)
+        else:       # (the frame store and the row table are data: kept by reference, like a saved tensor)
             ctx.save_for_backward(table.frames, table.rows, w1, b1, w2, feat)
-        ctx.table = table is not None
+        ctx.table, ctx.bf16 = table is not None, bf16
         return feat[0], feat[1]
 
     @staticmethod
@@ -385,19 +296,28 @@ class _LidarFeaturesBf16(torch.autograd.Function):
             obs = FrameTable(frames, rows)
         else:
             obs, w1, b1, w2, feat = ctx.saved_tensors
-        g_act = torch.zeros_like(feat[0]) if g_act is None else g_act.to(torch.bfloat16).contiguous()
-        g_crt = torch.zeros_like(feat[1]) if g_crt is None else g_crt.to(torch.bfloat16).contiguous()
-        dw1, db1, dw2, db2 = lidar_features_bf16_backward(obs, w1, b1, w2, feat, g_act, g_crt)
-        return None, dw1, db1, dw2, db2
+        if ctx.bf16:        # the fc1 gradients arrive in whatever precision fc1's backward produced: rounded to bf16 once
+            g_act, g_crt = (None if g is None else g.to(torch.bfloat16) for g in (g_act, g_crt))
+        g_act = torch.zeros_like(feat[0]) if g_act is None else g_act.contiguous()
+        g_crt = torch.zeros_like(feat[1]) if g_crt is None else g_crt.contiguous()
+        dw1, db1, dw2, db2 = _front_end_backward(ctx.bf16, obs, w1, b1, w2, feat, g_act, g_crt)
+        return None, None, dw1, db1, dw2, db2
+
+
+def lidar_features_fn(obs, w1, b1, w2, b2):
+    """Differentiable lidar_features: same arguments, returns (actor features, critic features), gradients flow to
+    w1 / b1 / w2 / b2 (the scan is data)."""
+    return _LidarFeatures.apply(False, obs, w1, b1, w2, b2)
 
 
 def lidar_features_bf16_fn(obs, w1, b1, w2, b2):
     """Differentiable bf16 front end of the opt-in fused bf16 update: ``obs`` f32[N,3,512] (normalised) or a ``FrameTable``, fp32
     weights (tower-major) -> (actor features, critic features), two bf16 matrices [N,4096]; fp32 gradients flow to
     w1 / b1 / w2 / b2 through csrc/mrca_policy_bf16_bwd.hip (the scan is data).  Not the reference's precision."""
-    return _LidarFeaturesBf16.apply(obs, w1, b1, w2, b2)
+    return _LidarFeatures.apply(True, obs, w1, b1, w2, b2)
 
 
+# ---------------------------------------------------------------------------------------- the opt-in fused bf16 update's fc1
 class _Fc1Bf16(torch.autograd.Function):
     """fc1 of the fused bf16 update as three library GEMMs with bf16 operands and fp32 accumulation:
     forward   h = feat x Wb^T                       fp32 result (the bias is the caller's, added in fp32)
@@ -429,24 +349,6 @@ def fc1_bf16(feat, weight, weight_bf16):
 
 
 # ------------------------------------------------------------------------------------------------ the PPO loss tail
-_loss_scratch = {}
-
-
-def _ppo_loss_scratch(device, stream):
-    """The loss kernel's partial sums + ticket: one buffer per (device, STREAM) -- two trainers / rank threads / side streams in
-    one process must not share the ticket -- allocated outside any graph capture (a buffer first created inside a capture
-    would live in that graph's private pool)."""
-    key = (device.type, device.index, int(stream))
-    if key not in _loss_scratch:
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("ppo_loss: first use on this stream inside a graph capture -- call it once before capturing")
-        lib = _lib.load()
-        n = C.c_size_t()
-        _lib.check(lib.mrca_ppo_loss_scratch(C.byref(n)), "mrca_ppo_loss_scratch")
-        _loss_scratch[key] = torch.zeros(n.value, dtype=torch.uint8, device=device)
-    return _loss_scratch[key]
-
-
 class _PPOLoss(torch.autograd.Function):
     """loss = L_pi + value_coef * L_v - coeff_entropy * H of model/ppo.py:172-185 with its gradients with respect to the
     network's outputs (mean, value, logstd) from ONE launch (csrc/mrca_ppo_loss.hip); backward scales them by the incoming
@@ -457,17 +359,14 @@ class _PPOLoss(torch.autograd.Function):
         lib = _lib.load()
         n = mean.shape[0]
         args = [t.detach().contiguous().view(-1) for t in (mean, value, logstd, action, old_logprob, adv, target)]
-        for t, numel in zip(args, (2 * n, n, 2, 2 * n, n, n, n)):
-            if not (t.is_cuda and t.dtype == torch.float32 and t.numel() == numel):
-                raise ValueError("ppo_loss: expected cuda float32 tensors mean [n,2], value [n,1], logstd [2], action [n,2], "
-                                 "old_logprob / adv / target [n,1]")
+        # mean [n,2], value [n,1], logstd [2], action [n,2], old_logprob / adv / target [n,1], flattened
+        _check("ppo_loss", torch.float32, *zip(args, (2 * n, n, 2, 2 * n, n, n, n)))
         dev = mean.device
         out = torch.empty(8, dtype=torch.float32, device=dev)
         gmean = torch.empty(n, 2, dtype=torch.float32, device=dev)
         gvalue = torch.empty(n, 1, dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            scratch = _ppo_loss_scratch(dev, stream.value or 0)
+        with _stream_on(dev) as stream:
+            scratch = _scratch_of("ppo_loss", dev, stream)
             _lib.check(lib.mrca_ppo_loss(*[t.data_ptr() for t in args], n, float(clip_value), float(value_coef),
                                          float(coeff_entropy), out.data_ptr(), gmean.data_ptr(), gvalue.data_ptr(),
                                          scratch.data_ptr(), scratch.numel(), stream), "mrca_ppo_loss")
@@ -494,32 +393,10 @@ def adam_step(param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, step):
     weight decay, no amsgrad).  ``param``, ``exp_avg``, ``exp_avg_sq`` are updated in place; ``step`` counts from 1."""
     lib = _lib.load()
     n = param.numel()
-    for t in (param, grad, exp_avg, exp_avg_sq):
-        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.dim() == 1 and t.numel() == n
-                and t.device == param.device):
-            raise ValueError(f"adam_step: expected four flat contiguous cuda float32 tensors of {n} elements on one device, "
-                             f"got {tuple(t.shape)} {t.dtype} {t.device}")
-    with torch.cuda.device(param.device):
-        stream = C.c_void_p(torch.cuda.current_stream(param.device).cuda_stream)
+    _check("adam_step", torch.float32, (param, (n,)), (grad, (n,)), (exp_avg, (n,)), (exp_avg_sq, (n,)), device=param.device)
+    with _stream_on(param.device) as stream:
         _lib.check(lib.mrca_adam_step(param.data_ptr(), grad.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), n,
                                       float(lr), float(beta1), float(beta2), float(eps), int(step), stream), "mrca_adam_step")
-
-
-_heads_scratch = {}
-
-
-def _heads_backward_scratch(device, stream):
-    """The partial records between the heads' backward and finalize kernels: one buffer per (device, STREAM), like the loss
-    kernel's -- two trainers, rank threads or side streams of one process must not overwrite each other's partials."""
-    key = (device.type, device.index, int(stream))
-    if key not in _heads_scratch:
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("policy_heads backward: first use on this stream inside a graph capture -- call it once before capturing")
-        lib = _lib.load()
-        n = C.c_size_t()
-        _lib.check(lib.mrca_policy_heads_backward_scratch(C.byref(n)), "mrca_policy_heads_backward_scratch")
-        _heads_scratch[key] = torch.empty(n.value, dtype=torch.uint8, device=device)
-    return _heads_scratch[key]
 
 
 class _PolicyHeads(torch.autograd.Function):
@@ -535,14 +412,11 @@ class _PolicyHeads(torch.autograd.Function):
         n = a.shape[0]
         a, c = a.detach().contiguous(), c.detach().contiguous()
         ws = [t.detach().contiguous().view(-1) for t in (w1, b1, w2, b2, wc, bc)]
-        for t, numel in zip([a, c] + ws, (n * 128, n * 128, 128, 1, 128, 1, 128, 1)):
-            if not (t.is_cuda and t.dtype == torch.float32 and t.numel() == numel and t.device == a.device):
-                raise ValueError("policy_heads: expected cuda float32 tensors a, c [n,128], three weight rows [1,128] and biases [1] "
-                                 "on one device")
+        # a, c [n,128], then three pairs of a weight row [1,128] and its bias [1]
+        _check("policy_heads", torch.float32, *zip([a, c] + ws, (n * 128, n * 128, 128, 1, 128, 1, 128, 1)), device=a.device)
         mean = torch.empty(n, 2, dtype=torch.float32, device=a.device)
         value = torch.empty(n, 1, dtype=torch.float32, device=a.device)
-        with torch.cuda.device(a.device):
-            stream = C.c_void_p(torch.cuda.current_stream(a.device).cuda_stream)
+        with _stream_on(a.device) as stream:
             _lib.check(lib.mrca_policy_heads(a.data_ptr(), c.data_ptr(), n, *[t.data_ptr() for t in ws], int(bool(relu_inputs)),
                                              mean.data_ptr(), value.data_ptr(), stream), "mrca_policy_heads")
         ctx.save_for_backward(a, c, mean, ws[0], ws[2], ws[4])
@@ -560,9 +434,8 @@ class _PolicyHeads(torch.autograd.Function):
         gvalue = None if gvalue is None else gvalue.contiguous()
         da, dc = torch.empty_like(a), torch.empty_like(c)
         dw = torch.empty(3 * 128 + 3, dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            scratch = _heads_backward_scratch(dev, stream.value or 0)
+        with _stream_on(dev) as stream:
+            scratch = _scratch_of("policy_heads backward", dev, stream)
             head = (a.data_ptr(), c.data_ptr(), mean.data_ptr(), None if gmean is None else gmean.data_ptr(),
                     None if gvalue is None else gvalue.data_ptr(), n, w1.data_ptr(), w2.data_ptr(), wc.data_ptr(),
                     int(ctx.relu_inputs), da.data_ptr(), dc.data_ptr(), dw.data_ptr())
@@ -590,22 +463,6 @@ def policy_heads(a, c, w_actor1, b_actor1, w_actor2, b_actor2, w_critic, b_criti
     return _PolicyHeads.apply(a, c, w_actor1, b_actor1, w_actor2, b_actor2, w_critic, b_critic, relu_inputs, zb_a, zb_c)
 
 
-_relu_cat_scratches = {}
-
-
-def _relu_cat_scratch(device, stream):
-    """per (device, stream), like the heads' scratch: the per-workgroup records of relu_cat's backward with bias sums"""
-    key = (device.type, device.index, int(stream))
-    if key not in _relu_cat_scratches:
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("relu_cat backward: first use on this stream inside a graph capture -- call it once before capturing")
-        lib = _lib.load()
-        n = C.c_size_t()
-        _lib.check(lib.mrca_relu_cat_backward_bias_scratch(C.byref(n)), "mrca_relu_cat_backward_bias_scratch")
-        _relu_cat_scratches[key] = torch.empty(n.value, dtype=torch.uint8, device=device)
-    return _relu_cat_scratches[key]
-
-
 class _ReluCat(torch.autograd.Function):
     """[relu(h1), goal, speed] (model/net.py:43-45) and dh1 = gout[:, :256] where h1 > 0, one launch each."""
 
@@ -616,12 +473,9 @@ class _ReluCat(torch.autograd.Function):
         lib = _lib.load()
         n = h1.shape[0]
         h1, goal, speed = h1.detach().contiguous(), goal.detach().contiguous(), speed.detach().contiguous()
-        for t, shape in ((h1, (n, 256)), (goal, (n, 2)), (speed, (n, 2))):
-            if not (t.is_cuda and t.dtype == torch.float32 and tuple(t.shape) == shape and t.device == h1.device):
-                raise ValueError("relu_cat: expected cuda float32 tensors h1 [n,256], goal [n,2], speed [n,2] on one device")
+        _check("relu_cat", torch.float32, (h1, (n, 256)), (goal, (n, 2)), (speed, (n, 2)), device=h1.device)
         out = torch.empty(n, 260, dtype=torch.float32, device=h1.device)
-        with torch.cuda.device(h1.device):
-            stream = C.c_void_p(torch.cuda.current_stream(h1.device).cuda_stream)
+        with _stream_on(h1.device) as stream:
             _lib.check(lib.mrca_relu_cat(h1.data_ptr(), goal.data_ptr(), speed.data_ptr(), n, out.data_ptr(), stream), "mrca_relu_cat")
         ctx.save_for_backward(h1)
         ctx.h1_bias = h1_bias is not None
@@ -634,11 +488,10 @@ class _ReluCat(torch.autograd.Function):
         gout = gout.contiguous()
         dh1 = torch.empty_like(h1)
         db = None
-        with torch.cuda.device(h1.device):
-            stream = C.c_void_p(torch.cuda.current_stream(h1.device).cuda_stream)
+        with _stream_on(h1.device) as stream:
             if ctx.h1_bias:
                 db = torch.empty(256, dtype=torch.float32, device=h1.device)
-                scratch = _relu_cat_scratch(h1.device, stream.value or 0)
+                scratch = _scratch_of("relu_cat backward", h1.device, stream)
                 _lib.check(lib.mrca_relu_cat_backward_bias(h1.data_ptr(), gout.data_ptr(), h1.shape[0], dh1.data_ptr(), db.data_ptr(),
                                                            scratch.data_ptr(), scratch.numel(), stream), "mrca_relu_cat_backward_bias")
             else:

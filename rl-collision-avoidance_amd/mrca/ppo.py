@@ -24,6 +24,15 @@ def _bounds(action_bound, device, dtype):
     return _bound_cache[key]
 
 
+def check_policy_path(fused, fused_bf16=False, obs_head=None):
+    """Raises ``ValueError`` for a policy-path request no path serves.  (A frame ring handed to the stock layers would be read
+    as if it were in deque order.)"""
+    if obs_head is not None and not fused:
+        raise ValueError("a frame ring (obs_head) can only be read by the fused policy path")
+    if fused_bf16 and not fused:
+        raise ValueError("fused_bf16 is a precision of the fused policy path: it needs fused=True")
+
+
 # ---------------------------------------------------------------------------------------------
 def generate_action(policy, obs, goal, speed, action_bound, generator=None, autocast_dtype=None, fused=False,
                     obs_head=None, noise=None, fused_bf16=False):
@@ -36,10 +45,7 @@ def generate_action(policy, obs, goal, speed, action_bound, generator=None, auto
     here.  ``fused_bf16=True`` (with ``fused``): the fused path's opt-in bf16 inference (bf16 MFMA front end and fc1,
     net.CNNPolicy.act_fused)."""
     from .net import gaussian_logprob
-    if obs_head is not None and not fused:
-        raise ValueError("a frame ring (obs_head) can only be read by the fused policy path")
-    if fused_bf16 and not fused:
-        raise ValueError("fused_bf16 is a precision of the fused policy path: it needs fused=True")
+    check_policy_path(fused, fused_bf16, obs_head)
     if fused and hasattr(policy, "act_fused"):
         lo, hi = _bounds(action_bound, goal.device, torch.float32)
         if noise is None:
@@ -75,8 +81,7 @@ def policy_input(env, fused):
 
 def generate_action_no_sampling(policy, obs, goal, speed, action_bound, fused=False, obs_head=None, fused_bf16=False):
     """model/ppo.py:84-107: deterministic mean action (circle_test.py:58-59).  ``fused_bf16``: as generate_action."""
-    if fused_bf16 and not fused:
-        raise ValueError("fused_bf16 is a precision of the fused policy path: it needs fused=True")
+    check_policy_path(fused, fused_bf16, obs_head)
     if fused and hasattr(policy, "act_fused"):
         lo, hi = _bounds(action_bound, goal.device, torch.float32)
         _v, _a, _lp, scaled, mean = policy.act_fused(obs, goal, speed, None, lo, hi, head=obs_head, bf16=fused_bf16)
@@ -601,19 +606,25 @@ def _ppo_epochs(policy, optimizer, batch_size, flat, epoch, coeff_entropy, clip_
             break
 
 
+def _flat_memory(memory, num_step, num_env, frames, obs_size, act_size, dist):
+    """``memory`` as ``ppo_update_stage1`` takes it -> what ``_ppo_epochs`` takes: (obss, goals, speeds, actions, logprobs,
+    targets, advs) with T*N rows each, the advantages normalised over ALL ranks (model/ppo.py:147-157)."""
+    obss, goals, speeds, actions, logprobs, targets, _values, _rewards, advs = memory
+    mean, std = _global_mean_std(advs, dist)
+    advs = (advs - mean) / std
+    n = num_step * num_env
+    obs_rows = obss if isinstance(obss, FrameRows) else obss.reshape(n, frames, obs_size)
+    return (obs_rows, goals.reshape(n, 2), speeds.reshape(n, 2), actions.reshape(n, act_size), logprobs.reshape(n, 1),
+            targets.reshape(n, 1), advs.reshape(n, 1))
+
+
 def ppo_update_stage1(policy, optimizer, batch_size, memory, epoch, coeff_entropy=0.02, clip_value=0.2,
                       num_step=2048, num_env=12, frames=1, obs_size=24, act_size=4, *, value_coef=20.0,
                       index_batches=None, dist=None, flat_grads=None, log=None, autocast_dtype=None, kl_ctl=None,
                       max_grad_norm=0.0, logstd_min=None):
     """model/ppo.py:143-194.  ``memory`` = (obss, goals, speeds, actions, logprobs, targets, values,
     rewards, advs) as device tensors shaped [T, N, ...] (obss may be a FrameRows: one stored frame per tick)."""
-    obss, goals, speeds, actions, logprobs, targets, _values, _rewards, advs = memory
-    mean, std = _global_mean_std(advs, dist)
-    advs = (advs - mean) / std
-    n = num_step * num_env
-    obs_rows = obss if isinstance(obss, FrameRows) else obss.reshape(n, frames, obs_size)
-    flat = (obs_rows, goals.reshape(n, 2), speeds.reshape(n, 2),
-            actions.reshape(n, act_size), logprobs.reshape(n, 1), targets.reshape(n, 1), advs.reshape(n, 1))
+    flat = _flat_memory(memory, num_step, num_env, frames, obs_size, act_size, dist)
     _ppo_epochs(policy, optimizer, batch_size, flat, epoch, coeff_entropy, clip_value, False, value_coef,
                 index_batches, dist, flat_grads, log, autocast_dtype, kl_ctl, max_grad_norm, logstd_min)
 
@@ -624,16 +635,10 @@ def ppo_update_stage2(policy, optimizer, batch_size, memory, filter_index, epoch
                       kl_ctl=None, max_grad_norm=0.0, logstd_min=None):
     """model/ppo.py:197-259: the advantage statistics use ALL transitions, then the filtered rows
     are deleted and minibatches use drop_last=True."""
-    obss, goals, speeds, actions, logprobs, targets, _values, _rewards, advs = memory
-    mean, std = _global_mean_std(advs, dist)
-    advs = (advs - mean) / std
-    n = num_step * num_env
-    keep = torch.ones(n, dtype=torch.bool, device=advs.device)
+    flat = _flat_memory(memory, num_step, num_env, frames, obs_size, act_size, dist)
+    keep = torch.ones(num_step * num_env, dtype=torch.bool, device=flat[-1].device)
     if filter_index is not None and len(filter_index):
-        keep[torch.as_tensor(filter_index, device=advs.device, dtype=torch.long)] = False
-    obs_rows = obss if isinstance(obss, FrameRows) else obss.reshape(n, frames, obs_size)
-    flat = tuple(x[keep] for x in (obs_rows, goals.reshape(n, 2), speeds.reshape(n, 2),
-                                   actions.reshape(n, act_size), logprobs.reshape(n, 1), targets.reshape(n, 1),
-                                   advs.reshape(n, 1)))
+        keep[torch.as_tensor(filter_index, device=keep.device, dtype=torch.long)] = False
+    flat = tuple(x[keep] for x in flat)
     _ppo_epochs(policy, optimizer, batch_size, flat, epoch, coeff_entropy, clip_value, True, value_coef,
                 index_batches, dist, flat_grads, log, autocast_dtype, kl_ctl, max_grad_norm, logstd_min)

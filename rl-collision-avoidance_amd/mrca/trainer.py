@@ -50,6 +50,22 @@ class HParams:
     logstd_min: float = float("-inf")
     max_grad_norm: float = 0.0        # > 0: global-norm gradient clipping (opt-in; the reference clips nothing)
 
+    def check_update_path(self):
+        """Raises ``ValueError`` for an update-side request no path serves."""
+        if self.update_bf16 and not self.update_fused:
+            raise ValueError("update_bf16 is a precision of the fused update path: it needs update_fused=True")
+        if self.update_bf16 and self.update_dtype is not None:
+            raise ValueError("update_bf16 (the fused bf16 update) and update_dtype (autocast on the stock layers) exclude each other")
+
+
+def act(policy, env, hp, gen, noise=None):
+    """The act step of a rollout tick: the policy's input as ``env`` offers it to the path ``hp`` selects, then a sampled action.
+    -> (v, a, logprob, scaled): ``a`` and ``logprob`` are what the buffer stores, ``scaled`` is what ``env.step`` takes.  ``noise``:
+    this tick's sampling draws when the caller made them (a replay of several ticks draws all of them in one launch)."""
+    obs, head = ppo.policy_input(env, hp.rollout_fused)
+    return ppo.generate_action(policy, obs, env.local_goal, env.speed, hp.action_bound, gen, hp.inference_dtype, hp.rollout_fused,
+                               head, noise=noise, fused_bf16=hp.rollout_bf16)
+
 
 def broadcast_parameters(module, dist):
     """Rank 0's parameters to every rank.  The broadcast writes INTO the parameter under no_grad (not through
@@ -74,10 +90,7 @@ class Stage1Trainer:
         self.policy = policy or CNNPolicy(frames=self.hp.laser_hist, action_space=self.hp.act_size,
                                           beams=self.hp.obs_size)
         self.policy.to(dev)
-        if self.hp.update_bf16 and not self.hp.update_fused:
-            raise ValueError("update_bf16 is a precision of the fused update path: it needs update_fused=True")
-        if self.hp.update_bf16 and self.hp.update_dtype is not None:
-            raise ValueError("update_bf16 (the fused bf16 update) and update_dtype (autocast on the stock layers) exclude each other")
+        self.hp.check_update_path()
         if self.hp.update_fused:
             self.policy.fused_train = True
         if self.hp.update_bf16:
@@ -117,11 +130,8 @@ class Stage1Trainer:
         """The device work of one tick with the buffer row taken from ``self._t_idx`` (a device tensor): nothing in
         here depends on a host value, so it can be captured as a hipGraph.  ``noise``: this tick's sampling draws when
         the caller made them (a replay of several ticks draws all of them in one launch)."""
-        env, hp, buf = self.env, self.hp, self.buffer
-        obs, head = ppo.policy_input(env, hp.rollout_fused)
-        v, a, logprob, scaled = ppo.generate_action(self.policy, obs, env.local_goal, env.speed, hp.action_bound, self.gen,
-                                                    hp.inference_dtype, hp.rollout_fused, head, noise=noise,
-                                                    fused_bf16=hp.rollout_bf16)
+        env, buf = self.env, self.buffer
+        v, a, logprob, scaled = act(self.policy, env, self.hp, self.gen, noise)
         so, sn = (None, None) if buf.env_bound else self._stored_obs()
         buf.store_state_at(self._t_idx, so, env.local_goal, env.speed, a, logprob, v, env.fresh, newest=sn)
         env.step(scaled.contiguous())
@@ -135,41 +145,51 @@ class Stage1Trainer:
             return None, self.env.newest_frame()
         return self.env.obs, None
 
-    def _capture(self):
-        """One tick as a hipGraph: ~50 launches (policy layers, sampling, the two env kernels, eight buffer stores)
-        become one graph launch.  The policy's parameters, the env's arena and the rollout buffer are all at fixed
-        addresses, the action-noise generator is registered with the graph, the buffer row is a device counter."""
-        if hasattr(self.env, "enable_timing"):
-            self.env.enable_timing(False)               # event records cannot be part of the captured tick
+    def _capture_ticks(self, body, lengths):
+        """Ticks of ``body(noise)`` as hipGraphs, one per entry of ``lengths``: that many ticks whose sampling noise is ONE
+        randn((ticks, N, 2)) at the graph's head -- a 5 us launch of its own in a 250 us tick, and NOT the numbers of as many
+        one-tick draws: the generator maps Philox offsets to elements by launch shape.  An entry of None is one tick that leaves
+        the draw to the body (``body(None)``: the eager tick's randn((N, 2)), so that a replay and an eager tick are one noise
+        stream).  The policy's parameters, the env's arena and the rollout buffer are all at fixed addresses, the action-noise
+        generator is registered with the graphs, the buffer row is a device counter."""
+        env = self.env
+        if hasattr(env, "enable_timing"):
+            env.enable_timing(False)                    # event records cannot be part of the captured tick
         if self.hp.rollout_fused:
             self.policy.refresh_rollout_cache()
-        side = torch.cuda.Stream(device=self.env.device)
-        side.wait_stream(torch.cuda.current_stream(self.env.device))
+        side = torch.cuda.Stream(device=env.device)
+        side.wait_stream(torch.cuda.current_stream(env.device))
         with torch.cuda.stream(side):
             # warm-up on the capture stream (lazy inits, workspace allocs).  The three ticks really advance the env (their
             # transitions are not logged: the first update's episode statistics miss them) but all write the buffer row
-            # the horizon is at, which the first real tick overwrites -- never a row past a short horizon
+            # the horizon is at, which the first real tick overwrites -- never a row past a short horizon (a body that stores
+            # nothing, bench.py's rollout, never reads the counter)
             for _ in range(3):
                 self._t_idx.fill_(self.t)
-                self._tick_body()
-        torch.cuda.current_stream(self.env.device).wait_stream(side)
+                body(None)
+        torch.cuda.current_stream(env.device).wait_stream(side)
         self._t_idx.fill_(self.t)
-        g = torch.cuda.CUDAGraph()
-        g.register_generator_state(self.gen)
-        with torch.cuda.graph(g, stream=side):
-            self._tick_body()
-        self._graph = g
-        # ... and EIGHT ticks as one graph for ``run``: a replay has a start-up of its own (a few us the eager path hides
-        # behind the previous tick's kernels) and the eight ticks' sampling noise is one launch instead of eight
-        if self.hp.horizon >= self.GRAPH_RUN:
-            g8 = torch.cuda.CUDAGraph()
-            g8.register_generator_state(self.gen)
-            with torch.cuda.graph(g8, stream=side):
-                noise = torch.randn((self.GRAPH_RUN, self.env.N, 2), device=self.env.device, dtype=torch.float32,
-                                    generator=self.gen)
-                for i in range(self.GRAPH_RUN):
-                    self._tick_body(noise[i])
-            self._graph_run = g8
+        graphs = []
+        for ticks in lengths:
+            g = torch.cuda.CUDAGraph()
+            g.register_generator_state(self.gen)
+            with torch.cuda.graph(g, stream=side):
+                if ticks is None:
+                    body(None)
+                else:
+                    noise = torch.randn((ticks, env.N, 2), device=env.device, dtype=torch.float32, generator=self.gen)
+                    for i in range(ticks):
+                        body(noise[i])
+            graphs.append(g)
+        return graphs
+
+    def _capture(self):
+        """One tick as a hipGraph: ~50 launches (policy layers, sampling, the two env kernels, eight buffer stores) become one
+        graph launch.  ... and EIGHT ticks as one graph for ``run``: a replay has a start-up of its own (a few us the eager
+        path hides behind the previous tick's kernels) and the eight ticks' sampling noise is one launch instead of eight."""
+        long_run = self.hp.horizon >= self.GRAPH_RUN
+        graphs = self._capture_ticks(self._tick_body, (None, self.GRAPH_RUN) if long_run else (None,))
+        self._graph, self._graph_run = graphs[0], graphs[1] if long_run else None
 
     def tick(self):
         """One pass of the while-loop body of ppo_stage1.py:64-118 for all robots."""
@@ -187,10 +207,7 @@ class Stage1Trainer:
             # and the row comes from the device-side counter (which the second of them moves on)
             self._tick_body()
         else:
-            obs, head = ppo.policy_input(env, hp.rollout_fused)
-            v, a, logprob, scaled = ppo.generate_action(self.policy, obs, env.local_goal, env.speed,
-                                                        hp.action_bound, self.gen, hp.inference_dtype, hp.rollout_fused, head,
-                                                        fused_bf16=hp.rollout_bf16)
+            v, a, logprob, scaled = act(self.policy, env, hp, self.gen)
             so, sn = self._stored_obs()
             buf.store_state(self.t, so, env.local_goal, env.speed, a, logprob, v, env.fresh, newest=sn)
             env.step(scaled.contiguous())
@@ -274,39 +291,18 @@ def make_bench_step(env, mode, dist, batch_size=16384, inference_dtype=None, upd
                  graph_tick=graph, update_fused=update_fused, rollout_bf16=fused_bf16)
     tr = Stage1Trainer(env, hp=hp, dist=dist, seed=0)
     tr.started = True  # bench.py resets the env itself
-    if mode == "rollout" and graph:
-        # the rollout of bench.py: policy + sampling + env tick (no buffer stores), captured once, replayed per tick
-        if fused:
-            tr.policy.refresh_rollout_cache()
-
+    if mode == "rollout":
+        # the rollout of bench.py: policy + sampling + env tick (no buffer stores)
         def body(noise=None):
-            obs, head = ppo.policy_input(env, hp.rollout_fused)
-            _v, _a, _lp, scaled = ppo.generate_action(tr.policy, obs, env.local_goal, env.speed, hp.action_bound, tr.gen,
-                                                      hp.inference_dtype, hp.rollout_fused, head, noise=noise,
-                                                      fused_bf16=hp.rollout_bf16)
+            _v, _a, _lp, scaled = act(tr.policy, env, hp, tr.gen, noise)
             env.step(scaled.contiguous())
-        env.enable_timing(False)
-        side = torch.cuda.Stream(device=env.device)
-        side.wait_stream(torch.cuda.current_stream(env.device))
-        with torch.cuda.stream(side):
-            for _ in range(3):
-                body()
-        torch.cuda.current_stream(env.device).wait_stream(side)
-        # one graph of ONE tick and one of EIGHT: a replay has a start-up of its own (a few us the eager path hides behind
-        # the previous tick's kernels: 265 vs 256 us per tick with one tick per replay, profiles/r04_v_bench_rollout*.json),
-        # so a run of n ticks replays the long graph n // 8 times and the short one for the remainder
-        # the sampling noise of all the ticks of a replay is drawn by ONE launch at its head (a randn of 8192 numbers is a
-        # 5 us launch of its own in a 250 us tick).  NOT the same numbers as eight one-tick draws: the generator's Philox
-        # offset -> element mapping depends on the launch's shape, so g8 and g1 are two different noise streams of one seed)
-        def capture(ticks):
-            g = torch.cuda.CUDAGraph()
-            g.register_generator_state(tr.gen)
-            with torch.cuda.graph(g, stream=side):
-                noise = torch.randn((ticks, env.N, 2), device=env.device, dtype=torch.float32, generator=tr.gen)
-                for i in range(ticks):
-                    body(noise[i])
-            return g
-        g1, g8 = capture(1), capture(8)
+        if not graph:
+            return lambda _k: body()
+        # ... captured once as one graph of ONE tick and one of EIGHT: a replay has a start-up of its own (a few us the eager
+        # path hides behind the previous tick's kernels: 265 vs 256 us per tick with one tick per replay,
+        # profiles/r04_v_bench_rollout*.json), so a run of n ticks replays the long graph n // 8 times and the short one for the
+        # remainder
+        g1, g8 = tr._capture_ticks(body, (1, 8))
 
         def step_fn(_k):
             g1.replay()
@@ -317,14 +313,6 @@ def make_bench_step(env, mode, dist, batch_size=16384, inference_dtype=None, upd
             for _ in range(n % 8):
                 g1.replay()
         step_fn.run_ticks = run_ticks
-        return step_fn
-    if mode == "rollout":
-        def step_fn(_k):
-            obs, head = ppo.policy_input(env, hp.rollout_fused)
-            _v, _a, _lp, scaled = ppo.generate_action(tr.policy, obs, env.local_goal, env.speed,
-                                                      hp.action_bound, tr.gen, hp.inference_dtype, hp.rollout_fused, head,
-                                                      fused_bf16=hp.rollout_bf16)
-            env.step(scaled.contiguous())
         return step_fn
 
     def train_fn(_k):

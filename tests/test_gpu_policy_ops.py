@@ -240,3 +240,55 @@ def test_policy_tail_adds_the_fc1_bias_itself(pol, n):
         assert torch.equal(a, b)
     with pytest.raises(ValueError):
         policy_ops.policy_tail(h1, *rest, fc1_b=rc["fc1_b"][:, :, :128].contiguous())
+
+
+def test_scratch_is_one_buffer_per_device_stream_and_op(pol):
+    """The ops that keep partial results between two launches take their scratch from ONE cache, keyed by (op, device, stream):
+    the same storage when a stream comes back, other storage on another stream and for another op, the loss kernel's zeroed
+    before its first launch (it holds a ticket) -- and whatever stream an op runs on, it computes what it computes on the
+    default stream (tolerances: the loss statistics' of tests/test_gpu_ppo_loss.py, the backward's of
+    tests/test_gpu_policy_bwd.py at this size)."""
+    from mrca import policy_ops as P
+    dev = torch.device("cuda", torch.cuda.current_device())
+    g = torch.Generator(device="cuda").manual_seed(11)
+    n, N = 256, 64
+    mean = torch.stack([torch.rand(n, generator=g, device="cuda"), torch.rand(n, generator=g, device="cuda") * 2 - 1], 1)
+    logstd = torch.tensor([-0.3, 0.1], device="cuda")
+    action = mean + torch.exp(logstd) * torch.randn(n, 2, generator=g, device="cuda")
+    value, target, adv, old_lp = (torch.randn(n, 1, generator=g, device="cuda") for _ in range(4))
+    x = torch.rand(N, 3, 512, generator=g, device="cuda") - 0.5
+    rc = pol.refresh_rollout_cache()
+    w = (rc["w1"], rc["b1"], rc["w2"])
+    feat = P.lidar_features(x, *w, rc["b2"])
+    ga, gc = torch.randn(2, N, 4096, generator=g, device="cuda").unbind(0)
+
+    def run():
+        stats = P.ppo_loss(mean, value, logstd, action, old_lp, adv, target, 0.1, 20.0, 5e-4)[1]
+        return stats, P.lidar_features_backward(x, *w, feat, ga, gc)
+
+    def scratch(op):        # of the current stream
+        with P._stream_on(dev) as handle:
+            return P._scratch_of(op, dev, handle)
+
+    want_stats, want_grads = run()
+    torch.cuda.synchronize()
+    s1, s2 = torch.cuda.Stream(), torch.cuda.Stream()
+    storage = {}
+    for s in (s1, s2, s1):
+        with torch.cuda.stream(s):
+            if s not in storage:
+                assert not bool(scratch("ppo_loss").any())              # before this stream's first launch of the loss
+            stats, grads = run()
+            here = (scratch("ppo_loss").data_ptr(), scratch("lidar_features_backward").data_ptr())
+        s.synchronize()
+        assert storage.setdefault(s, here) == here                     # the same storage on reuse
+        for k in range(5):
+            err, ref = abs(float(stats[k]) - float(want_stats[k])), max(1.0, abs(float(want_stats[k])))
+            print(f"stats[{k}] on a side stream: |d| {err:.3g}")
+            assert err <= 2e-6 * ref, (k, err)
+        for name, a, b in zip(("dw1", "db1", "dw2", "db2"), grads, want_grads):
+            err, scale = float((a - b).abs().max()), float(b.abs().max())
+            print(f"{name} on a side stream: |d| {err:.3g} of {scale:.3g}")
+            assert scale > 0.0 and err < 2e-5 * scale, (name, err, scale)
+    default = (scratch("ppo_loss").data_ptr(), scratch("lidar_features_backward").data_ptr())
+    assert len({*storage[s1], *storage[s2], *default}) == 6             # other storage per stream and per op

@@ -103,6 +103,62 @@ def test_kl_adaptive_lr_and_logstd_floor():
     assert float(pol.logstd.detach().min()) >= -1.2
 
 
+def test_scratch_cache_refuses_a_first_use_inside_a_capture_for_every_op(monkeypatch):
+    """A scratch buffer first created inside a graph capture would live in that graph's private pool: the cache refuses, in
+    the op's name, before it asks the library for a size or allocates -- so this needs neither a GPU nor the built library."""
+    import ctypes as C
+    from mrca import _lib, policy_ops as P
+
+    def unreachable(*_a, **_k):
+        raise AssertionError("the refusal comes before any library call or allocation")
+    monkeypatch.setattr(torch.cuda, "is_current_stream_capturing", lambda: True)
+    monkeypatch.setattr(_lib, "load", unreachable)
+    monkeypatch.setattr(torch, "empty", unreachable)
+    monkeypatch.setattr(torch, "zeros", unreachable)
+    assert sorted(P._SCRATCH_OPS) == ["lidar_features_backward", "lidar_features_bf16_backward", "policy_heads backward",
+                                      "ppo_loss", "relu_cat backward"]
+    assert [op for op, (_fn, zeroed) in P._SCRATCH_OPS.items() if zeroed] == ["ppo_loss"]      # the ticket starts at zero
+    cached = list(P._scratch)
+    for op in P._SCRATCH_OPS:
+        with pytest.raises(RuntimeError, match=op + ": first use on this stream inside a graph capture"):
+            P._scratch_of(op, torch.device("cuda", 0), C.c_void_p(0x1000))        # (no stream of this process has that handle)
+    assert list(P._scratch) == cached
+
+
+@pytest.mark.parametrize("request_", [dict(fused_bf16=True), dict(obs_head=torch.zeros(24, dtype=torch.uint8))],
+                         ids=["fused_bf16 without fused", "obs_head without fused"])
+def test_policy_path_requests_no_path_serves_are_refused_by_both_entries(request_):
+    """One judgement (ppo.check_policy_path) behind both entries: generate_action_no_sampling refuses a frame ring without the
+    fused path too -- it would hand the ring to the stock layers as if it were in deque order."""
+    from mrca import ppo
+    from mrca.net import CNNPolicy
+    env = ct.CpuEnv(S.stage1(num_worlds=1, robots_per_world=24, seed=1))
+    env.reset()
+    pol, bound = CNNPolicy(3, 2), ((0.0, -1.0), (1.0, 1.0))
+    with pytest.raises(ValueError):
+        ppo.generate_action(pol, env.obs, env.local_goal, env.speed, bound, fused=False, **request_)
+    with pytest.raises(ValueError):
+        ppo.generate_action_no_sampling(pol, env.obs, env.local_goal, env.speed, bound, fused=False, **request_)
+
+
+@pytest.mark.parametrize("request_", [dict(update_bf16=True), dict(update_bf16=True, update_fused=True, update_dtype=torch.bfloat16)],
+                         ids=["update_bf16 without update_fused", "update_bf16 with update_dtype"])
+def test_update_path_requests_no_path_serves_are_refused_by_the_trainer(request_):
+    from mrca.trainer import HParams, Stage1Trainer
+    env = ct.CpuEnv(S.stage1(num_worlds=1, robots_per_world=24, seed=1))
+    with pytest.raises(ValueError):
+        Stage1Trainer(env, hp=HParams(horizon=4, batch_size=32, epoch=1, **request_))
+
+
+def test_rollout_bf16_without_rollout_fused_is_refused_by_the_trainers_tick():
+    from mrca.trainer import HParams, Stage1Trainer
+    env = ct.CpuEnv(S.stage1(num_worlds=1, robots_per_world=24, seed=1))
+    tr = Stage1Trainer(env, hp=HParams(horizon=4, batch_size=32, epoch=1, rollout_bf16=True))
+    tr.start()
+    with pytest.raises(ValueError):
+        tr.tick()
+
+
 def test_rollout_cache_follows_the_parameters_whoever_changes_them():
     """The fused rollout path reads tower-major COPIES of the parameters.  They are rebuilt lazily whenever any parameter's
     in-place version, storage or device differs from what the copies were made from -- an optimiser step outside the
