@@ -95,8 +95,11 @@ int validate(const mrca_config* c) {
                     c->map_words_per_row);
     // the grid walks keep cell coordinates in fp32 (exact integers, sub-cell estimates good to << 1 cell up to
     // 2^16) and index the per-cell fields with 24-bit multiplies
-    if (c->map_width > 16384 || c->map_height > 16384)
-        return fail(MRCA_ERR_UNSUPPORTED, "map %dx%d cells: at most 16384 per side", c->map_width, c->map_height);
+    // (and the march addresses a field array with a 32-bit byte offset: the quadrant array of the largest map fits it; the octant
+    // array, twice the size, is checked where it is built -- upload_octants)
+    static_assert(mrca::field_fits_offsets(mrca::kMaxMapSide, mrca::kMaxMapSide, 4), "the quadrant array of the largest map");
+    if (c->map_width > mrca::kMaxMapSide || c->map_height > mrca::kMaxMapSide)
+        return fail(MRCA_ERR_UNSUPPORTED, "map %dx%d cells: at most %d per side", c->map_width, c->map_height, mrca::kMaxMapSide);
     if (!(c->map_cell > 0.0f)) return fail(MRCA_ERR_INVALID, "map_cell must be > 0");
     if (!c->map_bits) return fail(MRCA_ERR_INVALID, "map_bits is NULL");
     if (c->auto_reset < 0 || c->auto_reset > 2) return fail(MRCA_ERR_INVALID, "auto_reset %d", c->auto_reset);
@@ -521,6 +524,9 @@ static bool field_octants(const mrca_config* c) {
 
 // the octant array into a buffer of the env's own, and the march's three uniforms of the view onto it
 static int upload_octants(const mrca_config* cfg, mrca_env* env) {
+    if (!mrca::field_fits_offsets(cfg->map_width, cfg->map_height, 8))
+        return fail(MRCA_ERR_UNSUPPORTED, "map %dx%d cells: the octant free-rectangle array passes 4 GiB (MRCA_FIELD_OCTANTS=0 "
+                    "marches over the quadrant array)", cfg->map_width, cfg->map_height);
     const std::shared_ptr<const HostField> hf = host_field(cfg, true);
     const size_t bytes = hf->octants.size() * sizeof(uint16_t);
     HIP_TRY(device_alloc(&env->octant_rect, bytes));

@@ -226,7 +226,7 @@ MRCA_HD int med3_i32(int a, int b, int c) {
     return r;
 #else
     const int lo = imin(a, imin(b, c)), hi = imax(a, imax(b, c));
-    return a + b + c - lo - hi;   // no overflow for the operands used here (two of them < 2^20, one < 2^30)
+    return a + b + c - lo - hi;   // no overflow for the operands used here (two of them < 2^20, one <= 2^30 in magnitude)
 #endif
 }
 // a * b + c for |a|, |b| < 2^23 in ONE full-rate v_mad_i32_i24 (left to itself the compiler turns the multiply of an
@@ -251,8 +251,38 @@ MRCA_HD int clamp_from(int x, int hi) {   // clamp(x, LO, hi), LO <= hi
 #endif
 }
 
+// What the ray cast reads and writes through the view, addressed the GLOBAL way on the device: a pointer out of the EnvView
+// carries no address space, so a load through it is a flat_* instruction -- a 64-bit add per lane to form the address, a slot
+// on the LDS issue path as well, and a wait on both counters.  base + a 32-bit byte offset through an address-space-1 pointer is
+// ONE global_* instruction with the base in scalar registers and the offset in a vector register.  The host build of the same
+// functions is the plain C++ it always was.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define MRCA_GLOBAL __attribute__((address_space(1)))
+#else
+#define MRCA_GLOBAL
+#endif
+template <class T>
+MRCA_HD T global_load(const void* base, uint32_t byte_off) {
+    return *reinterpret_cast<const MRCA_GLOBAL T*>((const MRCA_GLOBAL char*)base + byte_off);
+}
+template <class T>
+MRCA_HD void global_store(void* base, uint32_t byte_off, T v) {
+    *reinterpret_cast<MRCA_GLOBAL T*>((MRCA_GLOBAL char*)base + byte_off) = v;
+}
+// (nontemporal: for what the launch does not read again)
+template <class T>
+MRCA_HD void global_store_nt(void* base, uint32_t byte_off, T v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    __builtin_nontemporal_store(v, reinterpret_cast<MRCA_GLOBAL T*>((MRCA_GLOBAL char*)base + byte_off));
+#else
+    global_store<T>(base, byte_off, v);
+#endif
+}
+
 struct FreeRectField {   // free-rectangle field straight from global memory (L1/L2-resident)
-    const uint16_t* d;   // base of the padded array: 4 entries (quadrants 0..3) per cell, or 8 (octants, mrca_host.h)
+    // base of the padded array: 4 entries (quadrants 0..3) per cell, or 8 (octants, mrca_host.h).  Every lookup is
+    // global_load<>(d, byte offset): the array's size in bytes fits 32 bits (mrca_create refuses a map whose array does not).
+    const uint16_t* d;
     int32_t w, h, pitch; // map size in cells, CELLS per padded row
     // The record layout as UNIFORM VALUES, so that one instruction stream marches over either array: log2 of a cell's
     // record size, and what a ray with |dx| >= |dy| adds to its quadrant's byte offset.  Quadrant array (the default, what
@@ -277,14 +307,14 @@ struct FreeRectField {   // free-rectangle field straight from global memory (L1
     }
     // the entry at byte offset qbytes (entry_bytes) of a cell's record
     MRCA_HD uint32_t operator()(int ix, int iy, uint32_t qbytes) const {
-        return *reinterpret_cast<const uint16_t*>(reinterpret_cast<const char*>(d) + (cell_offset(ix, iy) + qbytes));
+        return global_load<uint16_t>(d, cell_offset(ix, iy) + qbytes);
     }
     // all four entries of a cell of the QUADRANT array: .x = quadrants 0 | 1 << 16, .y = quadrants 2 | 3 << 16 (what a `head`
     // record carries)
     MRCA_HD void cell(int ix, int iy, uint32_t* lo, uint32_t* hi) const {
-        const uint32_t* p = reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(d) + cell_offset(ix, iy));
-        *lo = p[0];
-        *hi = p[1];
+        const uint32_t off = cell_offset(ix, iy);
+        *lo = global_load<uint32_t>(d, off);
+        *hi = global_load<uint32_t>(d, off + 4u);
     }
 };
 
@@ -330,14 +360,55 @@ MRCA_HD int lane_counter(int x) {
     return x;
 }
 
+// a value read afresh from its vector register: what the compiler knew about it (a compare it could re-use as a lane mask carried
+// round a loop) ends here
+MRCA_HD float lane_value(float x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm("" : "+v"(x));
+#endif
+    return x;
+}
+// does the condition hold for any lane of the wavefront?  (the host build marches one ray: the condition itself)
+MRCA_HD bool wave_any(bool c) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_ballot_w64(c) != 0ull;
+#else
+    return c;
+#endif
+}
+
+// grid_march_skip's treatment of an axis the ray does not travel along (see there): the origin it computes that axis' boundary
+// times from, and such a time
+MRCA_HD float idle_axis_origin(float f, bool travels) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return travels ? f : -kInf;
+#else
+    (void)travels;
+    return f;
+#endif
+}
+MRCA_HD float idle_axis_time(float raw, bool travels) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    (void)travels;
+    return raw;
+#else
+    return travels ? raw : kInf;
+#endif
+}
+
 template <class Field>
 MRCA_HD float grid_march_skip(const Field& field, const GridGeom& g, const MarchOrigin& org, float dx, float dy,
                               float tmax) {
-    const float fx = org.fx, fy = org.fy;
     const int ix0 = org.ix0, iy0 = org.iy0;
     const float tmax_c = tmax * g.inv_cell;
     const bool xnz = dx != 0.0f, ynz = dy != 0.0f;
     const bool xpos = dx > 0.0f, ypos = dy > 0.0f;
+    // The boundary times of an axis the ray does not travel along are +inf.  On the device such an axis gets its origin at -inf:
+    // every one of its times is then (b + inf) * inf = +inf by arithmetic, no select per axis and trip (with the origin itself
+    // 0 * inf is a NaN), and the secondary axis' numbers of such a ray are infinities that are never used (bothnz below).  The
+    // host build, the specification, keeps the origin and selects (idle_axis_time): it converts the secondary axis' position to
+    // an integer, which C++ does not define for an infinity.
+    const float fx = idle_axis_origin(org.fx, xnz), fy = idle_axis_origin(org.fy, ynz);
     // the ray's quadrant picks which of the four rectangles of the origin's cell it starts from (org.v_lo / v_hi: always
     // quadrant entries), its quadrant and major axis which entry of a cell's record every later lookup reads
     const uint32_t qbytes = field.entry_bytes(dx, dy);
@@ -350,8 +421,6 @@ MRCA_HD float grid_march_skip(const Field& field, const GridGeom& g, const March
     const float inv_dy = ynz ? rdy : kInf;
     const int sx = xpos ? 1 : -1, sy = ypos ? 1 : -1;
     const int ux = xpos ? 1 : 0, uy = ypos ? 1 : 0;      // current cell = pending boundary - u, on each axis
-    // a pending boundary only ever moves in the direction of travel: clamp(b, from b0) = med3(b, b0, lim)
-    const int limx = xpos ? 0x3FFFFFFF : -0x3FFFFFFF, limy = ypos ? 0x3FFFFFFF : -0x3FFFFFFF;
     // An axis-parallel ray never crosses a boundary of its zero axis -- which then is always the secondary
     // axis below (its exit time is +inf), so the whole estimate is skipped for such a ray.
     const bool bothnz = xnz & ynz;
@@ -359,30 +428,39 @@ MRCA_HD float grid_march_skip(const Field& field, const GridGeom& g, const March
     int bx = ix0 + ux;
     int by = iy0 + uy;
     // The loop's bookkeeping the vector way (a scalar instruction costs the launch twice a vector one, profiles/r06_ac_*):
-    //   * the result is selected inside the loop -- a ray hits once, then leaves it;
-    //   * ONE exit: `left`, a per-lane trip counter that a hit, the end of the beam and the trip guard all set to 0 (as lane
-    //     MASKS the three exits cost eleven scalar instructions per trip);
+    //   * the loop carries no result: a lane leaves it with the time t of its last trip and the entry v it last read, and the
+    //     range is formed ONCE behind the loop (t * cell where that trip was inside the beam and read an occupied cell: the same
+    //     single rounding the cell-by-cell walk does);
+    //   * ONE exit test: `left`, a per-lane trip counter that a hit, the end of the beam and the trip guard all bring to 0 (as
+    //     lane MASKS the three exits cost eleven scalar instructions per trip).  The end of the beam is folded into v -- a lane
+    //     with t >= tmax_c is given kCellOccupied, which ends it like a hit does; behind the loop its t says which it was -- so
+    //     that the counter's update is one compare, one decrement, one select;
+    //   * the jump's body is skipped by a WAVE-uniform branch when no lane is inside its beam any more (most waves' last trip: the
+    //     body and a memory round trip saved).  A lane past its end in a wave that goes on runs the body on its own numbers --
+    //     every lookup is clamped into the array -- and discards what it read (as a per-lane `if` the body cost the exec-mask
+    //     bookkeeping of a region per trip).  Its t may be +inf or a NaN (dx = dy = 0), and so may pT: the address is safe because
+    //     v_cvt_i32_f32 SATURATES (a NaN gives 0) and because med3_i32 and FreeRectField::cell_offset's clamp_from are inline
+    //     assembly on whatever integer comes out -- the compiler cannot treat the out-of-range conversion as a value that never
+    //     occurs.  Whoever rewrites either clamp in plain C++ must clamp pT as a float first.  (The host build marches one ray:
+    //     wave_any is the lane's own test, and the body never runs past the end);
     //   * the secondary axis is settled for every lane and selected away for an axis-parallel ray (its numbers are NaNs then,
     //     never used): a branch around it cost the exec-mask bookkeeping of a region per trip;
     //   * "consumed at or before t" is "before the next float above t" (t >= 0 by construction; -0 counts as +0; denormals are
     //     honoured, .amdhsa_float_denorm_mode_32 3): one bit trick instead of an equality compare and two mask operations per
     //     candidate.
-    float out = tmax;
     int left = lane_counter(kMaxMarchSteps);
+    float t;
     do {
         // faces of the rectangle known to be free: e cells beyond the current cell's own far face
         const int ex = (int)(v & 255u), ey = (int)((v >> 8) & 255u);   // (both as 8-bit fields: one v_and / v_bfe + a 24-bit mad each)
         const int Bx = mad24(ex, sx, bx);
         const int By = mad24(ey, sy, by);
-        const float rawx = ((float)Bx - fx) * inv_dx;
-        const float rawy = ((float)By - fy) * inv_dy;
-        const float tBx = xnz ? rawx : kInf;
-        const float tBy = ynz ? rawy : kInf;
+        const float tBx = idle_axis_time(((float)Bx - fx) * inv_dx, xnz);     // (+inf on an axis the ray does not travel, see fx / fy)
+        const float tBy = idle_axis_time(((float)By - fy) * inv_dy, ynz);
         const bool xe = tBx < tBy;  // leaves through the x face (ties: y first)
-        const float t = xe ? tBx : tBy;
-        if (t >= tmax_c) {
-            left = 0;
-        } else {
+        t = xe ? tBx : tBy;
+        const bool go = !(t >= tmax_c);
+        if (wave_any(go)) {
             // the other ("secondary") axis: which of its crossings were consumed before time t?
             // x exit: y crossings with ty(b) <= t;  y exit: x crossings with tx(b) < t.
             const float fS = xe ? fy : fx;
@@ -397,7 +475,8 @@ MRCA_HD float grid_march_skip(const Field& field, const GridGeom& g, const March
             // "only when close to a boundary" test would make the whole wavefront take the slow path
             // whenever one of its 64 rays is close).
             const float pT = fS + (xe ? dy : dx) * t;
-            const int b = med3_i32((int)floorf(pT) + (xe ? uy : ux), bS0, xe ? limy : limx);
+            // (a pending boundary only ever moves in the direction of travel: clamp(b, from bS0) = med3(b, bS0, +-2^30))
+            const int b = med3_i32((int)floorf(pT) + (xe ? uy : ux), bS0, (int)((uint32_t)sS << 30));
             const int bprev = b - sS;
             const float tp = ((float)bprev - fS) * invS;      // the crossing before b ...
             const float tc = ((float)b - fS) * invS;          // ... and b itself: consumed before t?
@@ -413,13 +492,15 @@ MRCA_HD float grid_march_skip(const Field& field, const GridGeom& g, const March
             bx = xe ? Bx + sx : bS;
             by = xe ? bS : By + sy;
             v = field(bx - ux, by - uy, qbytes);  // cells outside the map read as empty (the zero border)
-            const bool hit = v == kCellOccupied;
-            out = hit ? t * g.cell : out;
-            left = hit ? 0 : left - 1;
         }
-        left = lane_counter(left);
+        v = go ? v : kCellOccupied;
+        left = lane_counter(v == kCellOccupied ? 0 : left - 1);
     } while (left > 0);
-    return out;
+    // (what a lane left the loop with, read afresh: carried out of the loop as lane masks the two tests cost three scalar
+    // instructions per trip)
+    t = lane_value(t);
+    v = (uint32_t)lane_counter((int)v);
+    return (!(t >= tmax_c) & (v == kCellOccupied)) ? t * g.cell : tmax;
 }
 
 template <class Field>

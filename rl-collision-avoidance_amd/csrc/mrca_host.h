@@ -10,6 +10,16 @@
 
 namespace mrca {
 
+// The march addresses a field array as base + a 32-BIT byte offset (FreeRectField::cell_offset: one global load with the base in
+// scalar registers), so an array of `entries` 16-bit entries per padded cell must end below 4 GiB.  The quadrant array (4) of
+// the largest map mrca_create takes has 2.1 GB; the octant array (8) passes the bound from 16382 x 16382 cells on, and
+// mrca_create refuses it there.
+constexpr int kMaxMapSide = 16384;               // cells: what mrca_create accepts
+constexpr bool field_fits_offsets(int width, int height, int entries) {
+    return (uint64_t)(width + 2 * kFieldPadX) * (uint64_t)(height + 2 * kFieldPadY) * (uint64_t)entries * sizeof(uint16_t) <=
+           0xFFFFFFFFull;
+}
+
 // Quadrant free-rectangle field for grid_march_skip: FOUR 16-bit entries per cell, one per quadrant of the direction of
 // travel, q = (dx > 0) | (dy > 0) << 1 with sx = +-1, sy = +-1 accordingly.  For an EMPTY cell entry q packs the extents
 // ex | ey << 8 of a rectangle of empty cells [x, x + sx*ex] x [y, y + sy*ey] that has the cell in the corner a ray of

@@ -66,8 +66,10 @@ __device__ __forceinline__ void raycast_body(int only_fresh, int ray_first, int 
     const int tid = threadIdx.x;
     // (A variant of this kernel without the early exit -- so that nothing is waited for before every request of the
     // workgroup is out -- was measured and changed nothing: 27.96 us either way, profiles/r03/r03_l_bench_env.json.  The
-    // launch uses ~45 % of the VALU issue slots: what it waits for is a workgroup's chain of dependent round trips at full
-    // occupancy, and one early exit less does not shorten that chain -- DESIGN.md 5.2.)
+    // launch ALONE uses ~45 % of the VALU issue slots: what it waits for is a workgroup's chain of dependent round trips at full
+    // occupancy, and one early exit less does not shorten that chain.  Under mrca_step_many's run-ahead schedule, launches of
+    // two world ranges and the move launches in flight at once, the same instructions fill ~60 % of the slots and the tick
+    // follows their count nearly 1 : 1 -- DESIGN.md 5.2.)
     if (only_fresh && e.fresh[n] == 0) return;  // block-uniform
 
     float4* nb = reinterpret_cast<float4*>(lds);
@@ -110,7 +112,7 @@ __device__ __forceinline__ void raycast_body(int only_fresh, int ray_first, int 
     if (!BIG && is_prep) {
         xj = pose_p[jn * 3 + 0];
         yj = pose_p[jn * 3 + 1];
-        if constexpr (raster) oj = reinterpret_cast<const int4*>(e.outline)[jn];
+        if constexpr (raster) oj = global_load<int4>(e.outline, (uint32_t)jn * 16u);
         else hj = head_p[jn];
     }
     // beam directions in the robot frame for this thread's K beams (tid + k*T)
@@ -157,8 +159,8 @@ __device__ __forceinline__ void raycast_body(int only_fresh, int ray_first, int 
         int cell_start = 0, cell_count = 0;
         if (pl < 9) {
             const uint32_t h = hash_cell(icx + pl % 3 - 1, icy + pl / 3 - 1, world) & (uint32_t)e.bw_lmask;
-            cell_start = e.bw_lstart[h];
-            cell_count = e.bw_lstart[h + 1] - cell_start;
+            cell_start = global_load<int>(e.bw_lstart, h * 4u);
+            cell_count = global_load<int>(e.bw_lstart, h * 4u + 4u) - cell_start;
         }
         int cell_end = cell_count;         // inclusive prefix sum over lanes 0..8 (lanes >= 9 hold zeros)
 #pragma unroll
@@ -178,7 +180,7 @@ __device__ __forceinline__ void raycast_body(int only_fresh, int ray_first, int 
             const int qx = icx + q % 3 - 1, qy = icy + q / 3 - 1;
             const int q_end = __shfl(cell_end, q, kWave), q_count = __shfl(cell_count, q, kWave);
             const int idx = __shfl(cell_start, q, kWave) + (entry - (q_end - q_count));
-            const int j = valid ? e.bw_lsorted[idx] : -1;
+            const int j = valid ? global_load<int>(e.bw_lsorted, (uint32_t)idx * 4u) : -1;
             bool keep = false;
             float cxj = 0.0f, cyj = 0.0f;
             float4 chj = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
@@ -296,7 +298,7 @@ __device__ __forceinline__ void raycast_body(int only_fresh, int ray_first, int 
                            org.fy - reach <= (float)e.g.height;
         }
         if (map_in_reach) {
-            if constexpr (K == 1 || SEQ) {   // one ray at a time: the hand-tuned single-ray loop (54 VALU per jump)
+            if constexpr (K == 1 || SEQ) {   // one ray at a time: the hand-tuned single-ray loop (57 vector instructions per jump)
 #pragma unroll
                 for (int k = 0; k < K; ++k) rng[k] = grid_march_skip(field, e.g, org, dx[k], dy[k], kRangeMax);
             } else {                         // K rays in lock step: K lookups in flight per wait
@@ -409,12 +411,12 @@ __device__ __forceinline__ void raycast_body(int only_fresh, int ray_first, int 
             if (fresh) {     // deque([obs] * F), ppo_stage1.py:59-60: every slot, the head stays where it is
                 for (int f = 0; f < e.F; ++f) {
                     if (TICKS && !((stores >> f) & 1u)) continue;       // a later tick of the launch writes this slot
-                    __builtin_nontemporal_store(r, &ring_row[f * e.B + b]);
-                    if (word_lane) hit_row[f * words + (b >> 6)] = hm;
+                    global_store_nt(ring_row, (uint32_t)(f * e.B + b) * 4u, r);
+                    if (word_lane) global_store(hit_row, (uint32_t)(f * words + (b >> 6)) * 8u, hm);
                 }
             } else if (!TICKS || stores) {
-                __builtin_nontemporal_store(r, &ring_row[new_slot * e.B + b]);
-                if (word_lane) hit_row[new_slot * words + (b >> 6)] = hm;
+                global_store_nt(ring_row, (uint32_t)(new_slot * e.B + b) * 4u, r);
+                if (word_lane) global_store(hit_row, (uint32_t)(new_slot * words + (b >> 6)) * 8u, hm);
             }
             // lazy_obs = 0: the two reference-shaped views of this robot, formed here instead of by a materialize_kernel launch
             // behind every ray cast (get_laser_observation, stage_world1.py:127-141: the newest scan; the stack in deque order,
@@ -423,32 +425,33 @@ __device__ __forceinline__ void raycast_body(int only_fresh, int ray_first, int 
             if (VIEWS && views) {
                 const float nr = norm_obs(r);
                 // (nontemporal like the ring row: the launch does not read them again)
-                if (views & 1) __builtin_nontemporal_store(r, &e.scan[(size_t)n * (uint32_t)e.B + b]);
+                if (views & 1) global_store_nt(e.scan + (size_t)n * (uint32_t)e.B, (uint32_t)b * 4u, r);
                 if (views & 2) {
-                    float* dst = e.obs + (size_t)row * (uint32_t)e.B + b;
+                    float* dst = e.obs + (size_t)row * (uint32_t)e.B;      // (the robot's stack: workgroup-uniform)
                     if (fresh) {
-                        for (int f = 0; f < e.F; ++f) __builtin_nontemporal_store(nr, &dst[f * e.B]);
+                        for (int f = 0; f < e.F; ++f) global_store_nt(dst, (uint32_t)(f * e.B + b) * 4u, nr);
                     } else {
                         int slot = new_slot;
                         for (int f = 0; f < e.F - 1; ++f) {        // oldest first: the slot behind the newest, and on round the ring
                             slot = slot + 1 == e.F ? 0 : slot + 1;
-                            __builtin_nontemporal_store(norm_obs(fabsf(ring_row[slot * e.B + b])), &dst[f * e.B]);
+                            const float older = global_load<float>(ring_row, (uint32_t)(slot * e.B + b) * 4u);
+                            global_store_nt(dst, (uint32_t)(f * e.B + b) * 4u, norm_obs(fabsf(older)));
                         }
-                        __builtin_nontemporal_store(nr, &dst[(e.F - 1) * e.B]);
+                        global_store_nt(dst, (uint32_t)((e.F - 1) * e.B + b) * 4u, nr);
                     }
                 }
             }
         }
         if constexpr (TICKS) {
-            if (tid == 0 && mt.j == mt.T - 1) mt.head_out[n] = (uint8_t)head_after;
+            if (tid == 0 && mt.j == mt.T - 1) global_store(mt.head_out, (uint32_t)n, (uint8_t)head_after);
         } else {
-            if (tid == 0 && !fresh) ring_head_p[n] = (uint8_t)new_slot;
+            if (tid == 0 && !fresh) global_store(ring_head_p, (uint32_t)n, (uint8_t)new_slot);
         }
     }
     if (tid == 0 && (!TICKS || mt.j == mt.T - 1)) {  // get_local_goal (stage_world1.py:155-160)
-        const float gx = e.goal[n * 2 + 0] - x, gy = e.goal[n * 2 + 1] - y;
-        e.local_goal[n * 2 + 0] = gx * c + gy * s;
-        e.local_goal[n * 2 + 1] = gy * c - gx * s;
+        const float gx = global_load<float>(e.goal, (uint32_t)n * 8u) - x, gy = global_load<float>(e.goal, (uint32_t)n * 8u + 4u) - y;
+        global_store(e.local_goal, (uint32_t)n * 8u, gx * c + gy * s);
+        global_store(e.local_goal, (uint32_t)n * 8u + 4u, gy * c - gx * s);
     }
     MRCA_RSTAMP(6);     // stores issued (debug flag 64: acknowledged)
 }

@@ -1,0 +1,180 @@
+#!/usr/bin/env python3
+"""Instruction counts of the ray-cast kernels, read off the compiler's gfx950 assembly (host only: hipcc cross-compiles).
+
+    python tools/ray_inst_count.py [--all] [--csrc DIR]
+
+Compiles csrc/mrca_kernels.hip and csrc/mrca_raycast_ticks.hip to assembly with csrc/build.sh's flags (the way
+tests/test_isa_properties.py does) and prints, for every ray-cast kernel of a shape the product launches (asked of
+mrca_ray_shape.h itself, compiled for the host; --all: every instantiation):
+
+  * the kernel's static counts: vector instructions, scalar-side instructions, and the flat / global / LDS ones among them;
+  * the same for each MARCH loop (an innermost loop that loads a 16-bit field entry) and for the SLAB loop (the innermost loop
+    that reads a neighbour's 16-byte record from LDS, stores nothing and loads nothing from global memory).
+
+Instructions are classed by mnemonic prefix only: v_* is vector; s_* is the scalar side (s_nop, s_waitcnt and branches
+included: each takes an issue slot of the wave); flat_*, global_*, ds_*, buffer_*, scratch_* are memory instructions, listed by
+class and counted with neither.  A loop is the blocks the compiler's own comments attribute to one innermost loop header.
+These are STATIC counts: what a wave executes is the trips it takes times a loop's count (profiles/ray_diet/before_after.txt
+has the dynamic ones, from the SQ counters).
+"""
+import argparse
+import os
+import re
+import shutil
+import subprocess
+import sys
+import tempfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+
+MEM = ("flat", "global", "ds", "buffer", "scratch")
+
+# The (K, BIG, SEQ, RKW) the product launches are asked of csrc/mrca_ray_shape.h itself: the header compiled for the host and
+# ray_shape() called with the product's knobs (product_ray_shift, sequential = 1, no preparation wave) for every beam count
+# mrca_create accepts, small and big worlds, and collision rasters from 0.1 m (the finest it accepts) to 0.5 m.
+SHAPES_MAIN = r"""
+#include <cstdio>
+#include "mrca_ray_shape.h"
+int main() {
+    for (int beams = 64; beams <= 1024; beams += 64)
+        for (int big = 0; big < 2; ++big)
+            for (int r = 0; r <= 50; r = r ? r + 1 : 10) {        // no raster, then 0.10 .. 0.50 m (never in big worlds)
+                if (big && r) continue;
+                const float inv = r ? 1.0f / (0.01f * (float)r) : 0.0f;
+                const mrca::RayShape s = mrca::ray_shape(beams, big != 0, inv, mrca::raster_window(inv),
+                                                         mrca::product_ray_shift(beams, big), true, false);
+                std::printf("%d %d %d %d\n", s.k, s.big ? 1 : 0, s.seq ? 1 : 0, s.rkw);
+            }
+    return 0;
+}
+"""
+
+
+def product_shapes(csrc, tmp):
+    src, exe = os.path.join(tmp, "shapes.cpp"), os.path.join(tmp, "shapes")
+    open(src, "w").write(SHAPES_MAIN)
+    subprocess.run([os.environ.get("CXX", "g++"), "-O1", "-std=c++17", "-Wno-unknown-pragmas", "-I", csrc, src, "-o", exe],
+                   check=True, capture_output=True)
+    out = subprocess.run([exe], check=True, capture_output=True, text=True).stdout
+    return {tuple(map(int, line.split())) for line in out.splitlines()}
+
+
+def build_flags(csrc, src):
+    text = open(os.path.join(csrc, "build.sh")).read()
+    flags = " ".join(re.findall(r"^\s+(-f[\w=-]+(?:\s+-f[\w=-]+)*)", text, re.M)).split()
+    per = re.search(r'"\$\{src\}" == "%s" \]\] && per=\(([^)]*)\)' % src, text)
+    return flags + (per.group(1).split() if per else [])
+
+
+def assembly(csrc, src, tmp):
+    out = os.path.join(tmp, src + ".s")
+    subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", *build_flags(csrc, src), "-S", "--cuda-device-only",
+                    os.path.join(csrc, src + ".hip"), "-o", out], check=True, capture_output=True)
+    return open(out).read().split("\n")
+
+
+def variant(name):
+    """(label, (K, BIG, SEQ, RKW)) of a ray-cast kernel's mangled name, or None"""
+    m = re.search(r"raycast_kernelILi(\d)ELb([01])ELb([01])ELi(\d)ELb([01])E", name)
+    if m:
+        k, big, seq, rkw, views = map(int, m.groups())
+        return "raycast_kernel<K=%d, BIG=%d, SEQ=%d, RKW=%d, VIEWS=%d>" % (k, big, seq, rkw, views), (k, big, seq, rkw)
+    m = re.search(r"raycast_ticks_kernelILi(\d)ELb([01])ELi(\d)E", name)
+    if m:
+        k, seq, rkw = map(int, m.groups())
+        return "raycast_ticks_kernel<K=%d, SEQ=%d, RKW=%d>" % (k, seq, rkw), (k, 0, seq, rkw)
+    return None
+
+
+class Count:
+    def __init__(self):
+        self.v = self.s = 0
+        self.mem = dict.fromkeys(MEM, 0)
+        self.ushort = self.b128 = self.stores = 0
+
+    def add(self, op):
+        if op.startswith("v_"):
+            self.v += 1
+        elif op.startswith("s_"):
+            self.s += 1
+        else:
+            for c in MEM:
+                if op.startswith(c + "_"):
+                    self.mem[c] += 1
+            self.ushort += op.endswith("_load_ushort")
+            self.b128 += op == "ds_read_b128"
+            self.stores += "_store_" in op or op.startswith("ds_write") or op.startswith("ds_or")
+
+    def __str__(self):
+        return "vector %4d  scalar-side %4d  flat %2d  global %2d  lds %2d" % (
+            self.v, self.s, self.mem["flat"], self.mem["global"], self.mem["ds"])
+
+
+def kernels(lines):
+    """{mangled name: (Count of the kernel, {innermost loop header: Count})}"""
+    out, name, total, loops, loop = {}, None, None, None, None
+    for line in lines:
+        m = re.match(r"(_Z\w+):", line)
+        if m:
+            name, total, loops, loop = m.group(1), Count(), {}, None
+            continue
+        if name is None:
+            continue
+        if re.match(r"\.Lfunc_end\d+:", line):
+            out[name] = (total, loops)
+            name = None
+            continue
+        # a block begins: `.LBBn_m:` or `; %bb.k:`, with the compiler's loop comment behind it (or none: not in a loop)
+        b = re.match(r"(?:\.LBB\d+_(\d+)|; %bb\.\d+):\s*(?:;(.*))?$", line)
+        if b:
+            note = b.group(2) or ""
+            h = re.search(r"Header=BB\d+_(\d+)", note)
+            loop = h.group(1) if h else (b.group(1) if "Loop Header" in note else None)
+            continue
+        i = re.match(r"\t([a-z]\w+)", line)
+        if not i or line.startswith("\t."):
+            continue
+        total.add(i.group(1))
+        if loop is not None:
+            loops.setdefault(loop, Count()).add(i.group(1))
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--all", action="store_true", help="every instantiation, not only the product's shapes")
+    ap.add_argument("--csrc", default=os.path.join(ROOT, "rl-collision-avoidance_amd", "csrc"))
+    a = ap.parse_args()
+    if not (os.path.exists(HIPCC) or shutil.which(HIPCC)):
+        sys.exit("hipcc not found (HIPCC=%s)" % HIPCC)
+    with tempfile.TemporaryDirectory() as tmp:
+        product = product_shapes(a.csrc, tmp)
+        compiled = set()
+        for src in ("mrca_raycast_ticks", "mrca_kernels"):
+            found = kernels(assembly(a.csrc, src, tmp))
+            print("== %s.hip" % src)
+            for name in sorted(found, key=lambda n: variant(n) or ("", ())):
+                v = variant(name)
+                if v:
+                    compiled.add(v[1])
+                if not v or not (a.all or v[1] in product):
+                    continue
+                total, loops = found[name]
+                print(v[0])
+                print("    kernel      %s" % total)
+                march = [c for c in loops.values() if c.ushort]
+                slab = [c for c in loops.values() if c.b128 and not c.stores and not c.ushort and not c.mem["global"]]
+                for k, c in enumerate(march):
+                    print("    march loop %d%s %s" % (k, " (%d beams in lock step)" % c.ushort if c.ushort > 1 else "", c))
+                for c in slab:
+                    print("    slab loop   %s" % c)
+        # (a shape the header selects and neither source instantiates would be a launch without a kernel)
+        missing = sorted(product - compiled)
+        if missing:
+            sys.exit("mrca_ray_shape.h selects (K, BIG, SEQ, RKW) %s: no such kernel in the compiled sources" % missing)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
