@@ -702,6 +702,9 @@ static void init_step_many(mrca_env* env) {
             r.ticks_forced = true;
         }
     }
+    // (such a launch addresses the fresh flags of its ticks -- up to 8 slots apart -- from one base with a 32-bit offset:
+    // beyond that, a launch per tick)
+    if (7ull * r.slot_bytes + (unsigned long long)N > 0xffffffffull) ticks = 1;
     if (ticks > 1 && r.slots > 0 && device_alloc(&r.head_scratch, N) == hipSuccess) r.ticks_per_launch = ticks;
     else (void)hipGetLastError();
 }

@@ -1304,23 +1304,43 @@ MRCA_HD void open_episode(const EpisodeRules& r, float x, float y, float gx, flo
 // launch writes -- what it leaves out are a restart's duplicate copies and a row a restart up to two ticks later overwrites:
 // every slot has at most one writer per launch, and it is the last writer of the sequential order.
 //   h0: the head before the launch's first tick; fresh_bits: bit t = tick t of the launch is fresh for this robot.
-//   -> stores: bit s = tick j stores slot s; head: the head after the launch's last tick.
+//   -> stores: bit s = tick j stores slot s; head: the head after the launch's last tick; slot: the head after tick j -- the
+//      one slot a tick that is not fresh writes, and for the launch's last tick the same number as head; any: stores != 0.
+// In closed form (a loop over the launch's ticks ran in every wave of every workgroup on the same inputs): the head moves
+// once per tick that is not fresh, so behind tick t it is h0 + (the stale ticks among 0 .. t), less F at most once (that
+// count <= T <= F, h0 < F).  A restart behind tick j overwrites all tick j wrote; without one the m = T - 1 - j ticks behind
+// j are all stale and write the m slots behind tick j's head -- the only ones a fresh tick j leaves to others.
+// (fresh_bits' bits T and up are ignored.)
 struct RingStores {
     uint32_t stores;
     int head;
+    int slot;
+    bool any;
 };
-MRCA_HD RingStores ring_rule(int F, int T, int h0, uint32_t fresh_bits, int j) {
+// the wave-uniform part: fresh_bits, j, T and F are the same in every lane of a launch's workgroup, only h0 is loaded.
+//   stale_to_j / stale: ticks 0 .. j / 0 .. T - 1 that are not fresh; fresh: tick j is; later: a tick behind j is
+struct RingTicks {
+    int stale_to_j, stale;
+    bool fresh, later;
+};
+MRCA_HD RingTicks ring_ticks(int T, uint32_t fresh_bits, int j) {
+    const uint32_t in_launch = (1u << T) - 1u, to_j = (2u << j) - 1u;
+    const uint32_t bits = fresh_bits & in_launch;
+    return RingTicks{__builtin_popcount(~bits & to_j), __builtin_popcount(~bits & in_launch), ((bits >> j) & 1u) != 0u,
+                     (bits >> j >> 1) != 0u};
+}
+MRCA_HD int ring_wrap(int h, int F) { return h >= F ? h - F : h; }
+// the slots a FRESH tick j stores when no later tick of the launch is fresh: all but the m behind the head
+MRCA_HD uint32_t ring_fresh_stores(int F, int slot, int m) {
     const uint32_t all = (1u << F) - 1u;
-    int h = h0;
-    uint32_t mine = 0u, later = 0u;
-    for (int t = 0; t < T; ++t) {
-        const bool fresh = ((fresh_bits >> t) & 1u) != 0u;
-        h = fresh ? h : (h + 1 == F ? 0 : h + 1);
-        const uint32_t w = fresh ? all : 1u << h;
-        mine = t == j ? w : mine;
-        later |= t > j ? w : 0u;
-    }
-    return RingStores{mine & ~later, h};
+    const uint32_t x = ((1u << m) - 1u) << (slot + 1);       // (slot + 1 + m <= 2 F - 1 <= 15)
+    return all & ~(x | x >> F);
+}
+MRCA_HD RingStores ring_rule(int F, int T, int h0, uint32_t fresh_bits, int j) {
+    const RingTicks u = ring_ticks(T, fresh_bits, j);
+    const int slot = ring_wrap(h0 + u.stale_to_j, F);
+    const uint32_t mine = u.fresh ? ring_fresh_stores(F, slot, T - 1 - j) : 1u << slot;
+    return RingStores{u.later ? 0u : mine, ring_wrap(h0 + u.stale, F), slot, !u.later};
 }
 
 }  // namespace mrca

@@ -171,7 +171,7 @@ struct RayIn {
 // the slot that begins j * stride bytes behind tick 0's -- its pose there, head record / goal / fresh flags / outlines at the
 // four offsets -- or, as the launch's LAST tick when last_is_env is set, the env's own fields.  The ring heads are read from
 // head_in and left in head_out by the launch's last tick: two different arrays, no workgroup reads what another one writes.
-struct RayTicksIn {         // (the kernel's arguments behind the 14 leading dwords)
+struct RayTicksIn {         // (what launch_raycast_ticks makes the kernel's arguments behind the 14 leading dwords from)
     const float4* env_head; // (filled in by launch_raycast_ticks: e.head)
     const uint8_t* head_in;
     uint8_t* head_out;

@@ -15,15 +15,20 @@ namespace {
 
 // A launch of several ticks (raycast_body<..., TICKS = true>): which tick of the launch this workgroup casts and where the
 // fresh flags of all its ticks and the two head arrays are.  The single-tick kernel passes an empty one.
-typedef __attribute__((address_space(1))) uint8_t GlobalByte;
 struct RayTick {
     int j, T;                       // this workgroup's tick of the launch's T
-    const uint8_t* fresh0;          // tick 0's fresh flags; tick t's lie t * stride bytes on ...
-    long long stride;
-    const uint8_t* fresh_env;       // ... except the last tick's when it is the env's own field (else NULL)
+    // The fresh flags of the ticks that read ring slots -- all T, or all but the last when that one reads the env's own field
+    // (last_is_env) --: tick t's lie (t - lo_tick) * stride bytes behind fresh_lo, the lowest-addressed of them, so that an
+    // unsigned 32-bit offset reaches every one (launch_raycast_ticks checks that it does).
+    const uint8_t* fresh_lo;
+    int stride, lo_tick, ring_last; // (ring_last: the last tick whose flags are in a ring slot)
+    int env_tick;                   // the tick that reads the env's own field: T - 1, or none of 0 .. 63
     const uint8_t* head_in;         // the ring heads before the launch's first tick
     uint8_t* head_out;              // ... and where its last tick leaves them (never the same array)
 };
+
+// a robot's x and y in the pose array [N][3]: a pair that is aligned like a float
+struct alignas(4) PoseXY { float x, y; };
 
 // LDS |= without a return value (ds_or_b64): nothing to wait for
 __device__ __forceinline__ void mask_or(unsigned long long* p, unsigned long long v) {
@@ -99,8 +104,14 @@ __device__ __forceinline__ void raycast_body(int only_fresh, int ray_first, int 
     int lane_zero = 0;
     if constexpr (!BIG) asm volatile("v_mov_b32 %0, 0" : "=v"(lane_zero));
     const int nv = n + lane_zero;
-    const float x = pose_p[nv * 3 + 0], y = pose_p[nv * 3 + 1];
-    const float4 hd = head_p[nv];
+    // (pose_p, head_p and the beam table are kernel arguments, uniform: every load through them is base + a 32-bit byte offset,
+    // n < 2^24 -- one global_load with the base in scalar registers, like the loads through the view)
+    // (x and y as ONE load of a pair that is aligned like a float; small worlds: the index in a vector register, a full-rate
+    // 24-bit multiply)
+    auto pose_xy = [&](int i) { return global_load<PoseXY>(pose_p, BIG ? (uint32_t)i * 12u : __umul24((uint32_t)i, 12u)); };
+    const PoseXY xy = pose_xy(nv);
+    const float x = xy.x, y = xy.y;
+    const float4 hd = global_load<float4>(head_p, (uint32_t)nv * 16u);
     const float s = hd.x, c = hd.y;
     // the preparation wave requests "its" neighbour candidate in the same memory round trip
     const int pl = tid - prep_base;
@@ -110,18 +121,24 @@ __device__ __forceinline__ void raycast_body(int only_fresh, int ray_first, int 
     float4 hj = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     int4 oj = make_int4(0, 0, 0, 0);
     if (!BIG && is_prep) {
-        xj = pose_p[jn * 3 + 0];
-        yj = pose_p[jn * 3 + 1];
-        if constexpr (raster) oj = global_load<int4>(e.outline, (uint32_t)jn * 16u);
-        else hj = head_p[jn];
+        const PoseXY pj = pose_xy(jn);
+        xj = pj.x;
+        yj = pj.y;
+        if constexpr (raster) {
+            oj = global_load<int4>(e.outline, (uint32_t)jn * 16u);
+        } else {        // (sin and cos: the half of the record the slab tests want)
+            const float2 sc = global_load<float2>(head_p, (uint32_t)jn * 16u);
+            hj.x = sc.x;
+            hj.y = sc.y;
+        }
     }
     // beam directions in the robot frame for this thread's K beams (tid + k*T)
     float bc[K], bs[K];
 #pragma unroll
     for (int k = 0; k < K; ++k) {
-        const int b = (marches ? tid : 0) + k * T;
-        bc[k] = bcos_p[b];
-        bs[k] = bsin_p[b];
+        const uint32_t boff = (uint32_t)((marches ? tid : 0) + k * T) * 4u;
+        bc[k] = global_load<float>(bcos_p, boff);
+        bs[k] = global_load<float>(bsin_p, boff);
     }
     // slot of the newest frame so far (read by every thread BEFORE the first barrier, advanced by thread 0 after it) and
     // the fresh flag: requested last, used last
@@ -130,14 +147,18 @@ __device__ __forceinline__ void raycast_body(int only_fresh, int ray_first, int 
     uint8_t fresh_byte;
     int ring_slot;
     if constexpr (TICKS) {
-        // (every lane loads -- lanes T and up tick 0's flag again, masked out at the ballot -- and through a global address:
-        // behind a branch or as a flat load the request would wait for every other one of the prologue)
-        const int lt = tid & (kWave - 1);
-        const int t = lt < mt.T ? lt : 0;
-        const bool own = mt.fresh_env != nullptr && t == mt.T - 1;
-        const unsigned long long fa = own ? (unsigned long long)mt.fresh_env : (unsigned long long)mt.fresh0 + (long long)t * mt.stride;
-        fresh_byte = *reinterpret_cast<const GlobalByte*>(fa + (unsigned long long)n);
-        ring_slot = mt.head_in[nv];
+        // (every lane loads -- the lanes behind the last ring tick that tick's flag again: ring_rule ignores their bits -- and
+        // through a global address: behind a lane mask or as a flat load the request would wait for every other one of the
+        // prologue.  The offset wraps to (t - lo_tick) * stride + n >= 0 whatever the sign of stride.)
+        const uint32_t lt = (uint32_t)tid & (uint32_t)(kWave - 1);
+        const uint32_t t = lt < (uint32_t)mt.ring_last ? lt : (uint32_t)mt.ring_last;
+        fresh_byte = global_load<uint8_t>(mt.fresh_lo, (t - (uint32_t)mt.lo_tick) * (uint32_t)mt.stride + (uint32_t)n);
+        // (the pass's last launch of a range: lane T - 1 takes the env's own flag instead.  Every launch requests it -- one
+        // line per wave -- and no lane of another launch takes it: a second load and a select, no branch to hold up the
+        // requests behind it and no lane mask)
+        const uint8_t env_byte = global_load<uint8_t>(e.fresh, (uint32_t)nv);
+        fresh_byte = lt == (uint32_t)mt.env_tick ? env_byte : fresh_byte;
+        ring_slot = global_load<uint8_t>(mt.head_in, (uint32_t)nv);
     } else {
         fresh_byte = e.fresh[n];
         ring_slot = ring_head_p[n];
@@ -186,8 +207,9 @@ __device__ __forceinline__ void raycast_body(int only_fresh, int ray_first, int 
             float4 chj = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
             int lo = 0, hi = -1;
             if (j >= 0 && j != n && j / R_ == world) {
-                cxj = pose_p[j * 3 + 0];
-                cyj = pose_p[j * 3 + 1];
+                const PoseXY pj = pose_xy(j);
+                cxj = pj.x;
+                cyj = pj.y;
                 // a bucket may hold other cells too (hash collisions) and the same bucket may serve two of the nine
                 // cells: a robot counts only for the cell it really is in, so nobody is listed twice
                 if (hash_cell_coord(cxj, kLidarCell) == qx && hash_cell_coord(cyj, kLidarCell) == qy) {
@@ -196,7 +218,7 @@ __device__ __forceinline__ void raycast_body(int only_fresh, int ray_first, int 
                         beam_interval(ddx * c + ddy * s, ddy * c - ddx * s, e.B, e.beam_step, e.beam_inv_step, e.lidar_radius,
                                       e.lidar_near, &lo, &hi);
                         keep = lo <= hi;
-                        if (keep) chj = head_p[j];
+                        if (keep) chj = global_load<float4>(head_p, (uint32_t)j * 16u);
                     }
                 }
             }
@@ -377,47 +399,72 @@ __device__ __forceinline__ void raycast_body(int only_fresh, int ray_first, int 
         unsigned long long* hit_row = e.hit_bits + (size_t)row * (uint32_t)words;
         int new_slot;
         bool fresh;
-        uint32_t stores = 0u;     // TICKS: the slots this tick of the launch stores (ring_rule)
-        int head_after = 0;       // TICKS: the head behind the launch's last tick
+        uint32_t stores = 0u;     // TICKS: the slots a fresh tick of the launch stores (ring_rule)
+        bool any = true;          // TICKS: this tick stores a slot at all (no later tick of the launch restarts the robot)
         if constexpr (TICKS) {
-            // (the head stays in a vector register: the rule's few operations per tick go to the vector unit, see the note on
-            // scalar instructions above)
-            const uint32_t fresh_bits = (uint32_t)__ballot(fresh_byte != 0 && (tid & (kWave - 1)) < mt.T);
-            const RingStores rs = ring_rule(e.F, mt.T, ring_slot, fresh_bits, mt.j);
-            stores = (uint32_t)__builtin_amdgcn_readfirstlane((int)rs.stores);
-            head_after = rs.head;
-            fresh = ((fresh_bits >> mt.j) & 1u) != 0u;
-            new_slot = __ffs((int)stores) - 1;      // (a tick that is not fresh writes one slot, or none that survives)
+            // ring_rule in its parts.  What hangs on the flags, j and T alone is wave-uniform and the compiler leaves it on the
+            // scalar unit: the two tests the branches below want there anyway and the mask of the ticks up to j, about eight instructions.
+            // What hangs on the head stays on the vector unit, where the load left it -- an add, a wrap, and the slot goes into
+            // the store's offset as it is --: a scalar instruction is priced at two vector ones (see above), and the head on the
+            // scalar side would cost a v_readfirstlane_b32 and the offset's multiply there.  The launch's last tick leaves the
+            // head behind itself: its `slot` (ring_rule's head for j = T - 1).  Only a restart wants the store mask.
+            const uint32_t fresh_bits = (uint32_t)__ballot(fresh_byte != 0);
+            const RingTicks u = ring_ticks(mt.T, fresh_bits, mt.j);
+            new_slot = ring_wrap(ring_slot + u.stale_to_j, e.F);
+            fresh = u.fresh;
+            any = !u.later;
+            if (fresh && any) stores = (uint32_t)__builtin_amdgcn_readfirstlane((int)ring_fresh_stores(e.F, new_slot, mt.T - 1 - mt.j));
         } else {
             new_slot = ring_slot + 1 == e.F ? 0 : ring_slot + 1;
             fresh = __builtin_amdgcn_readfirstlane((int)fresh_byte) != 0;
         }
+        // (what each beam stores first, then ONE test of the store selection around the K beams' stores, and the K words of hit
+        // bits under ONE lane mask behind the K rows: tested per beam, the compiler repeated the scalar compares and branches K
+        // times and split a wave's row store in two around the word's)
+        float rk[K];
+        unsigned long long hmk[K];
 #pragma unroll
         for (int k = 0; k < K; ++k) {
-            const int b = tid + k * T;
             // (the range as the march returned it, the sign of a zero included: a beam that enters an occupied cell at boundary
             // time -0 -- a sensor exactly on the face of a wall, looking into it -- has range -0.0 in the oracle, and a caller that
             // compares scans bit for bit sees it here too.  The readers that normalise take |x|.)
-            const float r = rng[k] < kRangeMax ? rng[k] : kRangeMax;
+            rk[k] = rng[k] < kRangeMax ? rng[k] : kRangeMax;
             // what the beam hit: one bit per beam beside the ring (MRCA_F_HIT_BITS), set = another robot.  stageros casts
             // Stage's return value to uint8 for LaserScan.intensities (stageros.cpp:506): 1 floorplan, 0 robot or miss.  A wave
             // holds 64 consecutive beams (T is a multiple of 64: product_ray_shift), so its ballot IS the row's word b >> 6.
             // (ABI 4-5 kept the flag in the range's sign bit: a reader that forgot |x| got negative ranges.)
-            const unsigned long long hm = __ballot(from_robot[k] && rng[k] < kRangeMax);
-            const bool word_lane = (tid & (kWave - 1)) == 0;
+            hmk[k] = __ballot(from_robot[k] && rng[k] < kRangeMax);
+        }
+        const bool word_lane = (tid & (kWave - 1)) == 0;
+        {
             // (nontemporal stores: the launch does not read its rows again.  Measured A/B on one box, round 4: 21.7 us with
             // them, 22.9 us with plain stores (profiles/r04_g_ab_nontemporal_row_stores.txt) -- although FETCH_SIZE does not
             // move, 2502 vs 2504 KiB: what they relieve is the write path, not the free-rectangle field's residency)
             if (fresh) {     // deque([obs] * F), ppo_stage1.py:59-60: every slot, the head stays where it is
                 for (int f = 0; f < e.F; ++f) {
                     if (TICKS && !((stores >> f) & 1u)) continue;       // a later tick of the launch writes this slot
-                    global_store_nt(ring_row, (uint32_t)(f * e.B + b) * 4u, r);
-                    if (word_lane) global_store(hit_row, (uint32_t)(f * words + (b >> 6)) * 8u, hm);
+#pragma unroll
+                    for (int k = 0; k < K; ++k) global_store_nt(ring_row, (uint32_t)(f * e.B + tid + k * T) * 4u, rk[k]);
+                    if (word_lane) {
+#pragma unroll
+                        for (int k = 0; k < K; ++k) global_store(hit_row, (uint32_t)(f * words + ((tid + k * T) >> 6)) * 8u, hmk[k]);
+                    }
                 }
-            } else if (!TICKS || stores) {
-                global_store_nt(ring_row, (uint32_t)(new_slot * e.B + b) * 4u, r);
-                if (word_lane) global_store(hit_row, (uint32_t)(new_slot * words + (b >> 6)) * 8u, hm);
+            } else if (any) {
+                // (TICKS: the slot is a vector register's, below 8 -- a 24-bit multiply, full rate)
+                const uint32_t at = TICKS ? __umul24((uint32_t)new_slot, (uint32_t)e.B) : (uint32_t)(new_slot * e.B);
+#pragma unroll
+                for (int k = 0; k < K; ++k) global_store_nt(ring_row, (at + (uint32_t)(tid + k * T)) * 4u, rk[k]);
+                if (word_lane) {
+#pragma unroll
+                    for (int k = 0; k < K; ++k) global_store(hit_row, ((at >> 6) + (uint32_t)((tid + k * T) >> 6)) * 8u, hmk[k]);
+                }
             }
+        }
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            const int b = tid + k * T;
+            const float r = rk[k];
             // lazy_obs = 0: the two reference-shaped views of this robot, formed here instead of by a materialize_kernel launch
             // behind every ray cast (get_laser_observation, stage_world1.py:127-141: the newest scan; the stack in deque order,
             // x / 6 - 0.5) -- the same numbers: norm_obs of the ring's rows, the older ones as earlier launches stored them.  The
@@ -443,7 +490,7 @@ __device__ __forceinline__ void raycast_body(int only_fresh, int ray_first, int 
             }
         }
         if constexpr (TICKS) {
-            if (tid == 0 && mt.j == mt.T - 1) global_store(mt.head_out, (uint32_t)n, (uint8_t)head_after);
+            if (tid == 0 && mt.j == mt.T - 1) global_store(mt.head_out, (uint32_t)n, (uint8_t)new_slot);
         } else {
             if (tid == 0 && !fresh) global_store(ring_head_p, (uint32_t)n, (uint8_t)new_slot);
         }

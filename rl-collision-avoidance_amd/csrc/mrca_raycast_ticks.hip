@@ -23,20 +23,34 @@ namespace mrca {
 
 namespace {
 
+// The kernel's arguments behind the 14 leading dwords: RayTicksIn with the fresh flags as the base the kernel addresses them
+// from (RayTick::fresh_lo) instead of their offset in a slot -- the same 40 bytes.
+struct TicksIn {
+    const float4* env_head;
+    const uint8_t* head_in;
+    uint8_t* head_out;
+    const uint8_t* fresh_lo;
+    uint32_t off_goal, off_outline;
+#if defined(MRCA_PROFILING)
+    unsigned long long* launch_stamps;
+    int32_t launch_slot;
+#endif
+};
+
 // The leading 14 dwords (preloaded into SGPRs) are what the prologue needs first: the launch's range, where tick j's pose and
 // head record are, the beam table, the env's own pose; the env's head record -- the last tick's second load -- comes with the
-// rest.  `ticks`: T | last_is_env << 8.  104 bytes of arguments (a launch costs the host more from 128 bytes on,
-// tools/launch_cost_probe.hip).
+// rest.  `ticks`: T | env_tick << 8 | lo_tick << 16 | ring_last << 24 (RayTick).  104 bytes of arguments (a launch costs the
+// host more from 128 bytes on, tools/launch_cost_probe.hip).
 template <int K, bool SEQ, int RKW>
-__global__ __launch_bounds__(1024, (RKW == 4 ? 8 : 1)) void raycast_ticks_kernel(int ray_first, int ray_count, int R_, int ticks,
+__global__ __launch_bounds__(1024, (RKW == 4 ? 8 : 1)) void raycast_ticks_kernel(int ray_first, int ray_count, int R_, uint32_t ticks,
                                                        const char* __restrict__ slot0, int stride, uint32_t off_head,
                                                        const float* __restrict__ bcos_p, const float* __restrict__ bsin_p,
                                                        const float* __restrict__ env_pose, const EnvView* __restrict__ view_p,
-                                                       RayTicksIn in) {
+                                                       TicksIn in) {
     EnvView e = *view_p;        // (the env's view from device memory: its pose / head / goal / fresh / outline are slot 0's)
     const int T = ticks & 0xff, j = blockIdx.y;
-    const bool last_is_env = (ticks >> 8) != 0;
-    const bool own = last_is_env && j == T - 1;          // workgroup-uniform: this tick reads the env's own fields
+    const int env_tick = (ticks >> 8) & 0xff;
+    const bool own = j == env_tick;                      // workgroup-uniform: this tick reads the env's own fields
     const char* slot = slot0 + (long long)j * stride;
     const float* pose_p = own ? env_pose : reinterpret_cast<const float*>(slot);
     const float4* head_p = own ? in.env_head : reinterpret_cast<const float4*>(slot + off_head);
@@ -46,8 +60,7 @@ __global__ __launch_bounds__(1024, (RKW == 4 ? 8 : 1)) void raycast_ticks_kernel
     }
     e.pose = const_cast<float*>(pose_p);
     e.head = const_cast<float4*>(head_p);
-    const RayTick mt{j, T, reinterpret_cast<const uint8_t*>(slot0 + in.off_fresh), (long long)stride,
-                     last_is_env ? e.fresh : nullptr, in.head_in, in.head_out};
+    const RayTick mt{j, T, in.fresh_lo, stride, (int)((ticks >> 16) & 0xff), (int)(ticks >> 24), env_tick, in.head_in, in.head_out};
 #if defined(MRCA_PROFILING)
     e.launch_stamps = in.launch_stamps;
     e.launch_slot = in.launch_slot;
@@ -63,9 +76,26 @@ void launch_raycast_ticks(const EnvView& e, const RayTicks& t, hipStream_t s) {
     if (e.ray_count <= 0 || t.ticks <= 0) return;
     const RayShape shape = ray_shape(e);
     assert(!shape.big);
-    const int ticks = t.ticks | (t.last_is_env ? 1 << 8 : 0);
-    RayTicksIn in = t.in;
+    // The fresh flags of the launch's ticks that read ring slots, addressed from the lowest of them (RayTick::fresh_lo): every
+    // offset the kernel forms, (t - lo_tick) * stride + n, is below (ticks - 1) * |stride| + N, which mrca_create holds below
+    // 2^32 for every launch of several ticks it allows.
+    assert(t.ticks >= 2 && t.ticks <= 8);
+    const int ring_last = t.ticks - 1 - (t.last_is_env ? 1 : 0), lo_tick = t.stride < 0 ? ring_last : 0;
+    assert((unsigned long long)ring_last * (unsigned long long)(t.stride < 0 ? -(long long)t.stride : (long long)t.stride) +
+               (unsigned long long)(e.ray_first + e.ray_count) <= 0xffffffffull);
+    const uint32_t ticks = (uint32_t)t.ticks | (t.last_is_env ? (uint32_t)t.ticks - 1u : 0xffu) << 8 | (uint32_t)lo_tick << 16 | (uint32_t)ring_last << 24;
+    TicksIn in{};
     in.env_head = e.head;
+    in.head_in = t.in.head_in;
+    in.head_out = t.in.head_out;
+    in.fresh_lo = reinterpret_cast<const uint8_t*>(t.slot0) + t.in.off_fresh + (long long)lo_tick * t.stride;
+    in.off_goal = t.in.off_goal;
+    in.off_outline = t.in.off_outline;
+#if defined(MRCA_PROFILING)
+    in.launch_stamps = t.in.launch_stamps;
+    in.launch_slot = t.in.launch_slot;
+#endif
+    static_assert(sizeof(TicksIn) <= sizeof(RayTicksIn), "the ray cast of several ticks: no more than 104 bytes of arguments");
     with_ray_variant(shape, [&](auto v) {
         using V = decltype(v);
         hipLaunchKernelGGL((raycast_ticks_kernel<V::K, V::SEQ, V::RKW>), dim3(e.ray_count, t.ticks), dim3(shape.threads),
