@@ -1011,6 +1011,43 @@ MRCA_HD void beam_interval(float lx, float ly, int beams, int* lo, int* hi) {
     beam_interval(lx, ly, beams, kPi / (float)(beams - 1), (float)(beams - 1) / kPi, 0.2917f, 0.30f, lo, hi);
 }
 
+// The slab tests of a small world's ray cast, PAIR-major (raycast_body, exact rectangles): the kept neighbours' intervals
+// [lo_k, hi_k], laid end to end in the order of the compacted list, number the (neighbour, beam) pairs 0 .. P - 1 -- neighbour k
+// owns start_k .. start_k + (hi_k - lo_k), start_k the exclusive prefix sum of the lengths -- and thread t of the workgroup tests
+// pairs t, t + threads, ...: a wave tests 64 pairs per trip whichever beams they belong to, where the beam-major loop ran as many
+// trips as its busiest beam had neighbours.  The enumeration in its parts, swept on the host by tests/test_slab_pairs_host.py:
+//   lane_scan_step     one doubling step (d = 1, 2, 4 .. 32) of the inclusive prefix sum over a wave's 64 lanes: `below` is the
+//                      sum d lanes down (anything in the lanes under d).  A dropped candidate's length is 0, so the sum over the
+//                      LANES is the sum over the compacted list, which keeps the lanes' order;
+//   slab_pair_locate   the neighbour q pair p < P belongs to: the last k < cnt with start_k <= p (start_0 = 0; the starts do not
+//                      decrease).  start_of(k) is read for k < cnt rounded up to a multiple of eight (eight even of an empty
+//                      list), eight per trip and no tail: the list's slots behind the cnt-th hold kSlabPairPad, above every p;
+//   slab_pair_beam     ... and its beam.
+// For p >= P locate names the last neighbour and a beam behind its interval: such a pair is never formed (p < P is the loop's test).
+constexpr int kSlabPairPad = 0x7fffffff;
+MRCA_HD int lane_scan_step(int sum, int below, int lane, int d) { return lane >= d ? sum + below : sum; }
+template <class Starts>
+MRCA_HD int slab_pair_locate(int p, int cnt, Starts start_of) {
+    int q = -1;
+    int k0 = 0;
+    // (a list of up to eight, nearly every one of a Stage world, is straight-line code: eight reads, one wait.  Left to itself
+    // the compiler interleaves two and four trips of the loop behind that, and a wave pays some twenty scalar instructions
+    // of trip-count arithmetic for a loop it does not enter.)
+#pragma clang loop unroll(disable) vectorize(disable) interleave(disable)
+    do {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) q += start_of(k0 + i) <= p ? 1 : 0;
+        k0 += 8;
+    } while (k0 < cnt);
+    return q;
+}
+MRCA_HD int slab_pair_beam(int p, int lo_q, int start_q) { return lo_q + (p - start_q); }
+// The pair-major form merges a pair's entry distance into the beam's marched range with a SIGNED-integer minimum over the
+// bit patterns: ray_box_local returns +0 .. +inf (never a NaN, never -0), ordered as integers like as floats, and the march's
+// -0.0 (a sensor on the face of a wall, looking into it) is the smallest integer -- it survives every merge, as `t < -0.0` is
+// never true in the running minimum `r = t < r ? t : r` this replaces.  (An unsigned or a float minimum would make it +0.)
+MRCA_HD int32_t slab_pair_merge(int32_t marched_bits, int32_t t_bits) { return t_bits < marched_bits ? t_bits : marched_bits; }
+
 // ray_outline_entry<4> again, rearranged for the instruction count (what the fidelity ray cast runs at Stage's 0.2 m: 286 -> ~185
 // vector instructions per tested (beam, neighbour) pair).  Same times, same comparisons, same result:
 //   * the window's columns and rows are taken in WALK order (column w = the w-th the ray can reach: ax + w going right, ax + 3 - w

@@ -82,6 +82,12 @@ __device__ __forceinline__ void raycast_body(int only_fresh, int ray_first, int 
     int* nb_count = reinterpret_cast<int*>(nbi + kWave);
     unsigned long long* nbmask = reinterpret_cast<unsigned long long*>(nb_count + 4);   // [B] neighbours per beam
     int* nb_more = nb_count + 1;                                      // big worlds: another chunk of neighbours follows
+    // Small worlds' exact rectangles test the (neighbour, beam) pairs dealt densely to the threads instead of each thread its
+    // beams' neighbours (slab_pair_locate, mrca_device.h).  Then nbi[k] is (lo_k, start_k), nb_count[2] the number of pairs, and
+    // the masks' space holds the beams' ranges, 4 of its 8 bytes per beam: the marched range's bit pattern, which the pairs'
+    // entry distances are merged into (slab_pair_merge).
+    constexpr bool PAIRS = !BIG && RKW == 0;
+    int* rmin = reinterpret_cast<int*>(nb_count + 4);                 // [B]
     // fidelity mode (never in big worlds): the neighbours' outline records
     constexpr bool raster = RKW > 0 && !BIG;
     int4* nbo = reinterpret_cast<int4*>(nbmask + e.B);   // [64] OutlineBits as (ax, ay, lo, hi)
@@ -249,7 +255,9 @@ __device__ __forceinline__ void raycast_body(int only_fresh, int ray_first, int 
       if constexpr (BIG) {
         big_chunk();
       } else {
-        for (int b = pl; b < e.B; b += kWave) nbmask[b] = 0ull;
+        if constexpr (!PAIRS) {
+            for (int b = pl; b < e.B; b += kWave) nbmask[b] = 0ull;
+        }
         const float ddx = xj - x, ddy = yj - y;
         // conservative cull: a hit below 6 m needs the centre within 6 + circumradius(0.2907) m (fidelity mode: + one
         // raster-cell diagonal -- what is tested there are the robot's outline CELLS)
@@ -261,31 +269,46 @@ __device__ __forceinline__ void raycast_body(int only_fresh, int ray_first, int 
             keep = lo <= hi;
         }
         const unsigned long long m = __ballot(keep);
-        if (keep) {
-            const int idx = __popcll(m & ((1ull << pl) - 1ull));
-            // the slab tests want the lidar's origin in the neighbour's frame (once per neighbour, not per beam); the
-            // fidelity mode's closed form wants the neighbour's outline record
-            if constexpr (raster) {
-                nbo[idx] = oj;
-            } else {
-                float olx, oly;
+        if constexpr (PAIRS) {
+            // pair-major slab tests (slab_pair_locate, mrca_device.h): the kept neighbours' intervals laid end to end number the
+            // (neighbour, beam) pairs, and neighbour k's record is (lo_k, start_k), the exclusive prefix sum of the lengths before
+            // it.  The sum runs over the LANES -- a dropped candidate adds nothing, and the ballot's compaction keeps the lanes'
+            // order -- in six doubling steps.  The dropped lanes fill the list's slots behind the kept ones with the pad that
+            // ends the search, so that it reads the starts eight at a time without a tail.
+            const int below = __popcll(m & ((1ull << pl) - 1ull));
+            const int kept = __popcll(m);
+            const int len = keep ? hi - lo + 1 : 0;
+            int end = len;
+#pragma unroll
+            for (int d = 1; d < kWave; d <<= 1) end = lane_scan_step(end, __shfl_up(end, d, kWave), pl, d);
+            if (keep) {
+                float olx, oly;         // the lidar's origin in the neighbour's frame: once per neighbour, not per pair
                 ray_box_origin(x, y, xj, yj, hj.x, hj.y, &olx, &oly);
-                nb[idx] = make_float4(olx, oly, hj.x, hj.y);
+                nb[below] = make_float4(olx, oly, hj.x, hj.y);
             }
-            nbi[idx] = make_int2(lo, hi);
-        }
-        const int cnt0 = MRCA_DBG(e, 1) ? 0 : __popcll(m);
-        if (pl == 0) *nb_count = cnt0;
-        // scatter: bit k of nbmask[b] = "neighbour k can touch beam b".  ds_or_b64 without a return value: the wave
-        // fires one per neighbour and moves on (as a read-modify-write every neighbour cost an LDS round trip, ~2 000
-        // of the 5 600 ticks wave 0 spent preparing, profiles/r03/r03_k_ablate_raycast_phase_stamps.txt).
-        for (int k = 0; k < cnt0; ++k) {
-            const int2 iv = nbi[k];
-            for (int b = iv.x + pl; b <= iv.y; b += kWave) mask_or(&nbmask[b], 1ull << k);
+            nbi[keep ? below : kept + (pl - below)] = make_int2(lo, keep ? end - len : kSlabPairPad);
+            if (pl == 0) nb_count[0] = MRCA_DBG(e, 1) ? 0 : kept;
+            if (pl == kWave - 1) nb_count[2] = end;       // P, the number of pairs
+        } else {        // the raster lidar: beam-major, a mask of neighbours per beam
+            if (keep) {
+                const int idx = __popcll(m & ((1ull << pl) - 1ull));
+                // the fidelity mode's closed form wants the neighbour's outline record
+                nbo[idx] = oj;
+                nbi[idx] = make_int2(lo, hi);
+            }
+            const int cnt0 = MRCA_DBG(e, 1) ? 0 : __popcll(m);
+            if (pl == 0) *nb_count = cnt0;
+            // scatter: bit k of nbmask[b] = "neighbour k can touch beam b".  ds_or_b64 without a return value: the wave
+            // fires one per neighbour and moves on (as a read-modify-write every neighbour cost an LDS round trip, ~2 000
+            // of the 5 600 ticks wave 0 spent preparing, profiles/r03/r03_k_ablate_raycast_phase_stamps.txt).
+            for (int k = 0; k < cnt0; ++k) {
+                const int2 iv = nbi[k];
+                for (int b = iv.x + pl; b <= iv.y; b += kWave) mask_or(&nbmask[b], 1ull << k);
+            }
         }
       }
     }
-    MRCA_RSTAMP(2);     // wave 0: neighbour list and per-beam masks built
+    MRCA_RSTAMP(2);     // wave 0: neighbour list and the pairs' starts (beam-major: the per-beam masks) built
     // --- the march: K beams per thread in lock step
     float dx[K], dy[K], rng[K];
     bool from_robot[K];        // the range is a return from another robot (ranger_return 0.5: LaserScan intensity 0)
@@ -329,61 +352,100 @@ __device__ __forceinline__ void raycast_body(int only_fresh, int ray_first, int 
         }
     }
     MRCA_RSTAMP(3);     // this wave's beams marched
+    if constexpr (PAIRS) {      // what the pairs' entry distances are merged into: behind the same barrier as the list
+        if (marches) {
+#pragma unroll
+            for (int k = 0; k < K; ++k) rmin[tid + k * T] = __float_as_int(rng[k]);
+        }
+    }
     __syncthreads();  // neighbour list ready (the preparation wave built it while the others marched)
     MRCA_RSTAMP(4);     // through the barrier / past the flag
     if constexpr (!BIG) {
         if (!marches) return;  // the dedicated preparation wave is done (whole wave: the barrier below counts live waves)
     }
-    for (;;) {
-        const int cnt = *nb_count;
-        const int more = BIG ? *nb_more : 0;
-        if (marches) {
+    if constexpr (PAIRS) {
+        // (cnt and P are the workgroup's: on the scalar side, so that the search's trips and the branch around the second barrier
+        // are uniform to the compiler too)
+        const int cnt = __builtin_amdgcn_readfirstlane(nb_count[0]);
+        if (cnt > 0) {
+            const int P = __builtin_amdgcn_readfirstlane(nb_count[2]);
+            // thread tid tests pairs tid, tid + T, ...: a wave whose lowest pair is behind the last one has no lane in the loop
+            for (int p = tid; p < P; p += T) {
+                const int q = slab_pair_locate(p, cnt, [&](int k) { return nbi[k].y; });
+                const int2 iq = nbi[q];
+                const float4 nbq = nb[q];
+                const int b = slab_pair_beam(p, iq.x, iq.y);
+                // the beam's direction as its owner formed it above: the same loads, the same separately rounded operations
+                const float pc = global_load<float>(bcos_p, (uint32_t)b * 4u), ps = global_load<float>(bsin_p, (uint32_t)b * 4u);
+                const float t = ray_box_local(nbq.x, nbq.y, c * pc - s * ps, s * pc + c * ps, nbq.z, nbq.w);
+                // slab_pair_merge, as ds_min_i32 without a return value: nothing to wait for
+                (void)__hip_atomic_fetch_min(&rmin[b], __float_as_int(t), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            }
+            __syncthreads();      // every pair merged (the dedicated preparation wave has left: the barrier counts live waves)
+            // r = min(marched, the t of every pair of the beam), and `r < marched` is the flag of the running minimum
+            // `from_robot |= t < r; r = t < r ? t : r` over the same t in any order: that loop sets the flag at some t below the
+            // minimum so far, which is never above marched -- so only if the least t is below marched; and the first t below
+            // marched in its order finds the minimum so far still at marched, and sets it.  Neither is true of marched = -0.0.
 #pragma unroll
             for (int k = 0; k < K; ++k) {
-                const int b = tid + k * T;
-                float r = rng[k];
-                unsigned long long m = cnt > 0 ? nbmask[b] : 0ull;
-                if constexpr (raster) {
-                    // fidelity mode: the entry time of the first raster cell of each flagged neighbour's outline the beam's
-                    // walk visits -- in closed form, the same times grid_march's walk over the raster would compare
-                    if (m) {
-                        const float fxr = x * e.raster_inv, fyr = y * e.raster_inv;
-                        const int ixr = (int)floorf(fxr), iyr = (int)floorf(fyr);
-                        const float tmax_c = kRangeMax * e.raster_inv;
-                        const float inv_dx = dx[k] != 0.0f ? rcp_exact(dx[k]) : kInf;
-                        const float inv_dy = dy[k] != 0.0f ? rcp_exact(dy[k]) : kInf;
-                        // (the 4 x 4 form: an axis the ray never steps along gets origin -inf, see ray_outline_entry4)
-                        const float fxe = dx[k] != 0.0f ? fxr : -kInf, fye = dy[k] != 0.0f ? fyr : -kInf;
-                        const bool xpos = dx[k] > 0.0f, ypos = dy[k] > 0.0f;
-                        do {
-                            const int q = __ffsll((long long)m) - 1;
-                            m &= m - 1;
-                            const int4 oq = nbo[q];
-                            const OutlineBits ob{oq.x, oq.y, (uint32_t)oq.z, (uint32_t)oq.w};
-                            const float tc = RKW == 4 ? ray_outline_entry4(fxe, fye, ixr, iyr, xpos, ypos, inv_dx, inv_dy, ob)
-                                                      : ray_outline_entry<RKW>(fxr, fyr, ixr, iyr, dx[k], dy[k], inv_dx, inv_dy, ob);
-                            const float t = tc < tmax_c ? tc * e.raster_res : kInf;
-                            from_robot[k] = from_robot[k] || t < r;
-                            r = t < r ? t : r;
-                        } while (m);
-                    }
-                } else {
-                    while (m) {
-                        const int q = __ffsll((long long)m) - 1;
-                        m &= m - 1;
-                        const float4 nbq = nb[q];
-                        const float t = ray_box_local(nbq.x, nbq.y, dx[k], dy[k], nbq.z, nbq.w);
-                        from_robot[k] = from_robot[k] || t < r;
-                        r = t < r ? t : r;
-                    }
-                }
+                const float r = __int_as_float(rmin[tid + k * T]);
+                from_robot[k] = r < rng[k];
                 rng[k] = r;
             }
         }
-        if (!more) break;
-        __syncthreads();          // everybody is through with this chunk ...
-        if (is_prep) big_chunk();
-        __syncthreads();          // ... and the next one is ready
+    } else {        // big worlds' chunks and the raster lidar: beam-major, each thread its beams' flagged neighbours
+        for (;;) {
+            const int cnt = *nb_count;
+            const int more = BIG ? *nb_more : 0;
+            if (marches) {
+#pragma unroll
+                for (int k = 0; k < K; ++k) {
+                    const int b = tid + k * T;
+                    float r = rng[k];
+                    unsigned long long m = cnt > 0 ? nbmask[b] : 0ull;
+                    if constexpr (raster) {
+                        // fidelity mode: the entry time of the first raster cell of each flagged neighbour's outline the beam's
+                        // walk visits -- in closed form, the same times grid_march's walk over the raster would compare
+                        if (m) {
+                            const float fxr = x * e.raster_inv, fyr = y * e.raster_inv;
+                            const int ixr = (int)floorf(fxr), iyr = (int)floorf(fyr);
+                            const float tmax_c = kRangeMax * e.raster_inv;
+                            const float inv_dx = dx[k] != 0.0f ? rcp_exact(dx[k]) : kInf;
+                            const float inv_dy = dy[k] != 0.0f ? rcp_exact(dy[k]) : kInf;
+                            // (the 4 x 4 form: an axis the ray never steps along gets origin -inf, see ray_outline_entry4)
+                            const float fxe = dx[k] != 0.0f ? fxr : -kInf, fye = dy[k] != 0.0f ? fyr : -kInf;
+                            const bool xpos = dx[k] > 0.0f, ypos = dy[k] > 0.0f;
+                            do {
+                                const int q = __ffsll((long long)m) - 1;
+                                m &= m - 1;
+                                const int4 oq = nbo[q];
+                                const OutlineBits ob{oq.x, oq.y, (uint32_t)oq.z, (uint32_t)oq.w};
+                                const float tc = RKW == 4
+                                                     ? ray_outline_entry4(fxe, fye, ixr, iyr, xpos, ypos, inv_dx, inv_dy, ob)
+                                                     : ray_outline_entry<RKW>(fxr, fyr, ixr, iyr, dx[k], dy[k], inv_dx, inv_dy, ob);
+                                const float t = tc < tmax_c ? tc * e.raster_res : kInf;
+                                from_robot[k] = from_robot[k] || t < r;
+                                r = t < r ? t : r;
+                            } while (m);
+                        }
+                    } else {
+                        while (m) {
+                            const int q = __ffsll((long long)m) - 1;
+                            m &= m - 1;
+                            const float4 nbq = nb[q];
+                            const float t = ray_box_local(nbq.x, nbq.y, dx[k], dy[k], nbq.z, nbq.w);
+                            from_robot[k] = from_robot[k] || t < r;
+                            r = t < r ? t : r;
+                        }
+                    }
+                    rng[k] = r;
+                }
+            }
+            if (!more) break;
+            __syncthreads();          // everybody is through with this chunk ...
+            if (is_prep) big_chunk();
+            __syncthreads();          // ... and the next one is ready
+        }
     }
     if (!marches) return;
     MRCA_RSTAMP(5);     // neighbour slab tests done

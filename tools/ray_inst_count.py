@@ -9,7 +9,9 @@ mrca_ray_shape.h itself, compiled for the host; --all: every instantiation):
 
   * the kernel's static counts: vector instructions, scalar-side instructions, and the flat / global / LDS ones among them;
   * the same for each MARCH loop (an innermost loop that loads a 16-bit field entry) and for the SLAB loop (the innermost loop
-    that reads a neighbour's 16-byte record from LDS, stores nothing and loads nothing from global memory).
+    that reads a neighbour's 16-byte record from LDS, stores nothing and loads nothing from global memory) of the beam-major
+    kernels; for the pair-major ones (small worlds, exact rectangles) the PAIR loop -- the one that merges with ds_min_i32 --
+    without and beside the SEARCH loop inside it (slab_pair_locate: the list's starts, read two at a time).
 
 Instructions are classed by mnemonic prefix only: v_* is vector; s_* is the scalar side (s_nop, s_waitcnt and branches
 included: each takes an issue slot of the wave); flat_*, global_*, ds_*, buffer_*, scratch_* are memory instructions, listed by
@@ -91,7 +93,7 @@ class Count:
     def __init__(self):
         self.v = self.s = 0
         self.mem = dict.fromkeys(MEM, 0)
-        self.ushort = self.b128 = self.stores = 0
+        self.ushort = self.b128 = self.stores = self.ds_min = self.read2 = 0
 
     def add(self, op):
         if op.startswith("v_"):
@@ -104,6 +106,8 @@ class Count:
                     self.mem[c] += 1
             self.ushort += op.endswith("_load_ushort")
             self.b128 += op == "ds_read_b128"
+            self.ds_min += op == "ds_min_i32"
+            self.read2 += op == "ds_read2_b32"
             self.stores += "_store_" in op or op.startswith("ds_write") or op.startswith("ds_or")
 
     def __str__(self):
@@ -113,11 +117,11 @@ class Count:
 
 def kernels(lines):
     """{mangled name: (Count of the kernel, {innermost loop header: Count})}"""
-    out, name, total, loops, loop = {}, None, None, None, None
+    out, name, total, loops, loop, label = {}, None, None, None, None, None
     for line in lines:
         m = re.match(r"(_Z\w+):", line)
         if m:
-            name, total, loops, loop = m.group(1), Count(), {}, None
+            name, total, loops, loop, label = m.group(1), Count(), {}, None, None
             continue
         if name is None:
             continue
@@ -131,6 +135,11 @@ def kernels(lines):
             note = b.group(2) or ""
             h = re.search(r"Header=BB\d+_(\d+)", note)
             loop = h.group(1) if h else (b.group(1) if "Loop Header" in note else None)
+            label = b.group(1)
+            continue
+        # (the header of a loop INSIDE another one says so on the comment line below its label: `; =>  This Inner Loop Header`)
+        if label is not None and re.match(r"\s*;\s*=>\s*This Inner Loop Header", line):
+            loop = label
             continue
         i = re.match(r"\t([a-z]\w+)", line)
         if not i or line.startswith("\t."):
@@ -169,6 +178,14 @@ def main():
                     print("    march loop %d%s %s" % (k, " (%d beams in lock step)" % c.ushort if c.ushort > 1 else "", c))
                 for c in slab:
                     print("    slab loop   %s" % c)
+                # pair-major slab tests: the loop that merges with ds_min_i32 (counted without the search inside it) and the
+                # search, the loop inside it that reads the list's starts two at a time
+                for c in loops.values():
+                    if c.ds_min:
+                        print("    pair loop   %s  (without the search)" % c)
+                for c in loops.values():
+                    if c.read2 and not c.ds_min and not c.stores and not c.ushort and not c.mem["global"]:
+                        print("    pair search %s" % c)
         # (a shape the header selects and neither source instantiates would be a launch without a kernel)
         missing = sorted(product - compiled)
         if missing:
