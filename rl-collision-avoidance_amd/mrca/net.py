@@ -236,7 +236,8 @@ class CNNPolicy(nn.Module):
         output, 8 MB and 7 us per tick at 4096 robots -- the tail adds the bias while it stages h1), and everything
         behind it -- bias, ReLU, cat, fc2, heads, sample, logprob, clip -- in csrc/mrca_policy_tail.hip.  ``noise`` f32[N,2] standard normal draws or None (mean action).
         -> value [N,1], action [N,2], logprob [N,1], scaled [N,2], mean [N,2].  fp32; differs from the stock path by
-        summation order only (tests/test_gpu_policy_ops.py).  ``bf16=True``: the opt-in bf16 inference -- the front end on
+        summation order only (tests/test_gpu_policy_ops.py: 1e-5 / 1e-4 against the stock layers; tests/test_gpu_rollout_inference.py:
+        against a float64 model of the chain, no further from it than 8 x the stock layers are).  ``bf16=True``: the opt-in bf16 inference -- the front end on
         bf16 MFMAs (csrc/mrca_policy_bf16.hip, bf16 features) and fc1 as a bf16 x bf16 batched GEMM with fp32 accumulation
         and result; the tail is the same fp32 kernel (tests/test_gpu_policy_bf16.py)."""
         from . import policy_ops
