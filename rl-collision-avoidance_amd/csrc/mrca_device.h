@@ -973,15 +973,19 @@ MRCA_HD float ray_box_local(float lx, float ly, float dx, float dy, float sj, fl
 // wave): asin(x) <= x + (pi/2 - 1) x^3 on [0, 1] (the gap asin(x) - x over x^3 grows monotonically from 1/6 to
 // pi/2 - 1), and a degree-7 odd polynomial for atan (|error| < 1.2e-4 rad).  Two beam widths + 1 mm of radius +
 // 3e-3 rad of slack absorb the approximation and every rounding in here.
-MRCA_HD float atan2_approx(float y, float x) {
+// (atan2 in its two parts: the quotient a = min(|x|, |y|) / max(|x|, |y|) in [0, 1] is the caller's, exact or approximate)
+MRCA_HD float atan2_from_quotient(float a, float y, float x) {
     const float ax = fabsf(x), ay = fabsf(y);
-    const float mx = ax > ay ? ax : ay, mn = ax > ay ? ay : ax;
-    const float a = mx > 0.0f ? mn / mx : 0.0f;
     const float z = a * a;
     float r = ((-0.0464964749f * z + 0.15931422f) * z - 0.327622764f) * z * a + a;
     r = ay > ax ? 1.57079637f - r : r;
     r = x < 0.0f ? 3.14159274f - r : r;
     return y < 0.0f ? -r : r;
+}
+MRCA_HD float atan2_approx(float y, float x) {
+    const float ax = fabsf(x), ay = fabsf(y);
+    const float mx = ax > ay ? ax : ay, mn = ax > ay ? ay : ax;
+    return atan2_from_quotient(mx > 0.0f ? mn / mx : 0.0f, y, x);
 }
 
 // step = kPi / (beams - 1) and inv_step = (beams - 1) / kPi as fp32 quotients: the same for every robot and beam, so the
@@ -989,6 +993,18 @@ MRCA_HD float atan2_approx(float y, float x) {
 // `radius`: what the other robot lies inside of, seen from its centre -- the circumscribed circle of the rectangle + 1 mm
 // (0.2917 m), or, in fidelity mode, that plus one raster-cell diagonal (its outline CELLS); `near`: centre distances up
 // to which every beam is kept (0.30 m / radius + 0.01 m).
+// (in its parts: the half angle a circle is seen under whose radius over its centre's distance is `ratio`, with the slack,
+// and the beams within `alpha` of bearing phi)
+MRCA_HD float beam_half_angle(float ratio /* <= 1 */, float step) {
+    return (ratio + 0.5708f * (ratio * ratio * ratio)) + 2.0f * step + 3e-3f;
+}
+MRCA_HD void beam_interval_around(float phi, float alpha, int beams, float inv_step, int* lo, int* hi) {
+    const float flo = (phi - alpha + 0.5f * kPi) * inv_step;
+    const float fhi = (phi + alpha + 0.5f * kPi) * inv_step;
+    int l = (int)floorf(flo), h = (int)ceilf(fhi);
+    *lo = l < 0 ? 0 : l;
+    *hi = h > beams - 1 ? beams - 1 : h;
+}
 MRCA_HD void beam_interval(float lx, float ly, int beams, float step, float inv_step, float radius, float near, int* lo,
                            int* hi) {
     const float dist = sqrtf(lx * lx + ly * ly);
@@ -999,17 +1015,49 @@ MRCA_HD void beam_interval(float lx, float ly, int beams, float step, float inv_
     }
     float ratio = radius / dist;
     ratio = ratio < 1.0f ? ratio : 1.0f;
-    const float alpha = (ratio + 0.5708f * (ratio * ratio * ratio)) + 2.0f * step + 3e-3f;
-    const float phi = atan2_approx(ly, lx);
-    const float flo = (phi - alpha + 0.5f * kPi) * inv_step;
-    const float fhi = (phi + alpha + 0.5f * kPi) * inv_step;
-    int l = (int)floorf(flo), h = (int)ceilf(fhi);
-    *lo = l < 0 ? 0 : l;
-    *hi = h > beams - 1 ? beams - 1 : h;
+    beam_interval_around(atan2_approx(ly, lx), beam_half_angle(ratio, step), beams, inv_step, lo, hi);
 }
 MRCA_HD void beam_interval(float lx, float ly, int beams, int* lo, int* hi) {
     beam_interval(lx, ly, beams, kPi / (float)(beams - 1), (float)(beams - 1) / kPi, 0.2917f, 0.30f, lo, hi);
 }
+// The same cull at the accuracy of the hardware's reciprocals -- what every device path runs (the form above stays the host's:
+// the oracle-side harness lists a robot's neighbours with it).  `ops` supplies rcp(x) ~ 1 / x and rsq(x) ~ 1 / sqrt(x):
+// CullHardwareOps on the device (v_rcp_f32 / v_rsq_f32, 1 ulp), perturbed ones in tests/test_prep_interval_host.py.
+//   * ratio = radius * rsq(d2): no correctly rounded sqrtf (~25 vector instructions) and no IEEE division (~12) -- and no
+//     clamp to 1: `near` is above `radius` (by 0.0083 m at the least), so behind the near test ratio < 0.98;
+//   * the near test on the squares, d2 <= near * near.  Either outcome is safe at the boundary: the far branch at dist = near
+//     has ratio 0.972 (fidelity mode at a 0.2 m raster: 0.983), alpha 1.51 rad against an asin of 1.32;
+//   * a = mn * rcp(mx), held to at most 1;
+//   * no branch: inside `near` the half angle is 8 rad, which holds every beam whatever the bearing (phi - 8 + pi/2 < 0 and
+//     phi + 8 + pi/2 > pi for |phi| <= pi) -- one select instead of a dozen scalar-side instructions of lane-mask bookkeeping.
+//     The one pose where the far form has no value, d2 = 0 (0 x inf), is inside `near`: the quotient's clamp makes 1 of it, a
+//     finite bearing, and the far half angle, infinite there, is not the one selected -- nothing undefined is converted.
+// A relative error of 2^-22 in ratio or in a moves alpha or phi by under 1e-6 rad each: the 3e-3 rad of slack above are three
+// orders of magnitude more, and lo / hi move by one beam only where flo / fhi stand within that of an integer.  A kept beam
+// more or less changes how many pairs are tested, never a result.
+template <class Ops>
+MRCA_HD void beam_interval_approx(float lx, float ly, int beams, float step, float inv_step, float radius, float near,
+                                  const Ops& ops, int* lo, int* hi) {
+    const float d2 = lx * lx + ly * ly;
+    const float ax = fabsf(lx), ay = fabsf(ly);
+    const float mx = ay > ax ? ay : ax, mn = ay > ax ? ax : ay;       // (on the test the octant's fold takes: one compare)
+    float a = mn * ops.rcp(mx);
+    a = a < 1.0f ? a : 1.0f;
+    const float far_alpha = beam_half_angle(radius * ops.rsq(d2), step);
+    const float alpha = d2 <= near * near ? 8.0f : far_alpha;
+    beam_interval_around(atan2_from_quotient(a, ly, lx), alpha, beams, inv_step, lo, hi);
+}
+#if defined(__HIPCC__)
+struct CullHardwareOps {        // (device code only; the host pass of a device compile merely parses it)
+#if defined(__HIP_DEVICE_COMPILE__)
+    __device__ __forceinline__ float rcp(float v) const { return __builtin_amdgcn_rcpf(v); }
+    __device__ __forceinline__ float rsq(float v) const { return __builtin_amdgcn_rsqf(v); }
+#else
+    __device__ float rcp(float v) const;
+    __device__ float rsq(float v) const;
+#endif
+};
+#endif
 
 // The slab tests of a small world's ray cast, PAIR-major (raycast_body, exact rectangles): the kept neighbours' intervals
 // [lo_k, hi_k], laid end to end in the order of the compacted list, number the (neighbour, beam) pairs 0 .. P - 1 -- neighbour k
@@ -1026,6 +1074,59 @@ MRCA_HD void beam_interval(float lx, float ly, int beams, int* lo, int* hi) {
 // For p >= P locate names the last neighbour and a beam behind its interval: such a pair is never formed (p < P is the loop's test).
 constexpr int kSlabPairPad = 0x7fffffff;
 MRCA_HD int lane_scan_step(int sum, int below, int lane, int d) { return lane >= d ? sum + below : sum; }
+// What the device runs for those six steps: the same inclusive sum as six v_add_u32_dpp, the wave's 64 lanes as four ROWS of 16.
+// A step adds to every lane of the rows in `rows` (bit r = row r) the sum of another lane as it was before the step -- `shift`
+// lanes down inside the row, nothing where that leaves the row (row_shr), or the last lane of the 16 (row_bcast:15) or 32
+// (row_bcast:31) lanes below the lane's own row resp. half -- and leaves the other rows as they are.  After the four shifts
+// every lane holds its row's inclusive sum; the first broadcast carries row 0's total into row 1 and row 2's into row 3, the
+// second the lower half's total (lane 31) into rows 2 and 3.  A shuffle (__shfl_up) goes through the LDS crossbar instead: a
+// ds_bpermute_b32 round trip and about ten instructions of lane arithmetic per step, on the path the workgroup's barrier
+// waits for.  lane_scan_network is the plain model of a network stated this way (tests/test_prep_scan_host.py holds
+// kLaneScanNet to std::partial_sum and sees its neighbours fail); lane_scan_dpp runs kLaneScanNet on the device.
+struct LaneScanStep {
+    int shift;          // row_shr: lanes down inside the row; a broadcast: the source's lane among the `span` lanes below
+    int span;           // 0: row_shr; 16 / 32: a broadcast out of the 16 / 32 lanes below the lane's own row / half
+    unsigned rows;      // the rows written (the instruction's row_mask)
+};
+constexpr int kLaneScanSteps = 6;
+constexpr LaneScanStep kLaneScanNet[kLaneScanSteps] = {{1, 0, 0xfu}, {2, 0, 0xfu},    {4, 0, 0xfu},
+                                                       {8, 0, 0xfu}, {15, 16, 0xau},  {31, 32, 0xcu}};
+// the lane a step adds into `lane`, or -1 for nothing
+MRCA_HD int lane_scan_source(const LaneScanStep& st, int lane) {
+    if (!((st.rows >> (lane >> 4)) & 1u)) return -1;
+    if (st.span) return (lane & ~(st.span - 1)) - st.span + st.shift;       // (-16 .. -1 in row 0 resp. the lower half)
+    return (lane & 15) >= st.shift ? lane - st.shift : -1;
+}
+MRCA_HD void lane_scan_network(const LaneScanStep* net, int steps, int* sum /* [64] */) {
+    for (int i = 0; i < steps; ++i) {
+        int next[64];
+        for (int l = 0; l < 64; ++l) {
+            const int from = lane_scan_source(net[i], l);
+            next[l] = from >= 0 ? sum[l] + sum[from] : sum[l];
+        }
+        for (int l = 0; l < 64; ++l) sum[l] = next[l];
+    }
+}
+#if defined(__HIPCC__)
+// (the DPP control word of a step: row_shr:n is 0x110 + n, row_bcast:15 is 0x142, row_bcast:31 is 0x143; a lane without a
+// source reads the `old` operand, zero)
+template <int I = 0>
+__device__ __forceinline__ int lane_scan_dpp(int sum) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    if constexpr (I == kLaneScanSteps) {
+        return sum;
+    } else {
+        constexpr LaneScanStep st = kLaneScanNet[I];
+        static_assert(st.span == 0 ? st.shift >= 1 && st.shift <= 15 : st.shift == st.span - 1 && (st.span == 16 || st.span == 32),
+                      "no DPP control for this step");
+        constexpr int ctrl = st.span == 0 ? 0x110 + st.shift : st.span == 16 ? 0x142 : 0x143;
+        return lane_scan_dpp<I + 1>(sum + __builtin_amdgcn_update_dpp(0, sum, ctrl, st.rows, 0xf, false));
+    }
+#else
+    return sum;     // (the host pass of a device compile: never called)
+#endif
+}
+#endif
 template <class Starts>
 MRCA_HD int slab_pair_locate(int p, int cnt, Starts start_of) {
     int q = -1;

@@ -221,8 +221,8 @@ __device__ __forceinline__ void raycast_body(int only_fresh, int ray_first, int 
                 if (hash_cell_coord(cxj, kLidarCell) == qx && hash_cell_coord(cyj, kLidarCell) == qy) {
                     const float ddx = cxj - x, ddy = cyj - y;
                     if (ddx * ddx + ddy * ddy <= kLidarReach2) {
-                        beam_interval(ddx * c + ddy * s, ddy * c - ddx * s, e.B, e.beam_step, e.beam_inv_step, e.lidar_radius,
-                                      e.lidar_near, &lo, &hi);
+                        beam_interval_approx(ddx * c + ddy * s, ddy * c - ddx * s, e.B, e.beam_step, e.beam_inv_step, e.lidar_radius,
+                                             e.lidar_near, CullHardwareOps{}, &lo, &hi);
                         keep = lo <= hi;
                         if (keep) chj = global_load<float4>(head_p, (uint32_t)j * 16u);
                     }
@@ -261,34 +261,39 @@ __device__ __forceinline__ void raycast_body(int only_fresh, int ray_first, int 
         const float ddx = xj - x, ddy = yj - y;
         // conservative cull: a hit below 6 m needs the centre within 6 + circumradius(0.2907) m (fidelity mode: + one
         // raster-cell diagonal -- what is tested there are the robot's outline CELLS)
-        bool keep = cand && (ddx * ddx + ddy * ddy <= e.lidar_reach2);
-        int lo = 0, hi = -1;
-        if (keep) {
-            beam_interval(ddx * c + ddy * s, ddy * c - ddx * s, e.B, e.beam_step, e.beam_inv_step, e.lidar_radius, e.lidar_near,
-                          &lo, &hi);
-            keep = lo <= hi;
+        // (kept: a candidate with a beam in its interval.  The length first and the test on it: one compare, and the ballot is it)
+        int lo = 0, hi = -1, len = 0;
+        if (cand && (ddx * ddx + ddy * ddy <= e.lidar_reach2)) {
+            // (the cull at the hardware's accuracy, v_rsq_f32 and v_rcp_f32: a beam more or less at an interval's end)
+            beam_interval_approx(ddx * c + ddy * s, ddy * c - ddx * s, e.B, e.beam_step, e.beam_inv_step, e.lidar_radius,
+                                 e.lidar_near, CullHardwareOps{}, &lo, &hi);
+            len = imax(hi - lo + 1, 0);
         }
+        const bool keep = len > 0;
         const unsigned long long m = __ballot(keep);
         if constexpr (PAIRS) {
             // pair-major slab tests (slab_pair_locate, mrca_device.h): the kept neighbours' intervals laid end to end number the
             // (neighbour, beam) pairs, and neighbour k's record is (lo_k, start_k), the exclusive prefix sum of the lengths before
             // it.  The sum runs over the LANES -- a dropped candidate adds nothing, and the ballot's compaction keeps the lanes'
-            // order -- in six doubling steps.  The dropped lanes fill the list's slots behind the kept ones with the pad that
-            // ends the search, so that it reads the starts eight at a time without a tail.
-            const int below = __popcll(m & ((1ull << pl) - 1ull));
-            const int kept = __popcll(m);
-            const int len = keep ? hi - lo + 1 : 0;
-            int end = len;
-#pragma unroll
-            for (int d = 1; d < kWave; d <<= 1) end = lane_scan_step(end, __shfl_up(end, d, kWave), pl, d);
+            // order -- as six v_add_u32_dpp (lane_scan_dpp: the sum lane_scan_step's six doubling steps give, without their six
+            // round trips through the LDS crossbar).  The list's slots behind the kept ones hold the pad that ends the search, so
+            // that it reads the starts eight at a time without a tail: EVERY lane stamps the pad on its own slot's start first, and
+            // the kept lanes' records go over the first `kept` of them -- a wave's LDS instructions take effect in the order it
+            // issues them -- instead of each dropped lane working out a slot behind the list.
+            // (pl is the lane's number in its wave -- T is a multiple of 64 --: the kept lanes below it are v_mbcnt's count)
+            const int below = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+            const int end = lane_scan_dpp(len);
+            nbi[pl].y = kSlabPairPad;
+            if (pl == kWave - 1) {      // the last lane holds P, the number of pairs: it stores the list's length beside it
+                nb_count[0] = MRCA_DBG(e, 1) ? 0 : __popcll(m);
+                nb_count[2] = end;
+            }
             if (keep) {
                 float olx, oly;         // the lidar's origin in the neighbour's frame: once per neighbour, not per pair
                 ray_box_origin(x, y, xj, yj, hj.x, hj.y, &olx, &oly);
                 nb[below] = make_float4(olx, oly, hj.x, hj.y);
+                nbi[below] = make_int2(lo, end - len);
             }
-            nbi[keep ? below : kept + (pl - below)] = make_int2(lo, keep ? end - len : kSlabPairPad);
-            if (pl == 0) nb_count[0] = MRCA_DBG(e, 1) ? 0 : kept;
-            if (pl == kWave - 1) nb_count[2] = end;       // P, the number of pairs
         } else {        // the raster lidar: beam-major, a mask of neighbours per beam
             if (keep) {
                 const int idx = __popcll(m & ((1ull << pl) - 1ull));

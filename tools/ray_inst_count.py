@@ -11,7 +11,11 @@ mrca_ray_shape.h itself, compiled for the host; --all: every instantiation):
   * the same for each MARCH loop (an innermost loop that loads a 16-bit field entry) and for the SLAB loop (the innermost loop
     that reads a neighbour's 16-byte record from LDS, stores nothing and loads nothing from global memory) of the beam-major
     kernels; for the pair-major ones (small worlds, exact rectangles) the PAIR loop -- the one that merges with ds_min_i32 --
-    without and beside the SEARCH loop inside it (slab_pair_locate: the list's starts, read two at a time).
+    without and beside the SEARCH loop inside it (slab_pair_locate: the list's starts, read two at a time);
+  * for the small worlds' kernels the PREPARING stretch: what only the preparing wave issues before the march -- the cull, the
+    prefix sum over the lanes and the list's stores -- and the ds_bpermute_b32 (shuffles through the LDS crossbar) in it.  It is
+    the first region under a saved lane mask (s_and_saveexec_b64 .. s_or_b64 exec, exec) ahead of the first march loop that is
+    inside no other such region and writes LDS: the prologue's region under the same mask only requests global loads.
 
 Instructions are classed by mnemonic prefix only: v_* is vector; s_* is the scalar side (s_nop, s_waitcnt and branches
 included: each takes an issue slot of the wave); flat_*, global_*, ds_*, buffer_*, scratch_* are memory instructions, listed by
@@ -93,7 +97,7 @@ class Count:
     def __init__(self):
         self.v = self.s = 0
         self.mem = dict.fromkeys(MEM, 0)
-        self.ushort = self.b128 = self.stores = self.ds_min = self.read2 = 0
+        self.ushort = self.b128 = self.stores = self.ds_min = self.read2 = self.bpermute = self.ds_write = 0
 
     def add(self, op):
         if op.startswith("v_"):
@@ -108,6 +112,8 @@ class Count:
             self.b128 += op == "ds_read_b128"
             self.ds_min += op == "ds_min_i32"
             self.read2 += op == "ds_read2_b32"
+            self.bpermute += op == "ds_bpermute_b32"
+            self.ds_write += op.startswith("ds_write")
             self.stores += "_store_" in op or op.startswith("ds_write") or op.startswith("ds_or")
 
     def __str__(self):
@@ -115,18 +121,42 @@ class Count:
             self.v, self.s, self.mem["flat"], self.mem["global"], self.mem["ds"])
 
 
+def prep_stretch(insts, loops):
+    """Count of the preparing stretch (see the module's head) of a kernel's [(mnemonic, operands, innermost loop)], or None"""
+    march = {h for h, c in loops.items() if c.ushort}
+    end = next((k for k, (_, _, loop) in enumerate(insts) if loop in march), len(insts))
+    k = 0
+    while k < end:
+        op, args, _ = insts[k]
+        k += 1
+        if op != "s_and_saveexec_b64":
+            continue
+        saved = args.split(",")[0].strip()
+        close = next((j for j in range(k, end) if insts[j][0] == "s_or_b64" and
+                      [a.strip() for a in insts[j][1].split(",")] == ["exec", "exec", saved]), None)
+        if close is None:
+            return None
+        c = Count()
+        for op2, _, _ in insts[k:close]:
+            c.add(op2)
+        if c.ds_write:
+            return c
+        k = close + 1
+    return None
+
+
 def kernels(lines):
-    """{mangled name: (Count of the kernel, {innermost loop header: Count})}"""
-    out, name, total, loops, loop, label = {}, None, None, None, None, None
+    """{mangled name: (Count of the kernel, {innermost loop header: Count}, Count of the preparing stretch or None)}"""
+    out, name, total, loops, loop, label, insts = {}, None, None, None, None, None, None
     for line in lines:
         m = re.match(r"(_Z\w+):", line)
         if m:
-            name, total, loops, loop, label = m.group(1), Count(), {}, None, None
+            name, total, loops, loop, label, insts = m.group(1), Count(), {}, None, None, []
             continue
         if name is None:
             continue
         if re.match(r"\.Lfunc_end\d+:", line):
-            out[name] = (total, loops)
+            out[name] = (total, loops, prep_stretch(insts, loops))
             name = None
             continue
         # a block begins: `.LBBn_m:` or `; %bb.k:`, with the compiler's loop comment behind it (or none: not in a loop)
@@ -141,10 +171,11 @@ def kernels(lines):
         if label is not None and re.match(r"\s*;\s*=>\s*This Inner Loop Header", line):
             loop = label
             continue
-        i = re.match(r"\t([a-z]\w+)", line)
+        i = re.match(r"\t([a-z]\w+)\s*([^;]*)", line)
         if not i or line.startswith("\t."):
             continue
         total.add(i.group(1))
+        insts.append((i.group(1), i.group(2).strip(), loop))
         if loop is not None:
             loops.setdefault(loop, Count()).add(i.group(1))
     return out
@@ -169,9 +200,11 @@ def main():
                     compiled.add(v[1])
                 if not v or not (a.all or v[1] in product):
                     continue
-                total, loops = found[name]
+                total, loops, prep = found[name]
                 print(v[0])
-                print("    kernel      %s" % total)
+                print("    kernel      %s  ds_bpermute %d" % (total, total.bpermute))
+                if prep is not None and not v[1][1]:
+                    print("    preparing   %s  ds_bpermute %d" % (prep, prep.bpermute))
                 march = [c for c in loops.values() if c.ushort]
                 slab = [c for c in loops.values() if c.b128 and not c.stores and not c.ushort and not c.mem["global"]]
                 for k, c in enumerate(march):
