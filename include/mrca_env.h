@@ -33,7 +33,8 @@
 extern "C" {
 #endif
 
-/* 6, additive: mrca_dwa_actions, mrca_dwa_default_params (a sensor-level DWA baseline beside ORCA).
+/* 6, additive: mrca_scan_noise, mrca_scan_noise_default_params (a lidar noise model applied to the ring in place).
+ * 6, additive: mrca_dwa_actions,mrca_dwa_default_params (a sensor-level DWA baseline beside ORCA).
  * 6, additive: mrca_orca_actions_any (the ORCA baseline on worlds of any size); mrca_move_worlds / mrca_observe_worlds take the
  * full range of an env with robots_per_world > 64.
  * 6, additive: mrca_lidar_features_bf16 (the bf16 MFMA front end of the opt-in bf16 rollout inference); the opt-in fused bf16
@@ -378,6 +379,46 @@ int mrca_dwa_default_params(mrca_dwa_params* out);
 int mrca_dwa_actions(mrca_env* env, const mrca_dwa_params* params /* host, NULL = defaults */, const uint8_t* mask_dev,
                      float* actions_dev /* f32[N,2] */, int32_t* choice_dev /* i32[N] or NULL */,
                      float* score_dev /* f32[N] or NULL */, void* stream);
+
+/* A lidar noise model on the device: turns the exact ranges the ray cast has just stored into what a real ranger would have
+ * reported -- IN PLACE, in MRCA_F_SCAN_RING, so that everything sensor-level (the policy's fused front end, mrca_dwa_actions,
+ * ORCA's static points, the renderer's beam layer, mrca_rollout_store_state, mrca_materialize / mrca_newest_obs) reads the
+ * noisy row.  For beam b of robot n with clean range r (csrc/mrca_noise_device.h, separately rounded fp32 steps in a fixed
+ * order: reproducible bit for bit, tests/noise_ref.py restates it in NumPy):
+ *   U = philox4x32_10(n, MRCA_F_EPISODE[n], b, (MRCA_F_T[n] << 2) | 2, seed) -- the reset sampler's robot word and key; its
+ *       streams use counter word 3 = 0 and 1, which a word with low bits 2 cannot meet.  The draw hangs on (seed, robot,
+ *       episode, T, beam) and on nothing else: not on the launch shape, the mask or the order of calls.
+ *   r >= 6: the beam returned nothing -- it stays as it is, its hit bit stays clear.  Otherwise
+ *   z  = (((u01(U.x) + u01(U.y)) + u01(U.z)) - 1.5) * 2   (a three-uniform Irwin-Hall deviate: mean 0, variance 1, support
+ *        +-3 -- NOT a Gaussian);
+ *   r1 = r + (sigma_const + sigma_prop * r) * z if one of the sigmas is > 0, else r;
+ *   r2 = quantum * rintf(r1 / quantum) if quantum > 0, else r1;   !(r2 > 0) gives +0.0;   r2 >= 6 gives 6.0 and clears the
+ *   beam's bit in MRCA_F_HIT_BITS (a set bit never stands on a 6.0);   u01(U.w) < dropout gives 6.0, bit cleared, whatever
+ *   the above produced.
+ * Which slots: the newest one (MRCA_F_RING_HEAD[n]); for a robot whose MRCA_F_FRESH flag is set, all `frames` slots and their
+ * hit words (the cast has just filled them with one row, as the reference fills its deque).  With lazy_obs = 0 the same launch
+ * rewrites MRCA_F_SCAN[n] and the newest frame of MRCA_F_OBS[n] (all frames for a fresh robot) with x / 6 - 0.5 of the row.
+ *   ONE CALL PER CAST: the transform is in place and not idempotent -- call it once behind mrca_reset (with that reset's
+ * mask) and once behind every mrca_step / mrca_step_slice / mrca_step_worlds / mrca_observe_worlds, with a mask of the
+ * robots that call cast.  A second call behind the same cast adds the same draw again.  mrca_step_many casts several ticks
+ * per call and cannot be combined with it.
+ *   params    host; NULL = mrca_scan_noise_default_params: sigma_const 0.01 m, sigma_prop 0.01, dropout 0.005, quantum 0 -- a
+ *             small indoor lidar's order of magnitude, NOT the reference's: Stage is configured without ranger noise
+ *   mask_dev  u8[N] or NULL = all robots; rows whose byte is 0 are not touched
+ * All four params zero: MRCA_OK without a launch.  Asynchronous on `stream`, ONE launch (one wavefront per robot), capturable;
+ * writes the ring, the hit bits and (lazy_obs = 0) the two views of the masked robots and nothing else of the env.  Any
+ * robots_per_world, beams, frames, both lazy_obs values, exact and raster modes.  Validated before the first HIP call
+ * (MRCA_ERR_INVALID): every float finite; 0 <= sigma_const <= 6; 0 <= sigma_prop <= 1; 0 <= dropout <= 1; 0 <= quantum <= 1;
+ * a call before the env's first mrca_reset is refused. */
+typedef struct mrca_scan_noise_params {
+    float sigma_const;  /* [m], constant part of the range noise */
+    float sigma_prop;   /* per metre of range */
+    float dropout;      /* probability a returning beam reports nothing */
+    float quantum;      /* [m], 0 = none */
+} mrca_scan_noise_params;
+int mrca_scan_noise_default_params(mrca_scan_noise_params* out);
+int mrca_scan_noise(mrca_env* env, const mrca_scan_noise_params* params /* host, NULL = defaults */,
+                    const uint8_t* mask_dev /* u8[N] or NULL = all */, void* stream);
 
 /* Synchronises `stream` and reports (then clears) the env's sticky device-side status word: MRCA_OK, or MRCA_ERR_HIP with
  * mrca_last_error() saying what went wrong on the device since the last check.  Today one condition: the ordered

@@ -23,6 +23,7 @@
 #include "mrca_kernels.h"
 #include "mrca_orca.h"
 #include "mrca_dwa.h"
+#include "mrca_noise.h"
 #include "mrca_pass_plan.h"
 #include "mrca_render.h"
 #include "mrca_rollout_store.h"
@@ -315,6 +316,7 @@ struct mrca_env {
     // (mrca_reset, the observe phase).  Who reads the hash outside the tick asks here (mrca_orca_actions_any).
     bool lidar_hash_current = false;
     bool lidar_counts_pending = false;    // a move phase has left the next hash's bucket populations in bw_lcount
+    bool reset_seen = false;              // mrca_reset has been enqueued once: the ring holds scans (mrca_scan_noise asks)
     StreamCheck check;                    // (these four: mrca_step_many)
     AheadRing ahead;
     std::vector<WorldRange> ranges;       // world ranges 1 .. P - 1
@@ -786,6 +788,7 @@ int mrca_reset(mrca_env* env, const uint8_t* mask_dev, const float* poses_dev, c
     }
     mrca::launch_lidar_grid(env->view, /*counted=*/0, s);
     env->lidar_hash_current = true;
+    env->reset_seen = true;
     mrca::launch_raycast(env->view, /*only_fresh=*/1, s);
     if (!env->cfg.lazy_obs) mrca::launch_materialize(env->view, MRCA_VIEW_SCAN | MRCA_VIEW_OBS, s);
     HIP_TRY(hipGetLastError());
@@ -980,6 +983,46 @@ int mrca_dwa_actions(mrca_env* env, const mrca_dwa_params* params, const uint8_t
     memcpy(&q, &p, sizeof q);
     DeviceGuard guard(env->cfg.device);
     mrca::launch_dwa(env->view, q, mask_dev, actions_dev, choice_dev, score_dev, static_cast<hipStream_t>(stream));
+    HIP_TRY(hipGetLastError());
+    return MRCA_OK;
+}
+
+static_assert(sizeof(mrca_scan_noise_params) == sizeof(mrca::ScanNoiseParams) &&
+                  offsetof(mrca_scan_noise_params, quantum) == offsetof(mrca::ScanNoiseParams, quantum),
+              "mrca_scan_noise_params and mrca::ScanNoiseParams are one layout");
+
+int mrca_scan_noise_default_params(mrca_scan_noise_params* out) {
+    if (!out) return fail(MRCA_ERR_INVALID, "mrca_scan_noise_default_params: out is NULL");
+    // a small indoor lidar's order of magnitude (a centimetre, a percent of the range, one beam in two hundred lost), NOT the
+    // reference's: Stage is configured without ranger noise
+    out->sigma_const = 0.01f;
+    out->sigma_prop = 0.01f;
+    out->dropout = 0.005f;
+    out->quantum = 0.0f;
+    return MRCA_OK;
+}
+
+int mrca_scan_noise(mrca_env* env, const mrca_scan_noise_params* params, const uint8_t* mask_dev, void* stream) {
+    // everything that can be judged without the env, then the env
+    mrca_scan_noise_params p;
+    if (params) p = *params;
+    else mrca_scan_noise_default_params(&p);
+    const float fl[4] = {p.sigma_const, p.sigma_prop, p.dropout, p.quantum};
+    static const char* const names[4] = {"sigma_const", "sigma_prop", "dropout", "quantum"};
+    static const float upper[4] = {6.0f, 1.0f, 1.0f, 1.0f};
+    for (int i = 0; i < 4; ++i)
+        if (!std::isfinite(fl[i])) return fail(MRCA_ERR_INVALID, "mrca_scan_noise: %s is not finite", names[i]);
+    for (int i = 0; i < 4; ++i)
+        if (!(fl[i] >= 0.0f && fl[i] <= upper[i]))
+            return fail(MRCA_ERR_INVALID, "mrca_scan_noise: %s outside [0, %g]", names[i], (double)upper[i]);
+    if (!env) return fail(MRCA_ERR_INVALID, "env is NULL");
+    if (!env->reset_seen) return fail(MRCA_ERR_INVALID, "mrca_scan_noise before the first mrca_reset: there is no scan yet");
+    if (p.sigma_const == 0.0f && p.sigma_prop == 0.0f && p.dropout == 0.0f && p.quantum == 0.0f) return MRCA_OK;   // nothing to do
+    mrca::ScanNoiseParams q;
+    static_assert(std::is_trivially_copyable<mrca::ScanNoiseParams>::value, "");
+    memcpy(&q, &p, sizeof q);
+    DeviceGuard guard(env->cfg.device);
+    mrca::launch_scan_noise(env->view, q, mask_dev, env->cfg.lazy_obs ? 0 : (MRCA_VIEW_SCAN | MRCA_VIEW_OBS), static_cast<hipStream_t>(stream));
     HIP_TRY(hipGetLastError());
     return MRCA_OK;
 }

@@ -240,6 +240,11 @@ def main():
     ap.add_argument("--dwa-first", type=int, default=None, metavar="K",
                     help="robots with local index < K are driven by DWA, the rest by --policy, --orca or the stand-in; the "
                          "metrics are reported for both groups")
+    ap.add_argument("--lidar-noise", default=None, metavar="const=M,prop=P,dropout=Q[,quantum=M]",
+                    help="the lidar noise model (mrca_scan_noise) behind every ray cast: range noise of const + prop * range metres "
+                         "(an Irwin-Hall deviate of unit variance), beams lost with probability dropout, a read-out step of quantum "
+                         "metres; what is not named is 0, 'default' takes the library's defaults.  Every controller reads the noisy "
+                         "scans; the result line carries the params as lidar_noise")
     ap.add_argument("--render", default=None, metavar="PATH", help="write pictures of the run (top-down views with trails, rendered on "
                                                                     "the device and copied to the host once after the last tick): "
                                                                     "an animated GIF, or PATH.npz where PIL is missing")
@@ -265,7 +270,14 @@ def main():
     else:
         grid = scenario.load_map("circle_rink_r0010") if a.stage_resolution else None
         sc = scenario.circle_n(a.robots, a.radius, num_worlds=a.circles, seed=a.seed, grid=grid)
-    env = VecStageWorld(sc)
+    noise = None
+    if a.lidar_noise is not None:
+        from .noise import ScanNoiseParams
+        try:
+            noise = ScanNoiseParams.from_assignments(a.lidar_noise)
+        except ValueError as e:
+            ap.error(str(e))
+    env = VecStageWorld(sc, **({} if noise is None else {"scan_noise": noise}))
     if a.policy:
         pol = CNNPolicy(3, 2).to(env.device)
         pol.load_state_dict(torch.load(a.policy, map_location=env.device))
@@ -307,6 +319,7 @@ def main():
     if a.dwa or a.dwa_first is not None:
         import dataclasses
         out["dwa_params"] = dataclasses.asdict(dwa_params)
+    out["lidar_noise"] = None if noise is None else noise.as_dict()
     out["robots_per_circle"], out["radius_m"] = a.robots, a.radius
     if a.one_circle is not None:
         out["one_circle"], out["robots_per_circle"] = a.one_circle, a.one_circle

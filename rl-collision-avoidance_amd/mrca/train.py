@@ -110,7 +110,19 @@ def main(argv=None):
                                                                   "keeps driving at its last command until its group is done "
                                                                   "(what ppo_stage2.py's dead robots do under stageros), and the "
                                                                   "speed input survives a reset")
+    ap.add_argument("--lidar-noise", default=None, metavar="const=M,prop=P,dropout=Q[,quantum=M]",
+                    help="train under the lidar noise model (mrca_scan_noise): every training env applies it behind each ray cast "
+                         "(range noise of const + prop * range metres, beams lost with probability dropout, a read-out step of "
+                         "quantum metres; what is not named is 0, 'default' takes the library's defaults).  The periodic circle "
+                         "evaluation (--circle-every) stays on exact scans")
     a = ap.parse_args(argv)
+    noise = None
+    if a.lidar_noise is not None:
+        from .noise import ScanNoiseParams
+        try:
+            noise = ScanNoiseParams.from_assignments(a.lidar_noise)
+        except ValueError as e:
+            ap.error(str(e))
     if a.fused_bf16_inference and (a.bf16_inference or a.stock_policy_path):
         ap.error("--fused-bf16-inference runs the fused policy path: it cannot be combined with --bf16-inference or "
                  "--stock-policy-path")
@@ -168,16 +180,19 @@ def main(argv=None):
         hp.update_dtype = torch.bfloat16
     if a.bf16_inference:
         hp.inference_dtype = torch.bfloat16
-    env = VecStageWorld(sc)
+    noise_kw = {} if noise is None else {"scan_noise": noise}        # (without the flag the env is constructed as ever)
+    env = VecStageWorld(sc, **noise_kw)
+    if noise is not None:
+        out.info("lidar noise: %s", noise.as_dict())
     if a.mix_circle > 0 or a.mix_circles:
         from .multi_env import ConcatEnv
         parts = [env]
         if a.mix_circle > 0:
-            parts.append(VecStageWorld(scenario.circle_train(num_worlds=a.mix_circle, seed=a.seed * 1000 + rank)))
+            parts.append(VecStageWorld(scenario.circle_train(num_worlds=a.mix_circle, seed=a.seed * 1000 + rank), **noise_kw))
         for spec in filter(None, a.mix_circles.split(",")):
             r, rad, w = spec.split(":")
             parts.append(VecStageWorld(scenario.circle_n(int(r), float(rad), num_worlds=int(w), seed=a.seed * 1000 + rank,
-                                                         train=True)))
+                                                         train=True), **noise_kw))
         env = ConcatEnv(parts)
         out.info("training mix: %d robots of %s + %d robots in circle worlds (%s)", sc.num_robots, sc.name,
                  env.N - sc.num_robots, ", ".join("%d x %d robots" % (p.W, p.R) for p in parts[1:]))

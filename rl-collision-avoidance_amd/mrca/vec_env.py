@@ -37,10 +37,13 @@ def sparse_beam_index(raw_beams, beam_num):
 
 
 class VecStageWorld:
-    def __init__(self, scenario: Scenario, device=None, lib_path=None, lazy_obs=True):
+    def __init__(self, scenario: Scenario, device=None, lib_path=None, lazy_obs=True, scan_noise=None):
         """``lazy_obs=False``: the library forms the two reference-shaped views (MRCA_F_SCAN, MRCA_F_OBS) inside every
         ``step`` / ``reset`` -- what a plain C caller written against the reference's getters expects (mrca_config.lazy_obs
-        = 0: one more kernel per call); the default leaves them to the ``scan`` / ``obs`` properties."""
+        = 0: one more kernel per call); the default leaves them to the ``scan`` / ``obs`` properties.
+        ``scan_noise``: a ``noise.ScanNoiseParams`` -- the lidar noise model (mrca_scan_noise) is then applied once behind every
+        ray cast of ``reset`` / ``step`` / ``observe``, to exactly the robots that call cast; ``step_many`` refuses.  ``None``
+        (the default): exact ranges, nothing is launched."""
         if not torch.cuda.is_available():
             raise RuntimeError("VecStageWorld needs an MI355X (torch.cuda is unavailable); there is no CPU path")
         self.lib = _lib.load(lib_path)      # lib_path: another build of the same library (the profiling build)
@@ -100,6 +103,8 @@ class VecStageWorld:
             setattr(self, "_" + name if name in ("obs", "scan") else name, t)
         self._eager_views = 0 if lazy_obs else (_lib.VIEW_SCAN | _lib.VIEW_OBS)   # views the library itself keeps current
         self._views_current = 0          # bits of _lib.VIEW_*: which of MRCA_F_SCAN / MRCA_F_OBS follow the ring right now
+        self._scan_noise = None if scan_noise is None else scan_noise.struct()
+        self._noise_masks = {}           # (first, count) -> uint8[N] with ones in that range of robots: kept, so a capture can replay them
 
     # ------------------------------------------------------------------ the scans and the observation stack
     # The env keeps the last F scans of every robot as a RING of raw ranges (``scan_ring`` + ``ring_head``: a tick writes
@@ -291,6 +296,29 @@ class VecStageWorld:
                                              self._ptr(score, torch.float32, self.N), self._stream()), "mrca_dwa_actions")
         return out
 
+    def scan_noise(self, params=None, mask=None):
+        """The lidar noise model (mrca_scan_noise) applied IN PLACE to the newest scan row of every robot (``mask``: a uint8[N]
+        tensor, rows with 0 are not touched): range noise, quantisation and dropout as ``params`` (a ``noise.ScanNoiseParams``;
+        default: the library's) say, drawn per (seed, robot, episode, T, beam).  One launch on the current stream.  NOT
+        idempotent: call it ONCE behind each ``reset`` / ``step`` -- or construct the env with ``scan_noise=`` and let it."""
+        st = None if params is None else params.struct()
+        self._apply_noise(st, self._ptr(mask, torch.uint8, self.N))
+        return self
+
+    def _apply_noise(self, st, mask_ptr):
+        _lib.check(self.lib.mrca_scan_noise(self._h, None if st is None else C.byref(st), mask_ptr, self._stream()), "mrca_scan_noise")
+        self._views_current &= self._eager_views          # (the library keeps its eager views in step; the lazy ones are stale)
+
+    def _noise_range(self, first, count):
+        """the env's own noise behind a cast of robots [first, first + count)"""
+        if (first, count) == (0, self.N):
+            return self._apply_noise(self._scan_noise, None)
+        m = self._noise_masks.get((first, count))
+        if m is None:
+            m = self._noise_masks[(first, count)] = torch.zeros(self.N, dtype=torch.uint8, device=self.device)
+            m[first:first + count] = 1
+        self._apply_noise(self._scan_noise, C.c_void_p(m.data_ptr()))
+
     # ------------------------------------------------------------------ lifecycle
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -323,6 +351,8 @@ class VecStageWorld:
                                        self._ptr(poses, torch.float32, self.N * 3),
                                        self._ptr(goals, torch.float32, self.N * 2), self._stream()), "mrca_reset")
         self._views_current = self._eager_views
+        if self._scan_noise is not None:
+            self._apply_noise(self._scan_noise, self._ptr(mask, torch.uint8, self.N))
         return self
 
     def step(self, actions, ray_slice=None, worlds=None):
@@ -339,13 +369,18 @@ class VecStageWorld:
             _lib.check(self.lib.mrca_step_worlds(self._h, a, int(worlds[0]), int(worlds[1]), self._stream()),
                        "mrca_step_worlds")
             self._views_current = 0       # (lazy_obs=False re-formed the views of this range only)
+            cast = (int(worlds[0]) * self.R, int(worlds[1]) * self.R)
         elif ray_slice is None:
             _lib.check(self.lib.mrca_step(self._h, a, self._stream()), "mrca_step")
             self._views_current = self._eager_views
+            cast = (0, self.N)
         else:
             _lib.check(self.lib.mrca_step_slice(self._h, a, int(ray_slice[0]), int(ray_slice[1]), self._stream()),
                        "mrca_step_slice")
             self._views_current = 0
+            cast = (int(ray_slice[0]), int(ray_slice[1]))
+        if self._scan_noise is not None:
+            self._noise_range(*cast)
         return self
 
     def move(self, actions, worlds):
@@ -362,6 +397,8 @@ class VecStageWorld:
         _lib.check(self.lib.mrca_observe_worlds(self._h, int(worlds[0]), int(worlds[1]), self._stream()),
                    "mrca_observe_worlds")
         self._views_current = 0
+        if self._scan_noise is not None:
+            self._noise_range(int(worlds[0]) * self.R, int(worlds[1]) * self.R)
         return self
 
     def step_many(self, actions, first_tick, num_ticks, chains=1):
@@ -370,6 +407,9 @@ class VecStageWorld:
         ``chains`` = P > 0: the library's run-ahead schedule -- the move launches on a stream of the env's own, ahead of the ray
         casts of P world ranges on P streams (mrca_step_many); ``chains`` = -P: round 5's P chains half a tick
         apart.  The first call on a stream spends ~1 ms warming and checking the env's streams (and synchronises once)."""
+        if self._scan_noise is not None:
+            raise ValueError("step_many: this env was constructed with scan_noise, and mrca_step_many casts the rays of several "
+                             "ticks per call -- the noise model is applied once per cast (mrca_scan_noise); use step")
         # (the pointer table of a list is built once per list object: a 20-tick region is 0.6 ms, sixteen data_ptr() calls and
         # their checks are 2 % of it.  The entry keeps the tensors themselves: an element replaced in place -- pool[i] = t --
         # fails the identity compare below and rebuilds the table, and a table never outlives the memory it points at)
