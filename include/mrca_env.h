@@ -33,7 +33,8 @@
 extern "C" {
 #endif
 
-/* 6, additive: mrca_scan_noise, mrca_scan_noise_default_params (a lidar noise model applied to the ring in place).
+/* 6, additive: mrca_hybrid_actions, mrca_hybrid_default_params (hybrid control behind a policy: PID, policy or safe policy per robot).
+ * 6, additive: mrca_scan_noise, mrca_scan_noise_default_params (a lidar noise model applied to the ring in place).
  * 6, additive: mrca_dwa_actions,mrca_dwa_default_params (a sensor-level DWA baseline beside ORCA).
  * 6, additive: mrca_orca_actions_any (the ORCA baseline on worlds of any size); mrca_move_worlds / mrca_observe_worlds take the
  * full range of an env with robots_per_world > 64.
@@ -419,6 +420,58 @@ typedef struct mrca_scan_noise_params {
 int mrca_scan_noise_default_params(mrca_scan_noise_params* out);
 int mrca_scan_noise(mrca_env* env, const mrca_scan_noise_params* params /* host, NULL = defaults */,
                     const uint8_t* mask_dev /* u8[N] or NULL = all */, void* stream);
+
+/* Hybrid control behind a policy, after Fan, Long, Liu, Pan (IJRR 2020, Sec. 5): per robot and tick, which of three drives it --
+ * a PID law where nothing stands between it and its goal, the policy's command with v scaled down where something is
+ * dangerously close, the policy's command as it is everywhere else.  SENSOR-LEVEL: it reads the newest row of MRCA_F_SCAN_RING
+ * (through MRCA_F_RING_HEAD), MRCA_F_LOCAL_GOAL and the incoming command, NOT MRCA_F_HIT_BITS, poses or anything of another
+ * robot; behind mrca_scan_noise it sees the noisy row.  In the robot's frame, with goal g, command (vp, wp), ranges r_b
+ * (r = r_b + 0: a -0.0 counts as 0) and beam directions (c_b, s_b):
+ *   gl = |g| <= 0.5 (kGoalRadius): the command is (0, 0), mode -2.  Otherwise u = g / gl, reach = min(gl, look);
+ *   a beam with r < 6 is a return at p = r (c_b, s_b); it BLOCKS iff t = p . u lies in [0, reach] and |px uy - py ux| < corridor;
+ *   d_min = least r of all beams, d_front = least r of the beams with c_b >= front_cos (6: none), d_block = least r of the
+ *   blocking beams (6: none);
+ *   mode 2 (emergent) iff d_min < risk_dist: (vp s, wp), s = clamp((d_front - stop_dist) / (risk_dist - stop_dist), 0, safe_scale)
+ *          -- the robot may still turn away at full rate;
+ *   mode 1 (simple) iff not emergent and no beam blocks: ORCA's conversion of the velocity v_pid u to (v, omega) at heading 0
+ *          (v = min(v_pid ux, max_speed) if ux > 0 else 0; omega = clamp(k_omega uy) if ux > 0 else +-clamp(k_omega));
+ *   mode 0 (normal) otherwise: (vp, wp) copied bit for bit, a NaN or a -0.0 included.
+ * NOT THE PAPER'S LITERAL FORM: its safe policy runs the network again on a rescaled scan; this call sits behind the policy
+ * and scales its command only (mode_dev lets a caller run that second forward for the robots of mode 2 itself), and the
+ * corridor test stands in for the paper's "goal nearer than every obstacle".  The rule is csrc/mrca_hybrid_device.h,
+ * separately rounded fp32 steps in a fixed order, minima and a count over the beams: reproducible bit for bit
+ * (tests/hybrid_ref.py restates it in NumPy).
+ *   params      host; NULL = mrca_hybrid_default_params: risk_dist 0.6, stop_dist 0.3, safe_scale 0.75, corridor 1, look 6,
+ *               front_cos 0.5, v_pid 1, k_omega 6, max_speed 1 (profiles/hybrid/defaults.txt)
+ *   mask_dev    u8[N] or NULL = all robots
+ *   policy_dev  f32[N,2] in: the command to wrap
+ *   actions_dev f32[N,2] out, 8-byte aligned, may be policy_dev itself; rows whose mask byte is 0 are not touched (nor are
+ *               their mode / clear rows)
+ *   mode_dev    i32[N] or NULL; out: 0, 1, 2 or -2
+ *   clear_dev   f32[N,3] or NULL; out: d_min, d_front, d_block
+ * Asynchronous on `stream`, ONE launch (one wavefront per robot, the params travel as kernel arguments), capturable; reads
+ * the env as it stands at that point of the stream and writes none of it, so mrca_step with actions_dev can follow on the same
+ * stream.  Any robots_per_world, beams 64 .. 1024, frames 1 .. 8, both lazy_obs values, exact and raster collision modes.
+ * Validated before the first HIP call (MRCA_ERR_INVALID): every float finite; 0 <= stop_dist < risk_dist <= 6;
+ * 0 <= safe_scale <= 1; corridor > 0; 0 < look <= 6; -1 <= front_cos <= 1; v_pid > 0; 0 < max_speed <= 1; k_omega >= 0;
+ * actions_dev not NULL and 8-byte aligned; policy_dev not NULL; a call before the env's first mrca_reset is refused. */
+typedef struct mrca_hybrid_params {
+    float risk_dist;    /* [m] a return nearer than this makes the robot careful (mode 2) */
+    float stop_dist;    /* [m] the nearest return ahead at or below this: v = 0 */
+    float safe_scale;   /* the most of the incoming v that mode 2 lets through */
+    float corridor;     /* [m] half width of the strip towards the goal that must be free for the PID law */
+    float look;         /* [m] its length, at most (and at most the distance to the goal) */
+    float front_cos;    /* beams with cos >= this are "ahead" for d_front */
+    float v_pid;        /* [m/s] speed of the PID law */
+    float k_omega;      /* its turn gain (ORCA's) */
+    float max_speed;    /* at most 1 */
+} mrca_hybrid_params;
+int mrca_hybrid_default_params(mrca_hybrid_params* out);
+int mrca_hybrid_actions(mrca_env* env, const mrca_hybrid_params* params /* host, NULL = defaults */,
+                        const uint8_t* mask_dev /* u8[N] or NULL */, const float* policy_dev /* f32[N,2] in */,
+                        float* actions_dev /* f32[N,2] out; may be policy_dev itself */,
+                        int32_t* mode_dev /* i32[N] or NULL */, float* clear_dev /* f32[N,3] or NULL: d_min, d_front, d_block */,
+                        void* stream);
 
 /* Synchronises `stream` and reports (then clears) the env's sticky device-side status word: MRCA_OK, or MRCA_ERR_HIP with
  * mrca_last_error() saying what went wrong on the device since the last check.  Today one condition: the ordered

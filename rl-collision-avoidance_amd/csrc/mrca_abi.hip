@@ -24,6 +24,7 @@
 #include "mrca_orca.h"
 #include "mrca_dwa.h"
 #include "mrca_noise.h"
+#include "mrca_hybrid.h"
 #include "mrca_pass_plan.h"
 #include "mrca_render.h"
 #include "mrca_rollout_store.h"
@@ -1023,6 +1024,63 @@ int mrca_scan_noise(mrca_env* env, const mrca_scan_noise_params* params, const u
     memcpy(&q, &p, sizeof q);
     DeviceGuard guard(env->cfg.device);
     mrca::launch_scan_noise(env->view, q, mask_dev, env->cfg.lazy_obs ? 0 : (MRCA_VIEW_SCAN | MRCA_VIEW_OBS), static_cast<hipStream_t>(stream));
+    HIP_TRY(hipGetLastError());
+    return MRCA_OK;
+}
+
+static_assert(sizeof(mrca_hybrid_params) == sizeof(mrca::HybridParams) &&
+                  offsetof(mrca_hybrid_params, max_speed) == offsetof(mrca::HybridParams, max_speed),
+              "mrca_hybrid_params and mrca::HybridParams are one layout");
+
+int mrca_hybrid_default_params(mrca_hybrid_params* out) {
+    if (!out) return fail(MRCA_ERR_INVALID, "mrca_hybrid_default_params: out is NULL");
+    // (safe_scale, corridor, look): tuned on the closed-loop circles, profiles/hybrid/defaults.txt
+    out->risk_dist = 0.6f;
+    out->stop_dist = 0.3f;          // (the footprint's half diagonal is 0.2907 m)
+    out->safe_scale = 0.75f;
+    out->corridor = 1.0f;
+    out->look = 6.0f;               // as far as the lidar sees
+    out->front_cos = 0.5f;          // the front 120 degrees
+    out->v_pid = 1.0f;
+    out->k_omega = 6.0f;            // ORCA's
+    out->max_speed = 1.0f;
+    return MRCA_OK;
+}
+
+int mrca_hybrid_actions(mrca_env* env, const mrca_hybrid_params* params, const uint8_t* mask_dev, const float* policy_dev,
+                        float* actions_dev, int32_t* mode_dev, float* clear_dev, void* stream) {
+    // everything that can be judged without the env, then the env
+    mrca_hybrid_params p;
+    if (params) p = *params;
+    else mrca_hybrid_default_params(&p);
+    const float fl[9] = {p.risk_dist, p.stop_dist, p.safe_scale, p.corridor, p.look, p.front_cos, p.v_pid, p.k_omega, p.max_speed};
+    static const char* const names[9] = {"risk_dist", "stop_dist", "safe_scale", "corridor", "look", "front_cos", "v_pid", "k_omega",
+                                         "max_speed"};
+    for (int i = 0; i < 9; ++i)
+        if (!std::isfinite(fl[i])) return fail(MRCA_ERR_INVALID, "mrca_hybrid_actions: %s is not finite", names[i]);
+    if (!(p.stop_dist >= 0.0f)) return fail(MRCA_ERR_INVALID, "mrca_hybrid_actions: stop_dist must be >= 0");
+    if (!(p.stop_dist < p.risk_dist)) return fail(MRCA_ERR_INVALID, "mrca_hybrid_actions: risk_dist must be > stop_dist");
+    if (!(p.risk_dist <= 6.0f)) return fail(MRCA_ERR_INVALID, "mrca_hybrid_actions: risk_dist must be <= 6");
+    if (!(p.safe_scale >= 0.0f && p.safe_scale <= 1.0f)) return fail(MRCA_ERR_INVALID, "mrca_hybrid_actions: safe_scale outside [0, 1]");
+    if (!(p.corridor > 0.0f)) return fail(MRCA_ERR_INVALID, "mrca_hybrid_actions: corridor must be > 0");
+    if (!(p.look > 0.0f && p.look <= 6.0f)) return fail(MRCA_ERR_INVALID, "mrca_hybrid_actions: look outside (0, 6]");
+    if (!(p.front_cos >= -1.0f && p.front_cos <= 1.0f)) return fail(MRCA_ERR_INVALID, "mrca_hybrid_actions: front_cos outside [-1, 1]");
+    if (!(p.v_pid > 0.0f)) return fail(MRCA_ERR_INVALID, "mrca_hybrid_actions: v_pid must be > 0");
+    if (!(p.k_omega >= 0.0f)) return fail(MRCA_ERR_INVALID, "mrca_hybrid_actions: k_omega must be >= 0");
+    if (!(p.max_speed > 0.0f && p.max_speed <= 1.0f)) return fail(MRCA_ERR_INVALID, "mrca_hybrid_actions: max_speed outside (0, 1]");
+    if (!policy_dev) return fail(MRCA_ERR_INVALID, "mrca_hybrid_actions: policy_dev is NULL");
+    if (reinterpret_cast<uintptr_t>(policy_dev) % 4) return fail(MRCA_ERR_INVALID, "mrca_hybrid_actions: policy_dev must be 4-byte aligned");
+    if (!actions_dev) return fail(MRCA_ERR_INVALID, "mrca_hybrid_actions: actions_dev is NULL");
+    if (reinterpret_cast<uintptr_t>(actions_dev) % 8) return fail(MRCA_ERR_INVALID, "mrca_hybrid_actions: actions_dev must be 8-byte aligned");
+    if (reinterpret_cast<uintptr_t>(mode_dev) % 4) return fail(MRCA_ERR_INVALID, "mrca_hybrid_actions: mode_dev must be 4-byte aligned");
+    if (reinterpret_cast<uintptr_t>(clear_dev) % 4) return fail(MRCA_ERR_INVALID, "mrca_hybrid_actions: clear_dev must be 4-byte aligned");
+    if (!env) return fail(MRCA_ERR_INVALID, "env is NULL");
+    if (!env->reset_seen) return fail(MRCA_ERR_INVALID, "mrca_hybrid_actions before the first mrca_reset: there is no scan yet");
+    mrca::HybridParams q;
+    static_assert(std::is_trivially_copyable<mrca::HybridParams>::value, "");
+    memcpy(&q, &p, sizeof q);
+    DeviceGuard guard(env->cfg.device);
+    mrca::launch_hybrid(env->view, q, mask_dev, policy_dev, actions_dev, mode_dev, clear_dev, static_cast<hipStream_t>(stream));
     HIP_TRY(hipGetLastError());
     return MRCA_OK;
 }

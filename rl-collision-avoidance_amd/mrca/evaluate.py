@@ -105,6 +105,33 @@ def dwa_policy_fn(env, params=None, first=None, other=None, other_name="policy")
     return mixed
 
 
+def hybrid_policy_fn(env, other, params=None):
+    """Hybrid control (``VecStageWorld.hybrid_actions``) behind the controller function ``other``, whatever it is: per robot and
+    tick a PID law where the way to the goal is free, ``other``'s command with v scaled down where something is dangerously
+    close, ``other``'s command elsewhere.  ``fn.mode_shares()`` -> the share of the live robot-ticks (robots without a
+    terminal event yet) spent in each mode; the counts are kept on the device and read when that is called."""
+    from .hybrid import MODE_NAMES
+    codes = torch.tensor(list(MODE_NAMES), dtype=torch.int32, device=env.device)
+    counts = torch.zeros(len(MODE_NAMES), dtype=torch.int64, device=env.device)
+    mode = torch.zeros(env.N, dtype=torch.int32, device=env.device)
+
+    def fn(obs, local_goal, speed):
+        a = env.hybrid_actions(other(obs, local_goal, speed).float().contiguous(), params, mode=mode)
+        live = env.first_result == 0
+        counts.add_(((mode.unsqueeze(1) == codes) & live.unsqueeze(1)).sum(dim=0))
+        return a
+    fn.wants_obs = getattr(other, "wants_obs", True)
+    if getattr(other, "groups", None):
+        fn.groups = other.groups
+
+    def mode_shares():
+        c = counts.tolist()
+        total = sum(c)
+        return {name: (n / total if total else None) for name, n in zip(MODE_NAMES.values(), c)}
+    fn.mode_shares = mode_shares
+    return fn
+
+
 def perturbed_start(env, jitter_xy, jitter_th, seed):
     """Start poses of a circle world with every robot moved off its table pose by U(-jitter_xy, jitter_xy) metres in x
     and y and U(-jitter_th, jitter_th) radians of heading -- drawn from a Philox generator seeded with ``seed``, so that
@@ -240,6 +267,13 @@ def main():
     ap.add_argument("--dwa-first", type=int, default=None, metavar="K",
                     help="robots with local index < K are driven by DWA, the rest by --policy, --orca or the stand-in; the "
                          "metrics are reported for both groups")
+    ap.add_argument("--hybrid", action="store_true", help="hybrid control (mrca_hybrid_actions) behind whatever controller the other "
+                                                          "flags select: a PID law where the way to the goal is free, the command "
+                                                          "scaled down where something is dangerously close, the command as it is "
+                                                          "elsewhere; the result line gains hybrid_params and hybrid_modes (the share "
+                                                          "of live robot-ticks per mode)")
+    ap.add_argument("--hybrid-param", action="append", default=[], metavar="NAME=VALUE",
+                    help="a field of mrca_hybrid_params, e.g. risk_dist=0.8 (repeatable)")
     ap.add_argument("--lidar-noise", default=None, metavar="const=M,prop=P,dropout=Q[,quantum=M]",
                     help="the lidar noise model (mrca_scan_noise) behind every ray cast: range noise of const + prop * range metres "
                          "(an Irwin-Hall deviate of unit variance), beams lost with probability dropout, a read-out step of quantum "
@@ -302,6 +336,15 @@ def main():
         else:
             fn = dwa_policy_fn(env, dwa_params, first=a.dwa_first, other=fn, other_name="orca" if a.orca else "policy")
             name = f"DWA for local index < {a.dwa_first}, else {name}"
+    if a.hybrid_param and not a.hybrid:
+        ap.error("--hybrid-param goes with --hybrid")
+    if a.hybrid:
+        from .hybrid import HybridParams
+        try:
+            hybrid_params = HybridParams.from_assignments(a.hybrid_param)
+        except ValueError as e:
+            ap.error(str(e))
+        fn, name = hybrid_policy_fn(env, fn, hybrid_params), f"hybrid control (mrca_hybrid_actions) behind {name}"
     perturb = tuple(float(v) for v in a.perturb.split(",")) if a.perturb else None
     recorder = None
     if a.render:
@@ -319,6 +362,10 @@ def main():
     if a.dwa or a.dwa_first is not None:
         import dataclasses
         out["dwa_params"] = dataclasses.asdict(dwa_params)
+    if a.hybrid:
+        import dataclasses
+        out["hybrid_params"] = dataclasses.asdict(hybrid_params)
+        out["hybrid_modes"] = fn.mode_shares()
     out["lidar_noise"] = None if noise is None else noise.as_dict()
     out["robots_per_circle"], out["radius_m"] = a.robots, a.radius
     if a.one_circle is not None:

@@ -1,0 +1,50 @@
+"""Parameters of the hybrid control wrapper (include/mrca_env.h: mrca_hybrid_params, mrca_hybrid_actions).  The defaults are the
+library's own (mrca_hybrid_default_params): they are stated once, in C."""
+import ctypes as C
+import dataclasses
+
+from . import _lib
+
+_FIELDS = [name for name, _t in _lib.HybridParamsStruct._fields_]
+
+MODE_NORMAL, MODE_SIMPLE, MODE_EMERGENT, MODE_AT_GOAL = 0, 1, 2, -2
+MODE_NAMES = {MODE_NORMAL: "normal", MODE_SIMPLE: "simple", MODE_EMERGENT: "emergent", MODE_AT_GOAL: "at_goal"}
+
+
+def _library_defaults():
+    st = _lib.HybridParamsStruct()
+    _lib.check(_lib.load().mrca_hybrid_default_params(C.byref(st)), "mrca_hybrid_default_params")
+    return {k: getattr(st, k) for k in _FIELDS}
+
+
+@dataclasses.dataclass
+class HybridParams:
+    """Mirror of mrca_hybrid_params; a field left ``None`` takes the library's default."""
+    risk_dist: float = None             # a return nearer than this makes the robot careful (mode 2) [m], at most 6
+    stop_dist: float = None             # the nearest return ahead at or below this: v = 0 [m], below risk_dist
+    safe_scale: float = None            # the most of the incoming v that mode 2 lets through, 0..1
+    corridor: float = None              # half width of the strip towards the goal that must be free for the PID law [m]
+    look: float = None                  # its length at most [m], at most 6
+    front_cos: float = None             # beams with cos >= this are "ahead"
+    v_pid: float = None                 # speed of the PID law [m/s]
+    k_omega: float = None               # its turn gain
+    max_speed: float = None             # at most 1
+
+    def __post_init__(self):
+        for k, v in _library_defaults().items():
+            if getattr(self, k) is None:
+                setattr(self, k, v)
+
+    def struct(self):
+        return _lib.HybridParamsStruct(**{k: getattr(self, k) for k in _FIELDS})
+
+    @classmethod
+    def from_assignments(cls, items):
+        """``["risk_dist=0.8", "look=3"]`` (the evaluator's --hybrid-param) -> HybridParams."""
+        kw = {}
+        for it in items or ():
+            k, _eq, v = it.partition("=")
+            if k not in _FIELDS or not _eq:
+                raise ValueError(f"--hybrid-param {it!r}: expected name=value with name in {_FIELDS}")
+            kw[k] = float(v)
+        return cls(**kw)

@@ -296,6 +296,24 @@ class VecStageWorld:
                                              self._ptr(score, torch.float32, self.N), self._stream()), "mrca_dwa_actions")
         return out
 
+    def hybrid_actions(self, actions, params=None, mask=None, out=None, mode=None, clear=None):
+        """Hybrid control behind a policy (mrca_hybrid_actions): per robot, ``actions`` (float32[N,2], the policy's (v, omega))
+        replaced by a PID law where nothing stands between the robot and its goal, scaled down in v where something is
+        dangerously close, kept as it is elsewhere -- decided from each robot's newest scan and local goal alone.  One launch
+        on the current stream, nothing synchronises, nothing of the env is written: ``env.step(env.hybrid_actions(a))`` is one
+        tick.  ``out=None`` works IN PLACE on ``actions`` and returns it.  ``params``: a ``hybrid.HybridParams`` (default: the
+        library's); ``mask``: a uint8[N] tensor, rows with 0 keep what ``out`` (and ``mode`` / ``clear``) hold; ``mode``: an
+        int32[N] tensor that takes 0 (the policy), 1 (PID), 2 (the policy made careful) or -2 (at the goal); ``clear``: a
+        float32[N,3] tensor that takes (d_min, d_front, d_block)."""
+        if out is None:
+            out = actions
+        st = None if params is None else params.struct()
+        _lib.check(self.lib.mrca_hybrid_actions(self._h, None if st is None else C.byref(st), self._ptr(mask, torch.uint8, self.N),
+                                                self._ptr(actions, torch.float32, 2 * self.N), self._ptr(out, torch.float32, 2 * self.N),
+                                                self._ptr(mode, torch.int32, self.N), self._ptr(clear, torch.float32, 3 * self.N),
+                                                self._stream()), "mrca_hybrid_actions")
+        return out
+
     def scan_noise(self, params=None, mask=None):
         """The lidar noise model (mrca_scan_noise) applied IN PLACE to the newest scan row of every robot (``mask``: a uint8[N]
         tensor, rows with 0 are not touched): range noise, quantisation and dropout as ``params`` (a ``noise.ScanNoiseParams``;
