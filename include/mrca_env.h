@@ -33,7 +33,9 @@
 extern "C" {
 #endif
 
-/* 6, additive: mrca_hybrid_actions, mrca_hybrid_default_params (hybrid control behind a policy: PID, policy or safe policy per robot).
+/* 6, additive: mrca_hybrid_plan, mrca_hybrid_commit, mrca_safe_policy_default_params, mrca_lidar_features_scaled,
+ * mrca_lidar_features_bf16_scaled (hybrid control in the paper's form: the safe policy is the network on a rescaled scan).
+ * 6, additive: mrca_hybrid_actions, mrca_hybrid_default_params (hybrid control behind a policy: PID, policy or safe policy per robot).
  * 6, additive: mrca_scan_noise, mrca_scan_noise_default_params (a lidar noise model applied to the ring in place).
  * 6, additive: mrca_dwa_actions,mrca_dwa_default_params (a sensor-level DWA baseline beside ORCA).
  * 6, additive: mrca_orca_actions_any (the ORCA baseline on worlds of any size); mrca_move_worlds / mrca_observe_worlds take the
@@ -436,8 +438,8 @@ int mrca_scan_noise(mrca_env* env, const mrca_scan_noise_params* params /* host,
  *   mode 1 (simple) iff not emergent and no beam blocks: ORCA's conversion of the velocity v_pid u to (v, omega) at heading 0
  *          (v = min(v_pid ux, max_speed) if ux > 0 else 0; omega = clamp(k_omega uy) if ux > 0 else +-clamp(k_omega));
  *   mode 0 (normal) otherwise: (vp, wp) copied bit for bit, a NaN or a -0.0 included.
- * NOT THE PAPER'S LITERAL FORM: its safe policy runs the network again on a rescaled scan; this call sits behind the policy
- * and scales its command only (mode_dev lets a caller run that second forward for the robots of mode 2 itself), and the
+ * NOT THE PAPER'S LITERAL FORM: its safe policy runs the network on a rescaled scan; this call sits behind the policy
+ * and scales its command only (the literal form is mrca_hybrid_plan / mrca_hybrid_commit below), and the
  * corridor test stands in for the paper's "goal nearer than every obstacle".  The rule is csrc/mrca_hybrid_device.h,
  * separately rounded fp32 steps in a fixed order, minima and a count over the beams: reproducible bit for bit
  * (tests/hybrid_ref.py restates it in NumPy).
@@ -472,6 +474,51 @@ int mrca_hybrid_actions(mrca_env* env, const mrca_hybrid_params* params /* host,
                         float* actions_dev /* f32[N,2] out; may be policy_dev itself */,
                         int32_t* mode_dev /* i32[N] or NULL */, float* clear_dev /* f32[N,3] or NULL: d_min, d_front, d_block */,
                         void* stream);
+
+/* Hybrid control in the PAPER'S FORM (Fan, Long, Liu, Pan, IJRR 2020, Sec. 5): the safe policy is the NETWORK run on a scan in
+ * which obstacles look nearer, its speed capped.  The mode of mrca_hybrid_actions does not depend on the incoming command, so it
+ * is known before the forward runs, and a tick is   plan -> ONE forward with a per-robot scan scale -> commit -> step:
+ *   mrca_hybrid_plan     mode_dev[n] = exactly the mode mrca_hybrid_actions reports on the same state (same params);
+ *                        scale_dev[n] = scan_scale in mode 2, else 1.0f;  pid_dev[n] = the PID command in mode 1, (0, 0) in the
+ *                        other modes;  clear_dev[n] (optional) = d_min, d_front, d_block as mrca_hybrid_actions gives them
+ *   the forward          mrca_lidar_features_scaled / mrca_lidar_features_bf16_scaled (below) with scale_dev, then the rest of the
+ *                        inference as it is
+ *   mrca_hybrid_commit   mode 0: the forward's (vp, wp) bit for bit, a NaN or a -0.0 kept;  modes 1 and -2: pid_dev[n];
+ *                        mode 2: (vp > v_cap ? v_cap : vp, wp) -- a NaN vp stays a NaN, wp is kept so that the robot may still
+ *                        turn away at full rate;  any other mode value: (vp, wp) copied
+ * OUR READING OF THE PAPER'S "SCALED SCAN" (the front ends below): a beam that returned nothing (exactly 6.0, the lidar's range)
+ * stays "nothing", a return at r is seen at r s; and the WHOLE stack of three frames is scaled by the CURRENT tick's factor, so
+ * that the frames stay mutually consistent (a robot entering the safe mode sees no jump between frames).  The clearance
+ * scaling s(d_front) of mrca_hybrid_actions' mode 2 is deliberately NOT applied by the commit: the scaled scan is the paper's
+ * mechanism, and stacking ours on top would measure neither.  The rule is csrc/mrca_safe_device.h on top of
+ * csrc/mrca_hybrid_device.h (tests/safe_ref.py restates it in NumPy): reproducible bit for bit.
+ *
+ * mrca_hybrid_plan: ONE launch, one wavefront per robot, the params travel as kernel arguments; reads the newest ring row
+ * (MRCA_F_SCAN_RING through MRCA_F_RING_HEAD) and MRCA_F_LOCAL_GOAL, NO command; writes nothing of the env; asynchronous on
+ * `stream`, capturable.  Rows whose mask byte is 0 are not touched (pre-fill scale_dev with ones where a mask is used).
+ *   hybrid_params  host; NULL = mrca_hybrid_default_params (the classification; safe_scale is not used here)
+ *   safe_params    host; NULL = mrca_safe_policy_default_params: scan_scale 0.3, v_cap 0.75 (profiles/safe_policy/defaults.txt)
+ *   mask_dev u8[N] or NULL = all;  mode_dev i32[N], scale_dev f32[N], pid_dev f32[N,2] (8-byte aligned): out, not NULL;
+ *   clear_dev f32[N,3] or NULL
+ * Validated before the first HIP call (MRCA_ERR_INVALID): the table of mrca_hybrid_actions for hybrid_params; scan_scale and
+ * v_cap finite, 0 < scan_scale <= 1, 0 < v_cap <= 1; the three outputs not NULL; a call before the env's first mrca_reset is
+ * refused.
+ *
+ * mrca_hybrid_commit: ONE launch, one thread per robot, needs no env.  policy_dev f32[N,2] in; actions_dev f32[N,2] out, 8-byte
+ * aligned, may be policy_dev itself; mode_dev, pid_dev as the plan wrote them; rows whose mask byte is 0 are not touched. */
+typedef struct mrca_safe_policy_params {
+    float scan_scale;   /* what a return's range is multiplied by in mode 2, in (0, 1] */
+    float v_cap;        /* the most v that mode 2 lets through, in (0, 1] */
+} mrca_safe_policy_params;
+int mrca_safe_policy_default_params(mrca_safe_policy_params* out);
+int mrca_hybrid_plan(mrca_env* env, const mrca_hybrid_params* hybrid_params /* host, NULL = defaults */,
+                     const mrca_safe_policy_params* safe_params /* host, NULL = defaults */,
+                     const uint8_t* mask_dev /* u8[N] or NULL */, int32_t* mode_dev /* i32[N] */, float* scale_dev /* f32[N] */,
+                     float* pid_dev /* f32[N,2] */, float* clear_dev /* f32[N,3] or NULL */, void* stream);
+int mrca_hybrid_commit(int32_t n_robots, const mrca_safe_policy_params* safe_params /* host, NULL = defaults */,
+                       const uint8_t* mask_dev /* u8[N] or NULL */, const int32_t* mode_dev /* i32[N] */,
+                       const float* pid_dev /* f32[N,2] */, const float* policy_dev /* f32[N,2] in */,
+                       float* actions_dev /* f32[N,2] out; may be policy_dev itself */, void* stream);
 
 /* Synchronises `stream` and reports (then clears) the env's sticky device-side status word: MRCA_OK, or MRCA_ERR_HIP with
  * mrca_last_error() saying what went wrong on the device since the last check.  Today one condition: the ordered
@@ -538,6 +585,26 @@ int mrca_lidar_features_rows(const float* frames_dev, const int32_t* rows_dev, i
 int mrca_lidar_features_bf16(const float* obs_dev, const uint8_t* obs_head_dev, int32_t raw_scans, int32_t n_robots,
                              int32_t frames, int32_t beams, const float* w1_dev, const float* b1_dev, const float* w2_dev,
                              const float* b2_dev, uint16_t* feat_dev, void* stream);
+
+/* The two front ends with a PER-ROBOT SCAN SCALE: the safe policy of hybrid control in the paper's form (mrca_hybrid_plan above)
+ * in the same single forward as everybody else's -- no second pass, no gathered copy of the stacks, no scaled ring in memory.
+ * RAW RING FORM ONLY: obs_dev = MRCA_F_SCAN_RING, obs_head_dev = MRCA_F_RING_HEAD (normalised observations cannot be rescaled
+ * without undoing the normalisation; the row-table form belongs to the update).  scale_dev f32[N].  The rule is ONE separately
+ * rounded fp32 multiply in front of x / 6 - 0.5, for every beam of ALL THREE frames of robot n; with x = |raw range|:
+ *     x' = x < 6.0f ? x * scale[n] : x;      obs = x' / 6 - 0.5
+ * Our reading of the paper's "scaled scan": a beam that returned nothing (exactly 6.0, the lidar's range) stays "nothing", a
+ * return at r is seen at r s; and the whole stack is scaled by the CURRENT tick's factor, so that the three frames stay mutually
+ * consistent (a robot entering the safe mode sees no jump between frames).  With scale[n] == 1.0f every bit of feat equals
+ * mrca_lidar_features' / mrca_lidar_features_bf16's on the same ring (x * 1.0f == x for every finite x).  In the bf16 form the
+ * multiply happens in fp32 before rounding point (1); the rounding points are otherwise those of mrca_lidar_features_bf16.
+ * obs_head_dev == NULL or scale_dev == NULL: MRCA_ERR_INVALID; frames 3 and beams 512, else MRCA_ERR_UNSUPPORTED; alignment as
+ * the calls above.  scale_dev is NOT validated on the device: its producer (mrca_hybrid_plan) guarantees 0 < s <= 1. */
+int mrca_lidar_features_scaled(const float* obs_dev, const uint8_t* obs_head_dev, const float* scale_dev, int32_t n_robots,
+                               int32_t frames, int32_t beams, const float* w1_dev, const float* b1_dev, const float* w2_dev,
+                               const float* b2_dev, float* feat_dev, void* stream);
+int mrca_lidar_features_bf16_scaled(const float* obs_dev, const uint8_t* obs_head_dev, const float* scale_dev, int32_t n_robots,
+                                    int32_t frames, int32_t beams, const float* w1_dev, const float* b1_dev, const float* w2_dev,
+                                    const float* b2_dev, uint16_t* feat_dev, void* stream);
 
 /* The rest of the rollout inference behind fc1 in one kernel (model/net.py:41-55,61-70: ReLU, cat with goal and speed,
  * fc2 + ReLU of both towers, actor1 / actor2 / critic heads with sigmoid / tanh; model/ppo.py:57-82 generate_action:

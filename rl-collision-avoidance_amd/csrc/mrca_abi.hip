@@ -25,6 +25,7 @@
 #include "mrca_dwa.h"
 #include "mrca_noise.h"
 #include "mrca_hybrid.h"
+#include "mrca_safe.h"
 #include "mrca_pass_plan.h"
 #include "mrca_render.h"
 #include "mrca_rollout_store.h"
@@ -1047,27 +1048,33 @@ int mrca_hybrid_default_params(mrca_hybrid_params* out) {
     return MRCA_OK;
 }
 
+// the table of mrca_hybrid_params, for `who` (mrca_hybrid_actions, mrca_hybrid_plan): MRCA_OK or the failure
+static int check_hybrid_params(const char* who, const mrca_hybrid_params& p) {
+    const float fl[9] = {p.risk_dist, p.stop_dist, p.safe_scale, p.corridor, p.look, p.front_cos, p.v_pid, p.k_omega, p.max_speed};
+    static const char* const names[9] = {"risk_dist", "stop_dist", "safe_scale", "corridor", "look", "front_cos", "v_pid", "k_omega",
+                                         "max_speed"};
+    for (int i = 0; i < 9; ++i)
+        if (!std::isfinite(fl[i])) return fail(MRCA_ERR_INVALID, "%s: %s is not finite", who, names[i]);
+    if (!(p.stop_dist >= 0.0f)) return fail(MRCA_ERR_INVALID, "%s: stop_dist must be >= 0", who);
+    if (!(p.stop_dist < p.risk_dist)) return fail(MRCA_ERR_INVALID, "%s: risk_dist must be > stop_dist", who);
+    if (!(p.risk_dist <= 6.0f)) return fail(MRCA_ERR_INVALID, "%s: risk_dist must be <= 6", who);
+    if (!(p.safe_scale >= 0.0f && p.safe_scale <= 1.0f)) return fail(MRCA_ERR_INVALID, "%s: safe_scale outside [0, 1]", who);
+    if (!(p.corridor > 0.0f)) return fail(MRCA_ERR_INVALID, "%s: corridor must be > 0", who);
+    if (!(p.look > 0.0f && p.look <= 6.0f)) return fail(MRCA_ERR_INVALID, "%s: look outside (0, 6]", who);
+    if (!(p.front_cos >= -1.0f && p.front_cos <= 1.0f)) return fail(MRCA_ERR_INVALID, "%s: front_cos outside [-1, 1]", who);
+    if (!(p.v_pid > 0.0f)) return fail(MRCA_ERR_INVALID, "%s: v_pid must be > 0", who);
+    if (!(p.k_omega >= 0.0f)) return fail(MRCA_ERR_INVALID, "%s: k_omega must be >= 0", who);
+    if (!(p.max_speed > 0.0f && p.max_speed <= 1.0f)) return fail(MRCA_ERR_INVALID, "%s: max_speed outside (0, 1]", who);
+    return MRCA_OK;
+}
+
 int mrca_hybrid_actions(mrca_env* env, const mrca_hybrid_params* params, const uint8_t* mask_dev, const float* policy_dev,
                         float* actions_dev, int32_t* mode_dev, float* clear_dev, void* stream) {
     // everything that can be judged without the env, then the env
     mrca_hybrid_params p;
     if (params) p = *params;
     else mrca_hybrid_default_params(&p);
-    const float fl[9] = {p.risk_dist, p.stop_dist, p.safe_scale, p.corridor, p.look, p.front_cos, p.v_pid, p.k_omega, p.max_speed};
-    static const char* const names[9] = {"risk_dist", "stop_dist", "safe_scale", "corridor", "look", "front_cos", "v_pid", "k_omega",
-                                         "max_speed"};
-    for (int i = 0; i < 9; ++i)
-        if (!std::isfinite(fl[i])) return fail(MRCA_ERR_INVALID, "mrca_hybrid_actions: %s is not finite", names[i]);
-    if (!(p.stop_dist >= 0.0f)) return fail(MRCA_ERR_INVALID, "mrca_hybrid_actions: stop_dist must be >= 0");
-    if (!(p.stop_dist < p.risk_dist)) return fail(MRCA_ERR_INVALID, "mrca_hybrid_actions: risk_dist must be > stop_dist");
-    if (!(p.risk_dist <= 6.0f)) return fail(MRCA_ERR_INVALID, "mrca_hybrid_actions: risk_dist must be <= 6");
-    if (!(p.safe_scale >= 0.0f && p.safe_scale <= 1.0f)) return fail(MRCA_ERR_INVALID, "mrca_hybrid_actions: safe_scale outside [0, 1]");
-    if (!(p.corridor > 0.0f)) return fail(MRCA_ERR_INVALID, "mrca_hybrid_actions: corridor must be > 0");
-    if (!(p.look > 0.0f && p.look <= 6.0f)) return fail(MRCA_ERR_INVALID, "mrca_hybrid_actions: look outside (0, 6]");
-    if (!(p.front_cos >= -1.0f && p.front_cos <= 1.0f)) return fail(MRCA_ERR_INVALID, "mrca_hybrid_actions: front_cos outside [-1, 1]");
-    if (!(p.v_pid > 0.0f)) return fail(MRCA_ERR_INVALID, "mrca_hybrid_actions: v_pid must be > 0");
-    if (!(p.k_omega >= 0.0f)) return fail(MRCA_ERR_INVALID, "mrca_hybrid_actions: k_omega must be >= 0");
-    if (!(p.max_speed > 0.0f && p.max_speed <= 1.0f)) return fail(MRCA_ERR_INVALID, "mrca_hybrid_actions: max_speed outside (0, 1]");
+    if (const int rc = check_hybrid_params("mrca_hybrid_actions", p)) return rc;
     if (!policy_dev) return fail(MRCA_ERR_INVALID, "mrca_hybrid_actions: policy_dev is NULL");
     if (reinterpret_cast<uintptr_t>(policy_dev) % 4) return fail(MRCA_ERR_INVALID, "mrca_hybrid_actions: policy_dev must be 4-byte aligned");
     if (!actions_dev) return fail(MRCA_ERR_INVALID, "mrca_hybrid_actions: actions_dev is NULL");
@@ -1081,6 +1088,81 @@ int mrca_hybrid_actions(mrca_env* env, const mrca_hybrid_params* params, const u
     memcpy(&q, &p, sizeof q);
     DeviceGuard guard(env->cfg.device);
     mrca::launch_hybrid(env->view, q, mask_dev, policy_dev, actions_dev, mode_dev, clear_dev, static_cast<hipStream_t>(stream));
+    HIP_TRY(hipGetLastError());
+    return MRCA_OK;
+}
+
+static_assert(sizeof(mrca_safe_policy_params) == sizeof(mrca::SafeParams) &&
+                  offsetof(mrca_safe_policy_params, v_cap) == offsetof(mrca::SafeParams, v_cap),
+              "mrca_safe_policy_params and mrca::SafeParams are one layout");
+
+int mrca_safe_policy_default_params(mrca_safe_policy_params* out) {
+    if (!out) return fail(MRCA_ERR_INVALID, "mrca_safe_policy_default_params: out is NULL");
+    // tuned on the closed-loop circles, profiles/safe_policy/defaults.txt
+    out->scan_scale = 0.3f;
+    out->v_cap = 0.75f;
+    return MRCA_OK;
+}
+
+// the table of mrca_safe_policy_params, for `who`
+static int check_safe_params(const char* who, const mrca_safe_policy_params& p) {
+    if (!std::isfinite(p.scan_scale)) return fail(MRCA_ERR_INVALID, "%s: scan_scale is not finite", who);
+    if (!std::isfinite(p.v_cap)) return fail(MRCA_ERR_INVALID, "%s: v_cap is not finite", who);
+    if (!(p.scan_scale > 0.0f && p.scan_scale <= 1.0f)) return fail(MRCA_ERR_INVALID, "%s: scan_scale outside (0, 1]", who);
+    if (!(p.v_cap > 0.0f && p.v_cap <= 1.0f)) return fail(MRCA_ERR_INVALID, "%s: v_cap outside (0, 1]", who);
+    return MRCA_OK;
+}
+
+int mrca_hybrid_plan(mrca_env* env, const mrca_hybrid_params* hybrid_params, const mrca_safe_policy_params* safe_params,
+                     const uint8_t* mask_dev, int32_t* mode_dev, float* scale_dev, float* pid_dev, float* clear_dev, void* stream) {
+    // everything that can be judged without the env, then the env
+    mrca_hybrid_params p;
+    if (hybrid_params) p = *hybrid_params;
+    else mrca_hybrid_default_params(&p);
+    if (const int rc = check_hybrid_params("mrca_hybrid_plan", p)) return rc;
+    mrca_safe_policy_params sp;
+    if (safe_params) sp = *safe_params;
+    else mrca_safe_policy_default_params(&sp);
+    if (const int rc = check_safe_params("mrca_hybrid_plan", sp)) return rc;
+    if (!mode_dev) return fail(MRCA_ERR_INVALID, "mrca_hybrid_plan: mode_dev is NULL");
+    if (reinterpret_cast<uintptr_t>(mode_dev) % 4) return fail(MRCA_ERR_INVALID, "mrca_hybrid_plan: mode_dev must be 4-byte aligned");
+    if (!scale_dev) return fail(MRCA_ERR_INVALID, "mrca_hybrid_plan: scale_dev is NULL");
+    if (reinterpret_cast<uintptr_t>(scale_dev) % 4) return fail(MRCA_ERR_INVALID, "mrca_hybrid_plan: scale_dev must be 4-byte aligned");
+    if (!pid_dev) return fail(MRCA_ERR_INVALID, "mrca_hybrid_plan: pid_dev is NULL");
+    if (reinterpret_cast<uintptr_t>(pid_dev) % 8) return fail(MRCA_ERR_INVALID, "mrca_hybrid_plan: pid_dev must be 8-byte aligned");
+    if (reinterpret_cast<uintptr_t>(clear_dev) % 4) return fail(MRCA_ERR_INVALID, "mrca_hybrid_plan: clear_dev must be 4-byte aligned");
+    if (!env) return fail(MRCA_ERR_INVALID, "env is NULL");
+    if (!env->reset_seen) return fail(MRCA_ERR_INVALID, "mrca_hybrid_plan before the first mrca_reset: there is no scan yet");
+    mrca::HybridParams q;
+    mrca::SafeParams sq;
+    static_assert(std::is_trivially_copyable<mrca::SafeParams>::value, "");
+    memcpy(&q, &p, sizeof q);
+    memcpy(&sq, &sp, sizeof sq);
+    DeviceGuard guard(env->cfg.device);
+    mrca::launch_hybrid_plan(env->view, q, sq, mask_dev, mode_dev, scale_dev, pid_dev, clear_dev, static_cast<hipStream_t>(stream));
+    HIP_TRY(hipGetLastError());
+    return MRCA_OK;
+}
+
+int mrca_hybrid_commit(int32_t n_robots, const mrca_safe_policy_params* safe_params, const uint8_t* mask_dev, const int32_t* mode_dev,
+                       const float* pid_dev, const float* policy_dev, float* actions_dev, void* stream) {
+    mrca_safe_policy_params sp;
+    if (safe_params) sp = *safe_params;
+    else mrca_safe_policy_default_params(&sp);
+    if (const int rc = check_safe_params("mrca_hybrid_commit", sp)) return rc;
+    if (n_robots < 1) return fail(MRCA_ERR_INVALID, "mrca_hybrid_commit: n_robots %d (needs >= 1)", n_robots);
+    if (!mode_dev) return fail(MRCA_ERR_INVALID, "mrca_hybrid_commit: mode_dev is NULL");
+    if (reinterpret_cast<uintptr_t>(mode_dev) % 4) return fail(MRCA_ERR_INVALID, "mrca_hybrid_commit: mode_dev must be 4-byte aligned");
+    if (!pid_dev) return fail(MRCA_ERR_INVALID, "mrca_hybrid_commit: pid_dev is NULL");
+    if (reinterpret_cast<uintptr_t>(pid_dev) % 8) return fail(MRCA_ERR_INVALID, "mrca_hybrid_commit: pid_dev must be 8-byte aligned");
+    if (!policy_dev) return fail(MRCA_ERR_INVALID, "mrca_hybrid_commit: policy_dev is NULL");
+    if (reinterpret_cast<uintptr_t>(policy_dev) % 4) return fail(MRCA_ERR_INVALID, "mrca_hybrid_commit: policy_dev must be 4-byte aligned");
+    if (!actions_dev) return fail(MRCA_ERR_INVALID, "mrca_hybrid_commit: actions_dev is NULL");
+    if (reinterpret_cast<uintptr_t>(actions_dev) % 8) return fail(MRCA_ERR_INVALID, "mrca_hybrid_commit: actions_dev must be 8-byte aligned");
+    mrca::SafeParams sq;
+    memcpy(&sq, &sp, sizeof sq);
+    DeviceGuard guard(mrca::device_of(actions_dev));     // launch where the buffers live
+    mrca::launch_hybrid_commit(n_robots, sq, mask_dev, mode_dev, pid_dev, policy_dev, actions_dev, static_cast<hipStream_t>(stream));
     HIP_TRY(hipGetLastError());
     return MRCA_OK;
 }

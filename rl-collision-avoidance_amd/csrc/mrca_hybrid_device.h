@@ -9,7 +9,7 @@
 // WHERE THIS DIFFERS FROM THE PAPER.  The paper's safe policy runs the NETWORK AGAIN on a scan scaled down so that obstacles
 // look nearer, and clips its output.  This rule sits BEHIND the policy and scales the command it has already given: v is
 // multiplied by s in [0, safe_scale], omega is kept, so the robot can still turn away at full rate.  The mode goes out with the
-// command, so a caller who wants the literal form can run that second forward for the robots of mode 2 itself.  And the paper's
+// command; the literal form -- the network on the rescaled scan, in the same forward -- is mrca_safe_device.h's.  And the paper's
 // "the goal is nearer than every obstacle" is here a CORRIDOR test: no return stands within `corridor` metres of the straight
 // segment from the robot towards its goal, `look` metres long at most.
 //

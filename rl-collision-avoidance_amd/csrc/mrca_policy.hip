@@ -113,12 +113,19 @@ __device__ __forceinline__ float norm_scan(float x) {
     return __builtin_fmaf(r, inv6, q) - 0.5f;
 }
 
+// The safe policy's scan (mrca_lidar_features_scaled): a return at r is seen at r s, a beam that returned
+// nothing (the lidar's range, 6) stays "nothing".  ONE separately rounded fp32 multiply in front of norm_scan; x 1.0f is the
+// identity on every finite x.
+__device__ __forceinline__ float scale_range(float x, float s) { return x < 6.0f ? x * s : x; }
+
 // RAW: `obs` holds raw ranges (the env's ring of scans); the observation is formed while the scan is staged
-template <bool RAW>
+// SCALED (RAW only): robot n's ranges are multiplied by scale[n] on the way, all three frames alike
+template <bool RAW, bool SCALED>
 __global__ __launch_bounds__(64 * kWavesPerBlock) void lidar_features_kernel(
     const float* __restrict__ obs, const uint8_t* __restrict__ head, const int32_t* __restrict__ rows, int n_robots,
     const float* __restrict__ w1, const float* __restrict__ b1,
-    const float* __restrict__ w2, const float* __restrict__ b2, float* __restrict__ feat) {
+    const float* __restrict__ w2, const float* __restrict__ b2, float* __restrict__ feat, const float* __restrict__ scale) {
+    static_assert(RAW || !SCALED, "only raw ranges can be rescaled");
     extern __shared__ __attribute__((aligned(16))) float lds_all[];
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
@@ -220,11 +227,19 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void lidar_features_kernel(
     float4 sx[6];
     request_scan(sx, obs, frame_rows(head, rows, n), lane);
     FrameRows3 fr_next = frame_rows(head, rows, n + stride < n_robots ? n + stride : n);
+    // SCALED: the factor travels WITH the frame rows -- sc belongs to the scan that sits in sx, sc_next to the robot fr_next
+    // describes (fetched one robot ahead like it: no dependent load in front of the six float4 loads)
+    float sc = 1.0f, sc_next = 1.0f;
+    if (SCALED) {
+        sc = scale[n];
+        sc_next = scale[n + stride < n_robots ? n + stride : n];
+    }
 
 #define MRCA_STAGE_SCAN(q)                                                                               \
     {                                                                                                    \
         const int idx = (q) * 64 + lane; /* float4 index: ci = idx / 128, m = idx % 128 -> x[ci][4m .. 4m+3] */ \
         float4 v = sx[q];                                                                                \
+        if (SCALED) v = make_float4(scale_range(fabsf(v.x), sc), scale_range(fabsf(v.y), sc), scale_range(fabsf(v.z), sc), scale_range(fabsf(v.w), sc)); \
         if (RAW) v = make_float4(norm_scan(fabsf(v.x)), norm_scan(fabsf(v.y)), norm_scan(fabsf(v.z)), norm_scan(fabsf(v.w))); /* |x|: rows stored under ABI 4-5 carried a flag in the sign bit */ \
         const int ci = idx >> 7, m = idx & 127;                                                          \
         float* xe = lds + kXE + ci * kXPitch + 2 * m;                                                    \
@@ -237,12 +252,20 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void lidar_features_kernel(
 #define MRCA_REQUEST_NEXT()                                                                              \
     if (n + stride < n_robots) {                                                                         \
         request_scan(sx, obs, fr_next, lane);                                                            \
-        if (n + 2 * stride < n_robots) fr_next = frame_rows(head, rows, n + 2 * stride);                 \
+        if (SCALED) sc = sc_next;                                                                        \
+        if (n + 2 * stride < n_robots) {                                                                 \
+            fr_next = frame_rows(head, rows, n + 2 * stride);                                            \
+            if (SCALED) sc_next = scale[n + 2 * stride];                                                 \
+        }                                                                                                \
     }
 #define MRCA_REQUEST_NEXT_AFTER() /* inside the loop: robot n + stride has just been staged */             \
     if (n + 2 * stride < n_robots) {                                                                     \
         request_scan(sx, obs, fr_next, lane);                                                            \
-        if (n + 3 * stride < n_robots) fr_next = frame_rows(head, rows, n + 3 * stride);                 \
+        if (SCALED) sc = sc_next;                                                                        \
+        if (n + 3 * stride < n_robots) {                                                                 \
+            fr_next = frame_rows(head, rows, n + 3 * stride);                                            \
+            if (SCALED) sc_next = scale[n + 3 * stride];                                                 \
+        }                                                                                                \
     }
 #define MRCA_CONV1_LOAD(buf, T)                                                                          \
     _Pragma("unroll") for (int s_ = 0; s_ < 8; ++s_) {                                                   \
@@ -464,9 +487,11 @@ extern "C" int mrca_debug_fwd_stamps(double* out /* [8] */) {
 }
 #endif
 
+// scale_dev != NULL: the scaled instantiation (raw ring form; mrca_lidar_features_scaled has checked that)
 static int lidar_features_impl(const float* obs_dev, const uint8_t* obs_head_dev, const int32_t* rows_dev, int32_t raw_scans,
                                int32_t n_robots, int32_t frames, int32_t beams, const float* w1_dev, const float* b1_dev,
-                               const float* w2_dev, const float* b2_dev, float* feat_dev, void* stream) {
+                               const float* w2_dev, const float* b2_dev, float* feat_dev, void* stream,
+                               const float* scale_dev = nullptr) {
     using namespace mrca_policy;
     if (!obs_dev || !w1_dev || !b1_dev || !w2_dev || !b2_dev || !feat_dev)
         return mrca::set_error(MRCA_ERR_INVALID, "mrca_lidar_features: NULL pointer");
@@ -485,10 +510,13 @@ static int lidar_features_impl(const float* obs_dev, const uint8_t* obs_head_dev
         d.cus = cus;
     }
     if (!d.attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(lidar_features_kernel<false>),
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(lidar_features_kernel<false, false>),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e == hipSuccess)
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(lidar_features_kernel<true>),
+            e = hipFuncSetAttribute(reinterpret_cast<const void*>(lidar_features_kernel<true, false>),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e == hipSuccess)
+            e = hipFuncSetAttribute(reinterpret_cast<const void*>(lidar_features_kernel<true, true>),
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess)
             return mrca::set_error(MRCA_ERR_HIP, "mrca_lidar_features: %zu B of dynamic LDS refused: %s", lds,
@@ -499,12 +527,18 @@ static int lidar_features_impl(const float* obs_dev, const uint8_t* obs_head_dev
     int blocks = d.cus;
     const int pairs_needed = (n_robots + 1) / 2;          // a block holds two (actor, critic) pairs
     if (blocks > pairs_needed) blocks = pairs_needed;
-    if (raw_scans)
-        hipLaunchKernelGGL(lidar_features_kernel<true>, dim3(blocks), dim3(64 * kWavesPerBlock), lds,
-                           static_cast<hipStream_t>(stream), obs_dev, obs_head_dev, rows_dev, n_robots, w1_dev, b1_dev, w2_dev, b2_dev, feat_dev);
+    if (scale_dev)
+        hipLaunchKernelGGL((lidar_features_kernel<true, true>), dim3(blocks), dim3(64 * kWavesPerBlock), lds,
+                           static_cast<hipStream_t>(stream), obs_dev, obs_head_dev, rows_dev, n_robots, w1_dev, b1_dev, w2_dev, b2_dev, feat_dev,
+                           scale_dev);
+    else if (raw_scans)
+        hipLaunchKernelGGL((lidar_features_kernel<true, false>), dim3(blocks), dim3(64 * kWavesPerBlock), lds,
+                           static_cast<hipStream_t>(stream), obs_dev, obs_head_dev, rows_dev, n_robots, w1_dev, b1_dev, w2_dev, b2_dev, feat_dev,
+                           static_cast<const float*>(nullptr));
     else
-        hipLaunchKernelGGL(lidar_features_kernel<false>, dim3(blocks), dim3(64 * kWavesPerBlock), lds,
-                           static_cast<hipStream_t>(stream), obs_dev, obs_head_dev, rows_dev, n_robots, w1_dev, b1_dev, w2_dev, b2_dev, feat_dev);
+        hipLaunchKernelGGL((lidar_features_kernel<false, false>), dim3(blocks), dim3(64 * kWavesPerBlock), lds,
+                           static_cast<hipStream_t>(stream), obs_dev, obs_head_dev, rows_dev, n_robots, w1_dev, b1_dev, w2_dev, b2_dev, feat_dev,
+                           static_cast<const float*>(nullptr));
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return mrca::set_error(MRCA_ERR_HIP, "mrca_lidar_features launch: %s", hipGetErrorString(e));
     return MRCA_OK;
@@ -522,4 +556,15 @@ extern "C" int mrca_lidar_features_rows(const float* frames_dev, const int32_t* 
                                         float* feat_dev, void* stream) {
     if (!rows_dev) return mrca::set_error(MRCA_ERR_INVALID, "mrca_lidar_features_rows: rows_dev is NULL");
     return lidar_features_impl(frames_dev, nullptr, rows_dev, 0, n_samples, frames, beams, w1_dev, b1_dev, w2_dev, b2_dev, feat_dev, stream);
+}
+
+extern "C" int mrca_lidar_features_scaled(const float* obs_dev, const uint8_t* obs_head_dev, const float* scale_dev, int32_t n_robots,
+                                          int32_t frames, int32_t beams, const float* w1_dev, const float* b1_dev, const float* w2_dev,
+                                          const float* b2_dev, float* feat_dev, void* stream) {
+    if (!obs_head_dev) return mrca::set_error(MRCA_ERR_INVALID, "mrca_lidar_features_scaled: obs_head_dev is NULL (raw ring form only)");
+    if (!scale_dev) return mrca::set_error(MRCA_ERR_INVALID, "mrca_lidar_features_scaled: scale_dev is NULL");
+    if (reinterpret_cast<uintptr_t>(scale_dev) % 4)
+        return mrca::set_error(MRCA_ERR_INVALID, "mrca_lidar_features_scaled: scale_dev must be 4-byte aligned");
+    return lidar_features_impl(obs_dev, obs_head_dev, nullptr, 1, n_robots, frames, beams, w1_dev, b1_dev, w2_dev, b2_dev, feat_dev, stream,
+                               scale_dev);
 }

@@ -40,13 +40,23 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kWavesPerSim
     front_end_wave<RAW, false>(lds, obs, head, nullptr, n_robots, w1, b1, w2, b2, feat, blockIdx.x, gridDim.x);
 }
 
+// the safe policy's form (mrca_lidar_features_bf16_scaled): raw ring, robot n's ranges times scale[n] before rounding point 1
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kWavesPerSimd))) void lidar_features_bf16_scaled_kernel(
+    const float* __restrict__ obs, const uint8_t* __restrict__ head, const float* __restrict__ scale, int n_robots,
+    const float* __restrict__ w1, const float* __restrict__ b1, const float* __restrict__ w2, const float* __restrict__ b2,
+    uint16_t* __restrict__ feat) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    front_end_wave<true, false, true>(lds, obs, head, nullptr, n_robots, w1, b1, w2, b2, feat, blockIdx.x, gridDim.x, scale);
+}
+
 static DeviceInfo g_dev[64];
 
 }  // namespace mrca_policy_bf16
 
-extern "C" int mrca_lidar_features_bf16(const float* obs_dev, const uint8_t* obs_head_dev, int32_t raw_scans, int32_t n_robots,
-                                        int32_t frames, int32_t beams, const float* w1_dev, const float* b1_dev,
-                                        const float* w2_dev, const float* b2_dev, uint16_t* feat_dev, void* stream) {
+// scale_dev != NULL: the scaled kernel (raw ring form; mrca_lidar_features_bf16_scaled has checked that)
+static int lidar_features_bf16_impl(const float* obs_dev, const uint8_t* obs_head_dev, const float* scale_dev, int32_t raw_scans,
+                                    int32_t n_robots, int32_t frames, int32_t beams, const float* w1_dev, const float* b1_dev,
+                                    const float* w2_dev, const float* b2_dev, uint16_t* feat_dev, void* stream) {
     using namespace mrca_policy_bf16;
     if (!obs_dev || !w1_dev || !b1_dev || !w2_dev || !b2_dev || !feat_dev)
         return mrca::set_error(MRCA_ERR_INVALID, "mrca_lidar_features_bf16: NULL pointer");
@@ -65,7 +75,10 @@ extern "C" int mrca_lidar_features_bf16(const float* obs_dev, const uint8_t* obs
     int pairs = cus * 4 * kWavesPerSimd / 2;
     if (pairs > n_robots) pairs = n_robots;
     const size_t lds = kWaveBytes;
-    if (raw_scans)
+    if (scale_dev)
+        hipLaunchKernelGGL(lidar_features_bf16_scaled_kernel, dim3(2 * pairs), dim3(64), lds, static_cast<hipStream_t>(stream),
+                           obs_dev, obs_head_dev, scale_dev, n_robots, w1_dev, b1_dev, w2_dev, b2_dev, feat_dev);
+    else if (raw_scans)
         hipLaunchKernelGGL(lidar_features_bf16_kernel<true>, dim3(2 * pairs), dim3(64), lds, static_cast<hipStream_t>(stream),
                            obs_dev, obs_head_dev, n_robots, w1_dev, b1_dev, w2_dev, b2_dev, feat_dev);
     else
@@ -74,4 +87,24 @@ extern "C" int mrca_lidar_features_bf16(const float* obs_dev, const uint8_t* obs
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return mrca::set_error(MRCA_ERR_HIP, "mrca_lidar_features_bf16 launch: %s", hipGetErrorString(e));
     return MRCA_OK;
+}
+
+extern "C" int mrca_lidar_features_bf16(const float* obs_dev, const uint8_t* obs_head_dev, int32_t raw_scans, int32_t n_robots,
+                                        int32_t frames, int32_t beams, const float* w1_dev, const float* b1_dev,
+                                        const float* w2_dev, const float* b2_dev, uint16_t* feat_dev, void* stream) {
+    return lidar_features_bf16_impl(obs_dev, obs_head_dev, nullptr, raw_scans, n_robots, frames, beams, w1_dev, b1_dev, w2_dev, b2_dev,
+                                    feat_dev, stream);
+}
+
+extern "C" int mrca_lidar_features_bf16_scaled(const float* obs_dev, const uint8_t* obs_head_dev, const float* scale_dev,
+                                               int32_t n_robots, int32_t frames, int32_t beams, const float* w1_dev,
+                                               const float* b1_dev, const float* w2_dev, const float* b2_dev, uint16_t* feat_dev,
+                                               void* stream) {
+    if (!obs_head_dev)
+        return mrca::set_error(MRCA_ERR_INVALID, "mrca_lidar_features_bf16_scaled: obs_head_dev is NULL (raw ring form only)");
+    if (!scale_dev) return mrca::set_error(MRCA_ERR_INVALID, "mrca_lidar_features_bf16_scaled: scale_dev is NULL");
+    if (reinterpret_cast<uintptr_t>(scale_dev) % 4)
+        return mrca::set_error(MRCA_ERR_INVALID, "mrca_lidar_features_bf16_scaled: scale_dev must be 4-byte aligned");
+    return lidar_features_bf16_impl(obs_dev, obs_head_dev, scale_dev, 1, n_robots, frames, beams, w1_dev, b1_dev, w2_dev, b2_dev,
+                                    feat_dev, stream);
 }

@@ -71,6 +71,15 @@ __device__ __forceinline__ float obs_value(float v) {
     return RAW ? norm_scan(fabsf(v)) : v;      // |x|: as mrca_policy.hip (ring rows of ABI 4-5 carried a flag in the sign bit)
 }
 
+// the safe policy's scan (mrca_lidar_features_bf16_scaled) exactly as mrca_policy.hip's scale_range: a return at r is seen at
+// r s, a beam that returned nothing (6) stays "nothing"; one separately rounded fp32 multiply IN FRONT of rounding point 1
+__device__ __forceinline__ float scale_range(float x, float s) { return x < 6.0f ? x * s : x; }
+template <bool RAW, bool SCALED>
+__device__ __forceinline__ float obs_value_scaled(float v, float s) {
+    static_assert(RAW || !SCALED, "only raw ranges can be rescaled");
+    return SCALED ? norm_scan(scale_range(fabsf(v), s)) : obs_value<RAW>(v);
+}
+
 // The tower's weights as bf16 fragments (rounding point 2), staged coalesced through LDS as fp32 rows of odd pitch: the image
 // holds W2L / W1L (mrca_policy_bf16_layout.h) when this returns.  wa1: conv1's A fragments; wb2: conv2's B fragments of the
 // forward (w2[col][ci][tap], k = ci).
@@ -125,8 +134,9 @@ __device__ __forceinline__ void zero_h_paddings(unsigned char* lds, int lane) {
 }
 
 // the scan -> X (rounding point 1); X[0] = x[.][-1] = 0.  (X overlaps the previous robot's H rows, all read.)
-template <bool RAW>
-__device__ __forceinline__ void stage_scan(unsigned char* lds, const float4 (&sx)[6], int lane) {
+// SCALED: every range of the three frames times `sc`, the robot's factor (else `sc` is not read)
+template <bool RAW, bool SCALED = false>
+__device__ __forceinline__ void stage_scan(unsigned char* lds, const float4 (&sx)[6], int lane, float sc = 1.0f) {
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
         const int m = 64 * h + lane;
@@ -136,9 +146,9 @@ __device__ __forceinline__ void stage_scan(unsigned char* lds, const float4 (&sx
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             bf16x4 v;
-            v[0] = (__bf16)obs_value<RAW>(a[e]);
-            v[1] = (__bf16)obs_value<RAW>(b[e]);
-            v[2] = (__bf16)obs_value<RAW>(c[e]);
+            v[0] = (__bf16)obs_value_scaled<RAW, SCALED>(a[e], sc);
+            v[1] = (__bf16)obs_value_scaled<RAW, SCALED>(b[e], sc);
+            v[2] = (__bf16)obs_value_scaled<RAW, SCALED>(c[e], sc);
             v[3] = (__bf16)0.0f;
             *reinterpret_cast<bf16x4*>(lds + x_stage_off(4 * m + e)) = v;
         }
@@ -182,12 +192,14 @@ __device__ __forceinline__ void conv1_to_h(unsigned char* lds, const bf16x8 (&wa
 
 // One persistent wave of the forward: wave `gwave` of `nwaves` (even: a wave keeps its tower) walks the robots
 // gwave / 2, gwave / 2 + nwaves / 2, ...  TABLE: the scans come through a row table (`rows`; `head` unused), else from
-// a ring / deque tensor (`head`; `rows` unused).
-template <bool RAW, bool TABLE>
+// a ring / deque tensor (`head`; `rows` unused).  SCALED (RAW ring form): robot n's ranges times scale[n]; the factor of the
+// next robot is fetched WITH its frame rows, when its scan is requested.
+template <bool RAW, bool TABLE, bool SCALED = false>
 __device__ __forceinline__ void front_end_wave(unsigned char* lds, const float* __restrict__ obs, const uint8_t* __restrict__ head,
                                                const int32_t* __restrict__ rows, int n_robots, const float* __restrict__ w1,
                                                const float* __restrict__ b1, const float* __restrict__ w2,
-                                               const float* __restrict__ b2, uint16_t* __restrict__ feat, int gwave, int nwaves) {
+                                               const float* __restrict__ b2, uint16_t* __restrict__ feat, int gwave, int nwaves,
+                                               const float* __restrict__ scale = nullptr) {
     const int lane = threadIdx.x;
     const int tower = gwave & 1;
     const int col = lane & 31, hl = lane >> 5;
@@ -215,10 +227,13 @@ __device__ __forceinline__ void front_end_wave(unsigned char* lds, const float* 
     float4 sx[6];
     if (TABLE) request_scan_rows(sx, obs, rows, n, lane);
     else request_scan(sx, obs, head, n, lane);
+    float sc = 1.0f;                 // the factor of the robot whose scan sits in sx
+    if (SCALED) sc = scale[n];
 
     for (; n < n_robots; n += stride) {
-        stage_scan<RAW>(lds, sx, lane);
+        stage_scan<RAW, SCALED>(lds, sx, lane, sc);
         if (n + stride < n_robots) {
+            if (SCALED) sc = scale[n + stride];      // (this robot's scan is staged: sc is free; issued beside the head's load)
             if (TABLE) request_scan_rows(sx, obs, rows, n + stride, lane);
             else request_scan(sx, obs, head, n + stride, lane);
         }

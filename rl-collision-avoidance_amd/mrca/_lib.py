@@ -33,11 +33,13 @@ EXPORTS = ["mrca_abi_version", "mrca_last_error", "mrca_arena_bytes", "mrca_crea
            "mrca_relu_cat_backward", "mrca_policy_heads_backward_bias", "mrca_relu_cat_backward_bias_scratch",
            "mrca_relu_cat_backward_bias", "mrca_render", "mrca_orca_default_params", "mrca_orca_actions", "mrca_orca_actions_any",
            "mrca_dwa_default_params", "mrca_dwa_actions", "mrca_scan_noise_default_params", "mrca_scan_noise",
-           "mrca_hybrid_default_params", "mrca_hybrid_actions"]
+           "mrca_hybrid_default_params", "mrca_hybrid_actions",
+           "mrca_safe_policy_default_params", "mrca_hybrid_plan", "mrca_hybrid_commit", "mrca_lidar_features_scaled"]
 # declared in include/mrca_env.h like the names above, listed apart: tests/test_abi.py's header scan reads names of letters
 # and underscores only (tests/test_policy_bf16_host.py checks these against the header and the library)
 EXPORTS_WITH_DIGITS = ["mrca_lidar_features_bf16", "mrca_lidar_features_bf16_rows", "mrca_lidar_features_bf16_backward",
-                       "mrca_lidar_features_bf16_backward_rows", "mrca_lidar_features_bf16_backward_scratch"]
+                       "mrca_lidar_features_bf16_backward_rows", "mrca_lidar_features_bf16_backward_scratch",
+                       "mrca_lidar_features_bf16_scaled"]
 
 
 class RolloutRows(C.Structure):
@@ -72,6 +74,11 @@ class HybridParamsStruct(C.Structure):
     """include/mrca_env.h: mrca_hybrid_params"""
     _fields_ = [(k, C.c_float) for k in ("risk_dist", "stop_dist", "safe_scale", "corridor", "look", "front_cos", "v_pid", "k_omega",
                                          "max_speed")]
+
+
+class SafePolicyParamsStruct(C.Structure):
+    """include/mrca_env.h: mrca_safe_policy_params"""
+    _fields_ = [(k, C.c_float) for k in ("scan_scale", "v_cap")]
 
 
 class MrcaConfig(C.Structure):
@@ -176,6 +183,11 @@ def load(path=None):
     lib.mrca_hybrid_default_params.argtypes = [C.POINTER(HybridParamsStruct)]
     lib.mrca_hybrid_actions.argtypes = [C.c_void_p, C.POINTER(HybridParamsStruct), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_void_p]
+    lib.mrca_safe_policy_default_params.argtypes = [C.POINTER(SafePolicyParamsStruct)]
+    lib.mrca_hybrid_plan.argtypes = [C.c_void_p, C.POINTER(HybridParamsStruct), C.POINTER(SafePolicyParamsStruct)] + [C.c_void_p] * 6
+    lib.mrca_hybrid_commit.argtypes = [C.c_int32, C.POINTER(SafePolicyParamsStruct)] + [C.c_void_p] * 6
+    lib.mrca_lidar_features_scaled.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 6
+    lib.mrca_lidar_features_bf16_scaled.argtypes = lib.mrca_lidar_features_scaled.argtypes
     lib.mrca_enable_timing.argtypes = [C.c_void_p, C.c_int32]
     if hasattr(lib, "mrca_set_debug_flags"):      # profiling build only
         lib.mrca_set_debug_flags.argtypes = [C.c_void_p, C.c_int32]

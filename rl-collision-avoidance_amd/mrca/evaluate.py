@@ -132,6 +132,44 @@ def hybrid_policy_fn(env, other, params=None):
     return fn
 
 
+def safe_policy_fn(policy, env, params=None, safe=None, fused_bf16=False, skip_first=0):
+    """Hybrid control in the paper's form around the checkpoint ``policy`` (fused inference on the env's ring of raw scans):
+    per tick ``env.hybrid_plan`` -> ONE forward in which the robots of mode 2 see their scan through the plan's scale ->
+    ``env.hybrid_commit``.  ``skip_first = K``: robots with local index < K belong to another controller (--orca-first,
+    --dwa-first): they are masked out of the plan and the commit, so they stay in mode 0 with scale 1.  ``fn.mode_shares()`` as
+    ``hybrid_policy_fn``'s (the planned robots' live robot-ticks; counted on the device, read when that is called)."""
+    from .hybrid import MODE_NAMES
+    codes = torch.tensor(list(MODE_NAMES), dtype=torch.int32, device=env.device)
+    counts = torch.zeros(len(MODE_NAMES), dtype=torch.int64, device=env.device)
+    mode = torch.zeros(env.N, dtype=torch.int32, device=env.device)
+    scale = torch.ones(env.N, dtype=torch.float32, device=env.device)
+    pid = torch.zeros((env.N, 2), dtype=torch.float32, device=env.device)
+    mask = planned = None
+    if skip_first:
+        planned = torch.arange(env.N, device=env.device) % env.R >= int(skip_first)
+        mask = planned.to(torch.uint8).contiguous()
+
+    def fn(obs, local_goal, speed):
+        env.hybrid_plan(params, safe, mask=mask, mode=mode, scale=scale, pid=pid)
+        ring, head = ppo.policy_input(env, True)
+        _mean, scaled = ppo.generate_action_no_sampling(policy, ring, local_goal, speed, ACTION_BOUND, fused=True, obs_head=head,
+                                                        fused_bf16=fused_bf16, scan_scale=scale)
+        a = env.hybrid_commit(scaled.float().contiguous(), mode, pid, safe, mask=mask)
+        live = env.first_result == 0
+        if planned is not None:
+            live = live & planned
+        counts.add_(((mode.unsqueeze(1) == codes) & live.unsqueeze(1)).sum(dim=0))
+        return a
+    fn.wants_obs = False
+
+    def mode_shares():
+        c = counts.tolist()
+        total = sum(c)
+        return {name: (n / total if total else None) for name, n in zip(MODE_NAMES.values(), c)}
+    fn.mode_shares = mode_shares
+    return fn
+
+
 def perturbed_start(env, jitter_xy, jitter_th, seed):
     """Start poses of a circle world with every robot moved off its table pose by U(-jitter_xy, jitter_xy) metres in x
     and y and U(-jitter_th, jitter_th) radians of heading -- drawn from a Philox generator seeded with ``seed``, so that
@@ -274,6 +312,13 @@ def main():
                                                           "of live robot-ticks per mode)")
     ap.add_argument("--hybrid-param", action="append", default=[], metavar="NAME=VALUE",
                     help="a field of mrca_hybrid_params, e.g. risk_dist=0.8 (repeatable)")
+    ap.add_argument("--hybrid-safe", action="store_true",
+                    help="hybrid control in the paper's form (mrca_hybrid_plan, mrca_hybrid_commit): the robots of mode 2 are driven "
+                         "by the network on a rescaled scan, in the same forward as everybody else's, v capped; needs --policy P "
+                         "--fused (or --fused-bf16); --hybrid-param is taken for the classification; the result line gains "
+                         "hybrid_safe_params, hybrid_params and hybrid_modes")
+    ap.add_argument("--hybrid-safe-param", action="append", default=[], metavar="NAME=VALUE",
+                    help="a field of mrca_safe_policy_params, e.g. scan_scale=0.7 (repeatable)")
     ap.add_argument("--lidar-noise", default=None, metavar="const=M,prop=P,dropout=Q[,quantum=M]",
                     help="the lidar noise model (mrca_scan_noise) behind every ray cast: range noise of const + prop * range metres "
                          "(an Irwin-Hall deviate of unit variance), beams lost with probability dropout, a read-out step of quantum "
@@ -289,6 +334,18 @@ def main():
     if a.fused_bf16:
         a.fused = True
     from .vec_env import VecStageWorld
+    if a.hybrid_safe_param and not a.hybrid_safe:
+        ap.error("--hybrid-safe-param goes with --hybrid-safe")
+    if a.hybrid_safe:
+        if a.hybrid:
+            ap.error("--hybrid-safe is hybrid control in the paper's form, --hybrid the command scaling: choose one")
+        if a.orca or a.dwa:
+            ap.error("--hybrid-safe rescales the scan a checkpoint sees: not with --orca / --dwa (use --orca-first / --dwa-first "
+                     "for mixed groups)")
+        if not a.policy:
+            ap.error("--hybrid-safe needs --policy P: the stand-in reads no rescaled scan")
+        if not a.fused:
+            ap.error("--hybrid-safe needs --fused (or --fused-bf16): the scan is rescaled while the fused front end stages it")
     if a.one_circle is None and a.spacing is not None:
         ap.error("--spacing goes with --one-circle")
     if a.one_circle is not None:
@@ -316,6 +373,16 @@ def main():
         pol = CNNPolicy(3, 2).to(env.device)
         pol.load_state_dict(torch.load(a.policy, map_location=env.device))
         fn, name = cnn_policy_fn(pol, fused=a.fused, env=env, fused_bf16=a.fused_bf16), a.policy
+        if a.hybrid_safe:
+            from .hybrid import HybridParams, SafePolicyParams
+            try:
+                hybrid_params = HybridParams.from_assignments(a.hybrid_param)
+                safe_params = SafePolicyParams.from_assignments(a.hybrid_safe_param)
+            except ValueError as e:
+                ap.error(str(e))
+            fn = safe_policy_fn(pol, env, hybrid_params, safe_params, fused_bf16=a.fused_bf16,
+                                skip_first=max(a.orca_first or 0, a.dwa_first or 0))
+            safe_fn, name = fn, f"hybrid control in the paper's form (mrca_hybrid_plan, mrca_hybrid_commit) around {name}"
     else:
         fn, name = staggered_roundabout_policy(env.N), "staggered-roundabout stand-in (no checkpoint given)"
     orca_call = "mrca_orca_actions_any" if env.R > 64 else "mrca_orca_actions"
@@ -336,8 +403,8 @@ def main():
         else:
             fn = dwa_policy_fn(env, dwa_params, first=a.dwa_first, other=fn, other_name="orca" if a.orca else "policy")
             name = f"DWA for local index < {a.dwa_first}, else {name}"
-    if a.hybrid_param and not a.hybrid:
-        ap.error("--hybrid-param goes with --hybrid")
+    if a.hybrid_param and not (a.hybrid or a.hybrid_safe):
+        ap.error("--hybrid-param goes with --hybrid or --hybrid-safe")
     if a.hybrid:
         from .hybrid import HybridParams
         try:
@@ -366,6 +433,11 @@ def main():
         import dataclasses
         out["hybrid_params"] = dataclasses.asdict(hybrid_params)
         out["hybrid_modes"] = fn.mode_shares()
+    if a.hybrid_safe:
+        import dataclasses
+        out["hybrid_safe_params"] = dataclasses.asdict(safe_params)
+        out["hybrid_params"] = dataclasses.asdict(hybrid_params)
+        out["hybrid_modes"] = safe_fn.mode_shares()
     out["lidar_noise"] = None if noise is None else noise.as_dict()
     out["robots_per_circle"], out["radius_m"] = a.robots, a.radius
     if a.one_circle is not None:

@@ -48,3 +48,39 @@ class HybridParams:
                 raise ValueError(f"--hybrid-param {it!r}: expected name=value with name in {_FIELDS}")
             kw[k] = float(v)
         return cls(**kw)
+
+
+_SAFE_FIELDS = [name for name, _t in _lib.SafePolicyParamsStruct._fields_]
+
+
+def _library_safe_defaults():
+    st = _lib.SafePolicyParamsStruct()
+    _lib.check(_lib.load().mrca_safe_policy_default_params(C.byref(st)), "mrca_safe_policy_default_params")
+    return {k: getattr(st, k) for k in _SAFE_FIELDS}
+
+
+@dataclasses.dataclass
+class SafePolicyParams:
+    """Mirror of mrca_safe_policy_params (hybrid control in the paper's form: mrca_hybrid_plan, mrca_hybrid_commit); a field
+    left ``None`` takes the library's default."""
+    scan_scale: float = None            # what a return's range is multiplied by in front of the network in mode 2, in (0, 1]
+    v_cap: float = None                 # the most v that mode 2 lets through, in (0, 1]
+
+    def __post_init__(self):
+        for k, v in _library_safe_defaults().items():
+            if getattr(self, k) is None:
+                setattr(self, k, v)
+
+    def struct(self):
+        return _lib.SafePolicyParamsStruct(**{k: getattr(self, k) for k in _SAFE_FIELDS})
+
+    @classmethod
+    def from_assignments(cls, items):
+        """``["scan_scale=0.7"]`` (the evaluator's --hybrid-safe-param) -> SafePolicyParams."""
+        kw = {}
+        for it in items or ():
+            k, _eq, v = it.partition("=")
+            if k not in _SAFE_FIELDS or not _eq:
+                raise ValueError(f"--hybrid-safe-param {it!r}: expected name=value with name in {_SAFE_FIELDS}")
+            kw[k] = float(v)
+        return cls(**kw)

@@ -198,20 +198,21 @@ class CNNPolicy(nn.Module):
                 self._rc_bf16 = rc["fc1_w"].to(torch.bfloat16)
         return rc, self._rc_bf16
 
-    def _fc1_bf16(self, x, rc, fc1_w_bf16, head):
+    def _fc1_bf16(self, x, rc, fc1_w_bf16, head, scan_scale=None):
         """The bf16 front end (csrc/mrca_policy_bf16.hip) and fc1 as a bf16 x bf16 batched GEMM with fp32 accumulation and
         an fp32 result, before bias and ReLU -> f32[2, N, 256]"""
         from . import policy_ops
-        feat = policy_ops.lidar_features_bf16(x, rc["w1"], rc["b1"], rc["w2"], rc["b2"], head=head)    # bf16 [2, N, 4096]
+        feat = policy_ops.lidar_features_bf16(x, rc["w1"], rc["b1"], rc["w2"], rc["b2"], head=head, scale=scan_scale)    # bf16 [2, N, 4096]
         return torch.bmm(feat, fc1_w_bf16, out_dtype=torch.float32)
 
-    def mean_value_fused(self, x, goal, speed, head=None, bf16=False):
+    def mean_value_fused(self, x, goal, speed, head=None, bf16=False, scan_scale=None):
         """mean_value for the rollout: the conv front end of BOTH towers in one HIP kernel (csrc/mrca_policy.hip,
         fp32 MFMA), fc1 / fc2 of both towers as batched fp32 GEMMs.  fp32 throughout; differs from mean_value by
         summation order only (tests/test_gpu_policy_ops.py: 1e-5).  No autograd.  ``head``: ``x`` is the env's frame
         ring and head[n] the slot of robot n's newest frame (VecStageWorld.policy_obs()).  ``bf16=True``: the opt-in bf16
         inference -- the front end on bf16 MFMAs (csrc/mrca_policy_bf16.hip) and fc1 as a bf16 GEMM with fp32
-        accumulation; fc2 and the heads stay fp32."""
+        accumulation; fc2 and the heads stay fp32.  ``scan_scale`` f32[N]: the safe policy's per-robot scan scale (what
+        ``VecStageWorld.hybrid_plan`` returns; needs the ring of raw scans as ``head``), see ``policy_ops.lidar_features``."""
         from . import policy_ops
         if bf16:
             rc, w_bf16 = self._rollout_cache_bf16()
@@ -219,9 +220,9 @@ class CNNPolicy(nn.Module):
             rc = self._rollout_cache()
         with torch.no_grad():
             if bf16:
-                h = torch.relu(self._fc1_bf16(x, rc, w_bf16, head) + rc["fc1_b"])                 # [2, N, 256]
+                h = torch.relu(self._fc1_bf16(x, rc, w_bf16, head, scan_scale) + rc["fc1_b"])     # [2, N, 256]
             else:
-                feat = policy_ops.lidar_features(x, rc["w1"], rc["b1"], rc["w2"], rc["b2"], head=head)   # [2, N, 4096]
+                feat = policy_ops.lidar_features(x, rc["w1"], rc["b1"], rc["w2"], rc["b2"], head=head, scale=scan_scale)   # [2, N, 4096]
                 h = torch.relu(torch.baddbmm(rc["fc1_b"], feat, rc["fc1_w"]))                      # [2, N, 256]
             gs = torch.cat((goal, speed), dim=-1).unsqueeze(0).expand(2, -1, -1)
             h = torch.relu(torch.baddbmm(rc["fc2_b"], torch.cat((h, gs), dim=-1), rc["fc2_w"]))   # [2, N, 128]
@@ -230,7 +231,7 @@ class CNNPolicy(nn.Module):
             v = self.critic(h[1])
         return mean, v
 
-    def act_fused(self, x, goal, speed, noise, lo, hi, head=None, bf16=False):
+    def act_fused(self, x, goal, speed, noise, lo, hi, head=None, bf16=False, scan_scale=None):
         """generate_action for the rollout in three launches: the conv front end of both towers (csrc/mrca_policy.hip),
         fc1 of both towers as one batched fp32 GEMM (a plain bmm: a baddbmm first copies the broadcast bias into its
         output, 8 MB and 7 us per tick at 4096 robots -- the tail adds the bias while it stages h1), and everything
@@ -239,7 +240,8 @@ class CNNPolicy(nn.Module):
         summation order only (tests/test_gpu_policy_ops.py: 1e-5 / 1e-4 against the stock layers; tests/test_gpu_rollout_inference.py:
         against a float64 model of the chain, no further from it than 8 x the stock layers are).  ``bf16=True``: the opt-in bf16 inference -- the front end on
         bf16 MFMAs (csrc/mrca_policy_bf16.hip, bf16 features) and fc1 as a bf16 x bf16 batched GEMM with fp32 accumulation
-        and result; the tail is the same fp32 kernel (tests/test_gpu_policy_bf16.py)."""
+        and result; the tail is the same fp32 kernel (tests/test_gpu_policy_bf16.py).  ``scan_scale`` f32[N]: the safe
+        policy's per-robot scan scale, as ``mean_value_fused`` takes it (tests/test_gpu_safe_policy.py)."""
         from . import policy_ops
         if bf16:
             rc, w_bf16 = self._rollout_cache_bf16()
@@ -247,9 +249,9 @@ class CNNPolicy(nn.Module):
             rc = self._rollout_cache()
         with torch.no_grad():
             if bf16:
-                h1 = self._fc1_bf16(x, rc, w_bf16, head)                                # [2, N, 256] fp32, before bias and ReLU
+                h1 = self._fc1_bf16(x, rc, w_bf16, head, scan_scale)                    # [2, N, 256] fp32, before bias and ReLU
             else:
-                feat = policy_ops.lidar_features(x, rc["w1"], rc["b1"], rc["w2"], rc["b2"], head=head)   # [2, N, 4096]
+                feat = policy_ops.lidar_features(x, rc["w1"], rc["b1"], rc["w2"], rc["b2"], head=head, scale=scan_scale)   # [2, N, 4096]
                 h1 = torch.bmm(feat, rc["fc1_w"])                                        # [2, N, 256], before bias and ReLU
             return policy_ops.policy_tail(h1, goal.contiguous(), speed.contiguous(), rc["fc2_w"], rc["fc2_b"], rc["head_w"],
                                           rc["head_b"], rc["critic_w"], rc["critic_b"], rc["logstd"], noise, lo, hi,

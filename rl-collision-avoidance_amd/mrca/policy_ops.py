@@ -143,9 +143,10 @@ _FRONT_END = {False: (torch.float32, "lidar_features"), True: (torch.bfloat16, "
 _CONV_SHAPES = ((2, 32, 3, 5), (2, 32), (2, 32, 32, 3), (2, 32))        # w1, b1, w2, b2, tower-major
 
 
-def _front_end_forward(who, bf16, obs, w1, b1, w2, b2, out, head):
+def _front_end_forward(who, bf16, obs, w1, b1, w2, b2, out, head, scale=None):
     """The forward of the conv front end at either precision, for a stack tensor (with or without ring heads) or a
-    ``FrameTable`` -> features [2, N, 4096].  The weights are fp32 either way."""
+    ``FrameTable`` -> features [2, N, 4096].  The weights are fp32 either way.  ``scale`` f32[N]: the per-robot scan scale of
+    the safe policy (mrca_<stem>_scaled; raw ring form only)."""
     lib = _lib.load()
     dtype, stem = _FRONT_END[bf16]
     _check(who, torch.float32, *zip((w1, b1, w2, b2), _CONV_SHAPES))
@@ -154,6 +155,8 @@ def _front_end_forward(who, bf16, obs, w1, b1, w2, b2, out, head):
             raise ValueError(f"{who}: a FrameTable is in deque order already (no head)")
         if not obs.is_cuda:
             raise ValueError(f"{who}: the FrameTable must live on the GPU")
+        if scale is not None:
+            raise ValueError(f"{who}: scale needs the ring of RAW scans, head=RingHead(slots, raw=True), not a FrameTable")
         entry, source = f"mrca_{stem}_rows", (obs.frames.data_ptr(), obs.rows.data_ptr())
     else:
         head, raw = unwrap_head(head)
@@ -163,6 +166,12 @@ def _front_end_forward(who, bf16, obs, w1, b1, w2, b2, out, head):
         if head is not None:        # one entry per robot
             _check(who, torch.uint8, (head, obs.shape[0]))
         entry, source = f"mrca_{stem}", (obs.data_ptr(), None if head is None else head.data_ptr(), int(raw))
+        if scale is not None:
+            if head is None or not raw:
+                raise ValueError(f"{who}: scale needs the ring of RAW scans, head=RingHead(slots, raw=True) -- normalised "
+                                 "observations cannot be rescaled")
+            _check(who, torch.float32, (scale, (obs.shape[0],)), device=obs.device)
+            entry, source = f"mrca_{stem}_scaled", (obs.data_ptr(), head.data_ptr(), scale.data_ptr())
     N = obs.shape[0]
     if out is None:
         out = torch.empty(2, N, 4096, dtype=dtype, device=obs.device)
@@ -176,24 +185,28 @@ def _front_end_forward(who, bf16, obs, w1, b1, w2, b2, out, head):
     return out
 
 
-def lidar_features(obs, w1, b1, w2, b2, out=None, head=None):
+def lidar_features(obs, w1, b1, w2, b2, out=None, head=None, scale=None):
     """relu(conv2(relu(conv1(obs)))) of the actor and the critic tower in one launch.
     obs f32[N,3,512]; w1 f32[2,32,3,5], b1 f32[2,32], w2 f32[2,32,32,3], b2 f32[2,32] (tower-major: actor, critic)
     -> f32[2,N,4096], rows in the flatten order of [32,128].
     ``head`` u8[N] or a ``RingHead``: ``obs`` is a frame RING (VecStageWorld.policy_obs()) and head[n] the slot of
     robot n's newest frame; the kernel reads the frames in deque order while staging -- and, for a ring of RAW scans,
-    forms the observation x / 6 - 0.5 on the way.  None: ``obs`` is in deque order."""
-    return _front_end_forward("lidar_features", False, obs, w1, b1, w2, b2, out, head)
+    forms the observation x / 6 - 0.5 on the way.  None: ``obs`` is in deque order.
+    ``scale`` f32[N] (needs ``head=RingHead(..., raw=True)``): the safe policy's scan (mrca_lidar_features_scaled) -- every
+    return of robot n, in all three frames, is seen at ``scale[n]`` times its range (a beam that returned nothing stays
+    nothing); ones give the bits of ``scale=None``, which calls the unscaled entry point."""
+    return _front_end_forward("lidar_features", False, obs, w1, b1, w2, b2, out, head, scale)
 
 
-def lidar_features_bf16(obs, w1, b1, w2, b2, out=None, head=None):
+def lidar_features_bf16(obs, w1, b1, w2, b2, out=None, head=None, scale=None):
     """lidar_features on bf16 MFMAs (csrc/mrca_policy_bf16.hip): same arguments (fp32 weights, tower-major), returns
     bf16[2,N,4096].  Rounding points (include/mrca_env.h: mrca_lidar_features_bf16): the observation, w1, w2, h1 and the
     output are rounded to bf16 (nearest even); the biases are added in fp32.  Rollout inference only: a FrameTable (the
-    update's row-table form) is refused."""
+    update's row-table form) is refused.  ``scale``: as ``lidar_features`` (the multiply happens in fp32, in front of the
+    observation's rounding)."""
     if isinstance(obs, FrameTable):
         raise ValueError("lidar_features_bf16: inference only -- a FrameTable (the update path) is not supported")
-    return _front_end_forward("lidar_features_bf16", True, obs, w1, b1, w2, b2, out, head)
+    return _front_end_forward("lidar_features_bf16", True, obs, w1, b1, w2, b2, out, head, scale)
 
 
 def lidar_features_bf16_rows(table, w1, b1, w2, b2, out=None):

@@ -79,15 +79,22 @@ def policy_input(env, fused):
     return env.obs, None
 
 
-def generate_action_no_sampling(policy, obs, goal, speed, action_bound, fused=False, obs_head=None, fused_bf16=False):
-    """model/ppo.py:84-107: deterministic mean action (circle_test.py:58-59).  ``fused_bf16``: as generate_action."""
+def generate_action_no_sampling(policy, obs, goal, speed, action_bound, fused=False, obs_head=None, fused_bf16=False,
+                                scan_scale=None):
+    """model/ppo.py:84-107: deterministic mean action (circle_test.py:58-59).  ``fused_bf16``: as generate_action.
+    ``scan_scale`` f32[N] (fused paths on the ring of raw scans only): the safe policy's per-robot scan scale
+    (``VecStageWorld.hybrid_plan``); None is the path as it was."""
     check_policy_path(fused, fused_bf16, obs_head)
+    if scan_scale is not None and not fused:
+        raise ValueError("scan_scale needs the fused rollout inference (fused=True): the scan is rescaled while it is staged")
     if fused and hasattr(policy, "act_fused"):
         lo, hi = _bounds(action_bound, goal.device, torch.float32)
-        _v, _a, _lp, scaled, mean = policy.act_fused(obs, goal, speed, None, lo, hi, head=obs_head, bf16=fused_bf16)
+        kw = {} if scan_scale is None else {"scan_scale": scan_scale}
+        _v, _a, _lp, scaled, mean = policy.act_fused(obs, goal, speed, None, lo, hi, head=obs_head, bf16=fused_bf16, **kw)
         return mean, scaled
     with torch.no_grad():
-        mean, _v = policy.mean_value_fused(obs, goal, speed, head=obs_head, bf16=fused_bf16) if fused else \
+        kw = {} if scan_scale is None else {"scan_scale": scan_scale}
+        mean, _v = policy.mean_value_fused(obs, goal, speed, head=obs_head, bf16=fused_bf16, **kw) if fused else \
             policy.mean_value(obs, goal, speed)
         lo, hi = _bounds(action_bound, mean.device, mean.dtype)
         scaled = torch.minimum(torch.maximum(mean, lo), hi)

@@ -314,6 +314,43 @@ class VecStageWorld:
                                                 self._stream()), "mrca_hybrid_actions")
         return out
 
+    def hybrid_plan(self, params=None, safe=None, mask=None, mode=None, scale=None, pid=None, clear=None):
+        """The first half of hybrid control in the paper's form (mrca_hybrid_plan): per robot, from its newest scan and local
+        goal alone -- no command is read -- the mode ``hybrid_actions`` would report (int32[N]: 0, 1, 2, -2), the factor its
+        scan is to be seen through (float32[N]: ``safe.scan_scale`` in mode 2, else 1) and the PID command (float32[N,2]: mode
+        1's; zeros elsewhere).  -> ``(mode, scale, pid)``.  A tick is ``plan`` -> one forward with ``scan_scale=scale``
+        (``CNNPolicy.act_fused``) -> ``hybrid_commit`` -> ``step``.  One launch on the current stream, nothing synchronises,
+        nothing of the env is written.  ``params``: a ``hybrid.HybridParams``, ``safe``: a ``hybrid.SafePolicyParams`` (default:
+        the library's); ``mask``: a uint8[N] tensor, rows with 0 keep what the outputs hold (fresh outputs start as mode 0,
+        scale 1, pid 0); ``clear``: a float32[N,3] tensor that takes (d_min, d_front, d_block)."""
+        if mode is None:
+            mode = torch.zeros(self.N, dtype=torch.int32, device=self.device)
+        if scale is None:
+            scale = torch.ones(self.N, dtype=torch.float32, device=self.device)
+        if pid is None:
+            pid = torch.zeros((self.N, 2), dtype=torch.float32, device=self.device)
+        st = None if params is None else params.struct()
+        ss = None if safe is None else safe.struct()
+        _lib.check(self.lib.mrca_hybrid_plan(self._h, None if st is None else C.byref(st), None if ss is None else C.byref(ss),
+                                             self._ptr(mask, torch.uint8, self.N), self._ptr(mode, torch.int32, self.N),
+                                             self._ptr(scale, torch.float32, self.N), self._ptr(pid, torch.float32, 2 * self.N),
+                                             self._ptr(clear, torch.float32, 3 * self.N), self._stream()), "mrca_hybrid_plan")
+        return mode, scale, pid
+
+    def hybrid_commit(self, actions, mode, pid, safe=None, mask=None, out=None):
+        """The second half (mrca_hybrid_commit): ``actions`` (float32[N,2], what the forward with the plan's scan scale gave)
+        kept in mode 0, replaced by ``pid`` in modes 1 and -2, capped in v at ``safe.v_cap`` in mode 2 (omega kept).
+        ``out=None`` works IN PLACE on ``actions`` and returns it; ``mask``: rows with 0 keep what ``out`` holds.  One launch on
+        the current stream."""
+        if out is None:
+            out = actions
+        ss = None if safe is None else safe.struct()
+        _lib.check(self.lib.mrca_hybrid_commit(self.N, None if ss is None else C.byref(ss), self._ptr(mask, torch.uint8, self.N),
+                                               self._ptr(mode, torch.int32, self.N), self._ptr(pid, torch.float32, 2 * self.N),
+                                               self._ptr(actions, torch.float32, 2 * self.N), self._ptr(out, torch.float32, 2 * self.N),
+                                               self._stream()), "mrca_hybrid_commit")
+        return out
+
     def scan_noise(self, params=None, mask=None):
         """The lidar noise model (mrca_scan_noise) applied IN PLACE to the newest scan row of every robot (``mask``: a uint8[N]
         tensor, rows with 0 are not touched): range noise, quantisation and dropout as ``params`` (a ``noise.ScanNoiseParams``;
