@@ -33,7 +33,9 @@
 extern "C" {
 #endif
 
-/* 6, additive: mrca_hybrid_plan, mrca_hybrid_commit, mrca_safe_policy_default_params, mrca_lidar_features_scaled,
+/* 6, additive: mrca_goal_fields, mrca_subgoals, mrca_planner_grid, mrca_planner_default_params (a global planner: integer goal
+ * fields over the map, a subgoal per robot and tick).
+ * 6, additive: mrca_hybrid_plan, mrca_hybrid_commit, mrca_safe_policy_default_params, mrca_lidar_features_scaled,
  * mrca_lidar_features_bf16_scaled (hybrid control in the paper's form: the safe policy is the network on a rescaled scan).
  * 6, additive: mrca_hybrid_actions, mrca_hybrid_default_params (hybrid control behind a policy: PID, policy or safe policy per robot).
  * 6, additive: mrca_scan_noise, mrca_scan_noise_default_params (a lidar noise model applied to the ring in place).
@@ -520,7 +522,76 @@ int mrca_hybrid_commit(int32_t n_robots, const mrca_safe_policy_params* safe_par
                        const float* pid_dev /* f32[N,2] */, const float* policy_dev /* f32[N,2] in */,
                        float* actions_dev /* f32[N,2] out; may be policy_dev itself */, void* stream);
 
-/* Synchronises `stream` and reports (then clears) the env's sticky device-side status word: MRCA_OK, or MRCA_ERR_HIP with
+/* A GLOBAL PLANNER under the local controllers: every controller here steers at MRCA_F_LOCAL_GOAL, the straight line to the
+ * goal, which is enough on the circle and not on a map with walls.  After Fan, Long, Liu, Pan (IJRR 2020, long-range
+ * navigation) the learned policy becomes the LOCAL planner: mrca_goal_fields plans once per goal set, mrca_subgoals gives every
+ * robot a SUBGOAL a little way down the shortest path every tick, in the robot's frame, to be handed to the controller in place
+ * of MRCA_F_LOCAL_GOAL.  The rule is csrc/mrca_planner_device.h (tests/planner_ref.py restates it in NumPy and heapq):
+ *   planning grid  the env's map coarsened by `stride` s: PW = ceil(map_width / s), PH = ceil(map_height / s)
+ *                  (mrca_planner_grid); the map cell of a point is floorf((x - map_x0) / map_cell) as everywhere, the planning
+ *                  cell that divided by s; a point whose map cell lies outside the map is OFF GRID
+ *   blocked        a planning cell is blocked iff an occupied map cell lies within Chebyshev distance `inflate` (map cells) of
+ *                  one of its map cells; cells beyond the map are free
+ *   field          u32[PH][PW] per goal point: 0 at its planning cell (the SEED, blocked or not; it counts as unblocked from
+ *                  there on), 0xFFFFFFFF for every other blocked cell and every cell no path reaches, else the length of the
+ *                  shortest 8-connected path to the seed through unblocked cells, a straight step 5, a diagonal step 7, a
+ *                  diagonal step only between two unblocked cells (no corner is cut).  A goal off grid: all 0xFFFFFFFF.
+ *                  The least solution of D(c) = min D(n) + w: unique, so the words do not depend on the order anything ran in
+ *   walk           from the robot's planning cell, up to `lookahead` times: the allowed step of least D(n) + w, ties to the
+ *                  lowest direction in the order E, NE, N, NW, W, SW, S, SE, taken only if D(n) < D(c); from a 0xFFFFFFFF
+ *                  cell (a robot inside the inflation) every in-grid neighbour with a finite D is a candidate; stops at D = 0
+ *   status_dev     1: the walk reached the seed, the subgoal is the slot's goal point bit for bit;  0: the centre of the cell
+ *                  reached, map_x0 + ((float)i + 0.5f) * (map_cell * (float)s);  -1: no slot (slot < 0 or >= G);  -2: the robot
+ *                  is off grid, or has no candidate at its first step (walled in, or its goal is off grid).  For -1 and -2 the
+ *                  subgoal is MRCA_F_GOAL[n] bit for bit
+ *   local_dev      the subgoal in the robot's frame, by the expression and from the sine and cosine the ray cast uses for
+ *                  MRCA_F_LOCAL_GOAL: wherever the subgoal has the goal's bits, local has MRCA_F_LOCAL_GOAL[n]'s
+ *   dist_dev       (float)D(first cell) * ((map_cell * (float)s) / 5.0f) metres; +inf for 0xFFFFFFFF, off grid and no slot
+ * WHAT THE NUMBERS ARE NOT.  The chamfer 5 / 7 metric OVER-ESTIMATES the Euclidean length of a path by a few percent (up to 8 %
+ * at 26.6 degrees; a pure diagonal is 1 % short), on top of the 8-connected path's own detour.  There is NO line-of-sight
+ * smoothing: the subgoal is a cell centre on the 8-connected path, `lookahead` steps ahead.  One map for all worlds; other
+ * robots are not obstacles of the plan.
+ *
+ * mrca_goal_fields  the PLANNING call: field_dev[g] for goal point goals_dev[g].  One launch initialises the field, then ONE
+ *   launch per round relaxes every (goal, tile of 64 x 64 cells) in LDS from the field as it stands; the host reads a counter
+ *   every four launches and stops when a launch lowered nothing.  No grid-wide barrier, no cooperative launch, no wait on the
+ *   device; every loop has a fixed trip count.  IT SYNCHRONISES `stream` (like mrca_check below) while it looks for convergence,
+ *   returns synchronised, and is NOT capturable: inside a stream capture it is refused (MRCA_ERR_INVALID).  Never more than
+ *   max_rounds launches; max_rounds 0 = T (64 + 252) + 2 for T tiles per goal (derived at plan_round_bound,
+ *   csrc/mrca_planner_device.h; the shipped Stage-2 map takes some tens).  Not converged within that: MRCA_ERR_UNSUPPORTED, the
+ *   message names max_rounds, and every word of the field is then >= the true one.  rounds_out (host, may be NULL) = the launches
+ *   that lowered something.  Reads the env's map only; writes nothing of the env.
+ * mrca_subgoals  the PER-TICK call: asynchronous on `stream`, ONE launch (eight lanes per robot, the params travel as kernel
+ *   arguments), capturable; reads MRCA_F_POSE, MRCA_F_GOAL and the head records as they stand at that point of the stream and
+ *   writes nothing of the env.  Any robots_per_world, both lazy_obs values, exact and raster collision modes.
+ *   params      host; NULL = mrca_planner_default_params: stride 2, inflate 7, lookahead 15, max_rounds 0.  stride must be the
+ *               one the field was planned with (inflate and max_rounds are not read here)
+ *   field_dev   u32[G,PH,PW] as mrca_goal_fields left it;  goals_dev f32[G,2] the same goal points
+ *   slot_dev    i32[N]: which goal point robot n walks to, < 0 or >= G = none;  NULL = n % robots_per_world, needs
+ *               G == robots_per_world
+ *   mask_dev    u8[N] or NULL = all robots; rows whose mask byte is 0 are not touched in any output
+ *   local_dev   f32[N,2] out, 8-byte aligned, not NULL;  subgoal_dev f32[N,2], dist_dev f32[N], status_dev i32[N]: out or NULL
+ * Validated before the first HIP call (MRCA_ERR_INVALID): stride 1..8, inflate 0..64, lookahead 1..256, max_rounds >= 0;
+ * G 1..4096; goals_dev, field_dev and local_dev not NULL; local_dev 8-byte aligned; slot_dev NULL only with
+ * G == robots_per_world; a call before the env's first mrca_reset is refused. */
+typedef struct mrca_planner_params {
+    int32_t stride;      /* map cells per planning cell and axis, 1..8 */
+    int32_t inflate;     /* [map cells] obstacles are grown by this, 0..64 */
+    int32_t lookahead;   /* steps of the walk, 1..256 */
+    int32_t max_rounds;  /* mrca_goal_fields: at most this many relaxation launches; 0 = the derived bound */
+} mrca_planner_params;
+int mrca_planner_default_params(mrca_planner_params* out);
+int mrca_planner_grid(mrca_env* env, const mrca_planner_params* params /* host, NULL = defaults */, int32_t* pw_out, int32_t* ph_out);
+int mrca_goal_fields(mrca_env* env, const mrca_planner_params* params /* host, NULL = defaults */,
+                     const float* goals_dev /* f32[G,2] */, int32_t G, uint32_t* field_dev /* u32[G,PH,PW], caller-owned */,
+                     int32_t* rounds_out /* host, may be NULL */, void* stream);
+int mrca_subgoals(mrca_env* env, const mrca_planner_params* params /* host, NULL = defaults */, const uint32_t* field_dev,
+                  const float* goals_dev /* f32[G,2] */, int32_t G, const int32_t* slot_dev /* i32[N] or NULL */,
+                  const uint8_t* mask_dev /* u8[N] or NULL */, float* local_dev /* f32[N,2] */, float* subgoal_dev /* f32[N,2] or NULL */,
+                  float* dist_dev /* f32[N] or NULL */, int32_t* status_dev /* i32[N] or NULL */, void* stream);
+
+/* (mrca_goal_fields above synchronises its stream too, while it looks for convergence.)
+ * Synchronises `stream` and reports (then clears) the env's sticky device-side status word: MRCA_OK, or MRCA_ERR_HIP with
  * mrca_last_error() saying what went wrong on the device since the last check.  Today one condition: the ordered
  * collision pass of a world with more than 64 robots ran out of its (very long) bounded wait and left a robot
  * undecided.  mrca_step itself never synchronises; call this wherever a host round trip is acceptable (end of an

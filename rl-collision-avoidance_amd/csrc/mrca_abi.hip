@@ -26,6 +26,7 @@
 #include "mrca_noise.h"
 #include "mrca_hybrid.h"
 #include "mrca_safe.h"
+#include "mrca_planner.h"
 #include "mrca_pass_plan.h"
 #include "mrca_render.h"
 #include "mrca_rollout_store.h"
@@ -306,6 +307,7 @@ struct mrca_env {
     mrca::EnvView view;
     DeviceBuffer<uint16_t> octant_rect;     // the octant free-rectangle array (outside the arena: the arena's size is ABI), or none
     DeviceBuffer<mrca::EnvView> view_dev;   // `view` in device memory (outside the arena): what move_kernel / raycast_kernel read
+    DeviceBuffer<uint32_t> plan_counters;   // mrca_goal_fields' per-launch counters, from its first call on (it returns synchronised)
     size_t lds_bytes = 0;
     // timing
     int timing = 0;      // 0 off, n > 0: record events on every n-th step
@@ -1163,6 +1165,125 @@ int mrca_hybrid_commit(int32_t n_robots, const mrca_safe_policy_params* safe_par
     memcpy(&sq, &sp, sizeof sq);
     DeviceGuard guard(mrca::device_of(actions_dev));     // launch where the buffers live
     mrca::launch_hybrid_commit(n_robots, sq, mask_dev, mode_dev, pid_dev, policy_dev, actions_dev, static_cast<hipStream_t>(stream));
+    HIP_TRY(hipGetLastError());
+    return MRCA_OK;
+}
+
+static_assert(sizeof(mrca_planner_params) == sizeof(mrca::PlannerParams) &&
+                  offsetof(mrca_planner_params, max_rounds) == offsetof(mrca::PlannerParams, max_rounds),
+              "mrca_planner_params and mrca::PlannerParams are one layout");
+
+int mrca_planner_default_params(mrca_planner_params* out) {
+    if (!out) return fail(MRCA_ERR_INVALID, "mrca_planner_default_params: out is NULL");
+    out->stride = 2;        // 0.1 m planning cells on the shipped 0.05 m maps
+    out->inflate = 7;       // 0.35 m: the footprint's half diagonal (0.29 m) and a cell of slack
+    out->lookahead = 15;    // 1.5 m down the path
+    out->max_rounds = 0;    // the bound of mrca_planner_device.h (plan_round_bound)
+    return MRCA_OK;
+}
+
+// the table of mrca_planner_params, for `who`: *q = the params to use (NULL: the defaults), MRCA_OK or the failure
+static int check_planner_params(const char* who, const mrca_planner_params* params, mrca::PlannerParams* q) {
+    mrca_planner_params p;
+    if (params) p = *params;
+    else mrca_planner_default_params(&p);
+    if (p.stride < 1 || p.stride > mrca::kPlanMaxStride) return fail(MRCA_ERR_INVALID, "%s: stride %d outside 1..%d", who, p.stride, mrca::kPlanMaxStride);
+    if (p.inflate < 0 || p.inflate > mrca::kPlanMaxInflate)
+        return fail(MRCA_ERR_INVALID, "%s: inflate %d outside 0..%d", who, p.inflate, mrca::kPlanMaxInflate);
+    if (p.lookahead < 1 || p.lookahead > mrca::kPlanMaxLookahead)
+        return fail(MRCA_ERR_INVALID, "%s: lookahead %d outside 1..%d", who, p.lookahead, mrca::kPlanMaxLookahead);
+    if (p.max_rounds < 0) return fail(MRCA_ERR_INVALID, "%s: max_rounds %d is negative", who, p.max_rounds);
+    static_assert(std::is_trivially_copyable<mrca::PlannerParams>::value, "");
+    memcpy(q, &p, sizeof *q);
+    return MRCA_OK;
+}
+
+int mrca_planner_grid(mrca_env* env, const mrca_planner_params* params, int32_t* pw_out, int32_t* ph_out) {
+    mrca::PlannerParams q;
+    if (const int rc = check_planner_params("mrca_planner_grid", params, &q)) return rc;
+    if (!pw_out || !ph_out) return fail(MRCA_ERR_INVALID, "mrca_planner_grid: pw_out / ph_out is NULL");
+    if (!env) return fail(MRCA_ERR_INVALID, "env is NULL");
+    *pw_out = mrca::plan_cells(env->view.g.width, q.stride);
+    *ph_out = mrca::plan_cells(env->view.g.height, q.stride);
+    return MRCA_OK;
+}
+
+int mrca_goal_fields(mrca_env* env, const mrca_planner_params* params, const float* goals_dev, int32_t G, uint32_t* field_dev,
+                     int32_t* rounds_out, void* stream) {
+    // everything that can be judged without the env, then the env
+    mrca::PlannerParams q;
+    if (const int rc = check_planner_params("mrca_goal_fields", params, &q)) return rc;
+    if (G < 1 || G > mrca::kPlanMaxGoals) return fail(MRCA_ERR_INVALID, "mrca_goal_fields: G %d outside 1..%d", G, mrca::kPlanMaxGoals);
+    if (!goals_dev) return fail(MRCA_ERR_INVALID, "mrca_goal_fields: goals_dev is NULL");
+    if (reinterpret_cast<uintptr_t>(goals_dev) % 4) return fail(MRCA_ERR_INVALID, "mrca_goal_fields: goals_dev must be 4-byte aligned");
+    if (!field_dev) return fail(MRCA_ERR_INVALID, "mrca_goal_fields: field_dev is NULL");
+    if (reinterpret_cast<uintptr_t>(field_dev) % 4) return fail(MRCA_ERR_INVALID, "mrca_goal_fields: field_dev must be 4-byte aligned");
+    if (!env) return fail(MRCA_ERR_INVALID, "env is NULL");
+    if (!env->reset_seen) return fail(MRCA_ERR_INVALID, "mrca_goal_fields before the first mrca_reset");
+    DeviceGuard guard(env->cfg.device);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (capturing(s))
+        return fail(MRCA_ERR_INVALID, "mrca_goal_fields inside a stream capture: it synchronises the stream while it looks for convergence");
+    constexpr int kEvery = 4;     // the counters are read every kEvery launches, each launch has its own
+    if (!env->plan_counters) HIP_TRY(device_alloc(&env->plan_counters, kEvery * sizeof(uint32_t)));
+    uint32_t* counters = env->plan_counters.get();
+    const int pw = mrca::plan_cells(env->view.g.width, q.stride), ph = mrca::plan_cells(env->view.g.height, q.stride);
+    const int64_t bound = q.max_rounds > 0 ? (int64_t)q.max_rounds : mrca::plan_round_bound(pw, ph);
+    HIP_TRY(hipMemsetAsync(counters, 0, kEvery * sizeof(uint32_t), s));
+    mrca::launch_goal_field_init(env->view, q, goals_dev, G, field_dev, s);
+    HIP_TRY(hipGetLastError());
+    int64_t quiet = -1;           // the first launch in which nothing fell
+    for (int64_t base = 0; base < bound && quiet < 0; base += kEvery) {
+        const int nb = (int)std::min<int64_t>(kEvery, bound - base);
+        for (int r = 0; r < nb; ++r) mrca::launch_goal_field_round(env->view, q, G, field_dev, counters + r, s);
+        HIP_TRY(hipGetLastError());
+        uint32_t seen[kEvery] = {0, 0, 0, 0};
+        HIP_TRY(hipMemcpyAsync(seen, counters, sizeof seen, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemsetAsync(counters, 0, sizeof seen, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        for (int r = nb - 1; r >= 0; --r)
+            if (seen[r] == 0) quiet = base + r;
+    }
+    mrca::launch_goal_field_finish(env->view, q, G, field_dev, s);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(s));
+    if (rounds_out) *rounds_out = (int32_t)std::min<int64_t>(quiet >= 0 ? quiet : bound, INT32_MAX);
+    if (quiet < 0)
+        return fail(MRCA_ERR_UNSUPPORTED, "mrca_goal_fields: not converged within max_rounds = %lld launches (the field holds upper bounds)",
+                    (long long)bound);
+    return MRCA_OK;
+}
+
+int mrca_subgoals(mrca_env* env, const mrca_planner_params* params, const uint32_t* field_dev, const float* goals_dev, int32_t G,
+                  const int32_t* slot_dev, const uint8_t* mask_dev, float* local_dev, float* subgoal_dev, float* dist_dev,
+                  int32_t* status_dev, void* stream) {
+    // everything that can be judged without the env, then the env
+    mrca::PlannerParams q;
+    if (const int rc = check_planner_params("mrca_subgoals", params, &q)) return rc;
+    if (G < 1 || G > mrca::kPlanMaxGoals) return fail(MRCA_ERR_INVALID, "mrca_subgoals: G %d outside 1..%d", G, mrca::kPlanMaxGoals);
+    if (!field_dev) return fail(MRCA_ERR_INVALID, "mrca_subgoals: field_dev is NULL");
+    if (reinterpret_cast<uintptr_t>(field_dev) % 4) return fail(MRCA_ERR_INVALID, "mrca_subgoals: field_dev must be 4-byte aligned");
+    if (!goals_dev) return fail(MRCA_ERR_INVALID, "mrca_subgoals: goals_dev is NULL");
+    if (reinterpret_cast<uintptr_t>(goals_dev) % 4) return fail(MRCA_ERR_INVALID, "mrca_subgoals: goals_dev must be 4-byte aligned");
+    if (reinterpret_cast<uintptr_t>(slot_dev) % 4) return fail(MRCA_ERR_INVALID, "mrca_subgoals: slot_dev must be 4-byte aligned");
+    if (!local_dev) return fail(MRCA_ERR_INVALID, "mrca_subgoals: local_dev is NULL");
+    if (reinterpret_cast<uintptr_t>(local_dev) % 8) return fail(MRCA_ERR_INVALID, "mrca_subgoals: local_dev must be 8-byte aligned");
+    if (reinterpret_cast<uintptr_t>(subgoal_dev) % 4) return fail(MRCA_ERR_INVALID, "mrca_subgoals: subgoal_dev must be 4-byte aligned");
+    if (reinterpret_cast<uintptr_t>(dist_dev) % 4) return fail(MRCA_ERR_INVALID, "mrca_subgoals: dist_dev must be 4-byte aligned");
+    if (reinterpret_cast<uintptr_t>(status_dev) % 4) return fail(MRCA_ERR_INVALID, "mrca_subgoals: status_dev must be 4-byte aligned");
+    if (!env) return fail(MRCA_ERR_INVALID, "env is NULL");
+    if (!slot_dev && G != env->cfg.robots_per_world)
+        return fail(MRCA_ERR_INVALID, "mrca_subgoals: slot_dev NULL (slot = n %% robots_per_world) needs G == robots_per_world (%d), got %d",
+                    env->cfg.robots_per_world, G);
+    if (!env->reset_seen) return fail(MRCA_ERR_INVALID, "mrca_subgoals before the first mrca_reset: there is no head record yet");
+    // (a measurement switch, tools/planner_probe.py: a robot per thread in place of eight lanes per robot -- the same outputs)
+    static const int lanes = [] {
+        const char* v = getenv("MRCA_SUBGOAL_LANES");
+        return (v && v[0] == '1' && !v[1]) ? 1 : 8;
+    }();
+    DeviceGuard guard(env->cfg.device);
+    mrca::launch_subgoals(env->view, q, field_dev, goals_dev, G, slot_dev, mask_dev, local_dev, subgoal_dev, dist_dev, status_dev, lanes,
+                          static_cast<hipStream_t>(stream));
     HIP_TRY(hipGetLastError());
     return MRCA_OK;
 }

@@ -34,7 +34,8 @@ EXPORTS = ["mrca_abi_version", "mrca_last_error", "mrca_arena_bytes", "mrca_crea
            "mrca_relu_cat_backward_bias", "mrca_render", "mrca_orca_default_params", "mrca_orca_actions", "mrca_orca_actions_any",
            "mrca_dwa_default_params", "mrca_dwa_actions", "mrca_scan_noise_default_params", "mrca_scan_noise",
            "mrca_hybrid_default_params", "mrca_hybrid_actions",
-           "mrca_safe_policy_default_params", "mrca_hybrid_plan", "mrca_hybrid_commit", "mrca_lidar_features_scaled"]
+           "mrca_safe_policy_default_params", "mrca_hybrid_plan", "mrca_hybrid_commit", "mrca_lidar_features_scaled",
+           "mrca_planner_default_params", "mrca_planner_grid", "mrca_goal_fields", "mrca_subgoals"]
 # declared in include/mrca_env.h like the names above, listed apart: tests/test_abi.py's header scan reads names of letters
 # and underscores only (tests/test_policy_bf16_host.py checks these against the header and the library)
 EXPORTS_WITH_DIGITS = ["mrca_lidar_features_bf16", "mrca_lidar_features_bf16_rows", "mrca_lidar_features_bf16_backward",
@@ -79,6 +80,11 @@ class HybridParamsStruct(C.Structure):
 class SafePolicyParamsStruct(C.Structure):
     """include/mrca_env.h: mrca_safe_policy_params"""
     _fields_ = [(k, C.c_float) for k in ("scan_scale", "v_cap")]
+
+
+class PlannerParamsStruct(C.Structure):
+    """include/mrca_env.h: mrca_planner_params"""
+    _fields_ = [(k, C.c_int32) for k in ("stride", "inflate", "lookahead", "max_rounds")]
 
 
 class MrcaConfig(C.Structure):
@@ -188,6 +194,11 @@ def load(path=None):
     lib.mrca_hybrid_commit.argtypes = [C.c_int32, C.POINTER(SafePolicyParamsStruct)] + [C.c_void_p] * 6
     lib.mrca_lidar_features_scaled.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 6
     lib.mrca_lidar_features_bf16_scaled.argtypes = lib.mrca_lidar_features_scaled.argtypes
+    lib.mrca_planner_default_params.argtypes = [C.POINTER(PlannerParamsStruct)]
+    lib.mrca_planner_grid.argtypes = [C.c_void_p, C.POINTER(PlannerParamsStruct), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    lib.mrca_goal_fields.argtypes = [C.c_void_p, C.POINTER(PlannerParamsStruct), C.c_void_p, C.c_int32, C.c_void_p,
+                                     C.POINTER(C.c_int32), C.c_void_p]
+    lib.mrca_subgoals.argtypes = [C.c_void_p, C.POINTER(PlannerParamsStruct), C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 7
     lib.mrca_enable_timing.argtypes = [C.c_void_p, C.c_int32]
     if hasattr(lib, "mrca_set_debug_flags"):      # profiling build only
         lib.mrca_set_debug_flags.argtypes = [C.c_void_p, C.c_int32]

@@ -170,6 +170,37 @@ def safe_policy_fn(policy, env, params=None, safe=None, fused_bf16=False, skip_f
     return fn
 
 
+def planner_policy_fn(env, other, params=None):
+    """The global planner under the controller function ``other`` (a checkpoint or a stand-in): the goal fields are planned at
+    the first tick (``VecStageWorld.plan_goals``: the distinct goals of the env as they stand behind the reset), and every tick
+    ``other`` is handed the robots' subgoals in their own frames (``VecStageWorld.subgoals``) in place of ``env.local_goal``.
+    ``fn.report()`` -> the params, the status counts of the last tick and the mean path length at the first tick."""
+    from .planner import STATUS_NAMES, PlannerParams
+    params = params if params is not None else PlannerParams.for_grid(env.scenario.grid)
+    state = {"fields": None, "first_dist": None}
+    out = (torch.zeros((env.N, 2), dtype=torch.float32, device=env.device), torch.zeros((env.N, 2), dtype=torch.float32, device=env.device),
+           torch.zeros(env.N, dtype=torch.float32, device=env.device), torch.zeros(env.N, dtype=torch.int32, device=env.device))
+
+    def fn(obs, local_goal, speed):
+        if state["fields"] is None:
+            state["fields"] = env.plan_goals(params=params)
+        local, _sub, dist, _status = env.subgoals(state["fields"], out=out)
+        if state["first_dist"] is None:
+            finite = dist[torch.isfinite(dist)]
+            state["first_dist"] = float(finite.mean()) if finite.numel() else None
+        return other(obs, local, speed)
+    fn.wants_obs = getattr(other, "wants_obs", True)
+
+    def report():
+        f = state["fields"]
+        return {"planner_params": params.as_dict(),
+                "planner_goals": None if f is None else f.num_goals, "planner_rounds": None if f is None else f.rounds,
+                "planner_status_last_tick": {name: int((out[3] == code).sum()) for code, name in STATUS_NAMES.items()},
+                "planner_mean_initial_path_m": state["first_dist"]}
+    fn.report = report
+    return fn
+
+
 def perturbed_start(env, jitter_xy, jitter_th, seed):
     """Start poses of a circle world with every robot moved off its table pose by U(-jitter_xy, jitter_xy) metres in x
     and y and U(-jitter_th, jitter_th) radians of heading -- drawn from a Philox generator seeded with ``seed``, so that
@@ -276,7 +307,17 @@ def main():
     ap.add_argument("--policy", default=None, help="state_dict file with the reference's keys (policy/stage2.pth)")
     ap.add_argument("--max-ticks", type=int, default=1200)   # circle_world.py:198 allows 10000
     ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--robots", type=int, default=50, help="robots per circle (50 = the reference's table; others: scenario.circle_n)")
+    ap.add_argument("--robots", type=int, default=None, help="robots per circle (default 50 = the reference's table; others: "
+                                                             "scenario.circle_n) or per doorway room (default 12, at most 24)")
+    ap.add_argument("--scenario", default="circle", choices=["circle", "doorway"],
+                    help="doorway: scenario.doorway, --circles rooms split by a wall whose one door lies on no robot's straight line "
+                         "to its goal (excludes --radius / --one-circle / --stage-resolution)")
+    ap.add_argument("--planner", action="store_true",
+                    help="the global planner under --policy P [--fused | --fused-bf16] or the stand-in: goal fields planned once "
+                         "(mrca_goal_fields), the controller handed each robot's subgoal (mrca_subgoals) in place of the local goal; "
+                         "the result line gains planner_params, the status counts of the last tick and the mean initial path length")
+    ap.add_argument("--planner-param", action="append", default=[], metavar="NAME=VALUE",
+                    help="a field of mrca_planner_params on top of PlannerParams.for_grid of the map, e.g. lookahead=10 (repeatable)")
     ap.add_argument("--radius", type=float, default=25.0)
     ap.add_argument("--one-circle", type=int, default=None, metavar="N",
                     help="ONE circle of N robots in an open world (scenario.circle_big: the radius grows with N so that the "
@@ -334,6 +375,16 @@ def main():
     if a.fused_bf16:
         a.fused = True
     from .vec_env import VecStageWorld
+    doorway = a.scenario == "doorway"
+    if doorway and (a.radius != 25.0 or a.one_circle is not None or a.stage_resolution):
+        ap.error("--scenario doorway excludes --radius / --one-circle / --stage-resolution")
+    if a.robots is None:
+        a.robots = 12 if doorway else 50
+    if a.planner_param and not a.planner:
+        ap.error("--planner-param goes with --planner")
+    if a.planner and (a.orca or a.dwa or a.hybrid or a.hybrid_safe or a.orca_first is not None or a.dwa_first is not None):
+        ap.error("--planner hands the subgoal to a controller that takes the local goal as an argument (--policy, the stand-in): the "
+                 "kernels of --orca / --dwa / --hybrid / --hybrid-safe read the env's own local goal")
     if a.hybrid_safe_param and not a.hybrid_safe:
         ap.error("--hybrid-safe-param goes with --hybrid-safe")
     if a.hybrid_safe:
@@ -356,6 +407,11 @@ def main():
         if a.one_circle < 1:
             ap.error("--one-circle needs at least one robot")
         sc = scenario.circle_big(a.one_circle, seed=a.seed, spacing=a.spacing)
+    elif doorway:
+        try:
+            sc = scenario.doorway(num_worlds=a.circles, robots=a.robots, seed=a.seed, timeout=a.max_ticks)
+        except ValueError as e:
+            ap.error(str(e))
     elif a.robots == 50 and a.radius == 25.0:
         sc = scenario.circle(num_worlds=a.circles, seed=a.seed, stage_resolution=a.stage_resolution)
     else:
@@ -383,8 +439,18 @@ def main():
             fn = safe_policy_fn(pol, env, hybrid_params, safe_params, fused_bf16=a.fused_bf16,
                                 skip_first=max(a.orca_first or 0, a.dwa_first or 0))
             safe_fn, name = fn, f"hybrid control in the paper's form (mrca_hybrid_plan, mrca_hybrid_commit) around {name}"
+    elif doorway:
+        fn, name = go_to_goal_policy, "go-to-goal stand-in (no checkpoint given)"
     else:
         fn, name = staggered_roundabout_policy(env.N), "staggered-roundabout stand-in (no checkpoint given)"
+    if a.planner:
+        from .planner import PlannerParams
+        try:
+            planner_params = PlannerParams.from_assignments(a.planner_param, base=PlannerParams.for_grid(sc.grid))
+        except ValueError as e:
+            ap.error(str(e))
+        fn = planner_fn = planner_policy_fn(env, fn, planner_params)
+        name = f"global planner (mrca_goal_fields, mrca_subgoals) under {name}"
     orca_call = "mrca_orca_actions_any" if env.R > 64 else "mrca_orca_actions"
     if a.orca or a.orca_first is not None:
         from .orca import OrcaParams
@@ -438,6 +504,10 @@ def main():
         out["hybrid_safe_params"] = dataclasses.asdict(safe_params)
         out["hybrid_params"] = dataclasses.asdict(hybrid_params)
         out["hybrid_modes"] = safe_fn.mode_shares()
+    if a.planner:
+        out.update(planner_fn.report())
+    if doorway:
+        out["scenario"] = a.scenario
     out["lidar_noise"] = None if noise is None else noise.as_dict()
     out["robots_per_circle"], out["radius_m"] = a.robots, a.radius
     if a.one_circle is not None:

@@ -191,6 +191,36 @@ def circle_train(num_worlds=1, seed=0, timeout=900, grid=None):
     return sc
 
 
+DOORWAY_DOOR_Y = (1.8, 3.4)      # the door's extent along the dividing wall [m]
+
+
+def doorway(num_worlds=1, robots=2, seed=0, timeout=900):
+    """A walled room of 10 m x 8 m (0.1 m cells) split at x = 0 by a wall with ONE door, up at y in DOORWAY_DOOR_Y -- and every
+    robot's straight line to its goal crosses the wall below it: a controller that steers at the goal alone ends at the wall,
+    one that is handed subgoals (``VecStageWorld.plan_goals`` / ``subgoals``) goes round through the door.  Robots with an even
+    local index start on the left and have their goal on the right, odd ones the other way (table starts and goals, at most
+    24); nothing resets, an episode times out after ``timeout`` ticks."""
+    R = int(robots)
+    if not 1 <= R <= 24:
+        raise ValueError("doorway: 1..24 robots")
+    cell, w, h = 0.1, 100, 80
+    x0, y0 = -5.0, -4.0
+    occ = np.zeros((h, w), bool)
+    occ[:2, :] = occ[-2:, :] = occ[:, :2] = occ[:, -2:] = True
+    yc = y0 + (np.arange(h) + 0.5) * cell
+    occ[(yc < DOORWAY_DOOR_Y[0]) | (yc > DOORWAY_DOOR_Y[1]), w // 2 - 1: w // 2 + 1] = True
+    init, goal = np.zeros((R, 3)), np.zeros((R, 2))
+    for i in range(R):
+        side = -1.0 if i % 2 == 0 else 1.0
+        row, col = (i // 2) % 6, (i // 2) // 6
+        init[i] = (side * (3.8 - 0.9 * col), -3.2 + 0.8 * row, 0.0 if side < 0 else np.pi)
+        goal[i] = (-side * (3.35 - 0.9 * col), -3.2 + 0.8 * (5 - row))
+    mode = np.full(R, RESET_TABLE, np.int32)
+    return Scenario("doorway", num_worlds, R, GridData.from_dense(occ, cell, x0, y0), timeout=int(timeout), w_thresh=0.7,
+                    pre_dist_zero=True, auto_reset=AUTO_NONE, seed=seed, reset_mode=mode, goal_mode=mode.copy(),
+                    init_table=init, goal_table=goal)
+
+
 def circle_n(robots, radius, num_worlds=1, seed=0, train=False, timeout=None, grid=None):
     """Smaller relatives of the circle test inside the same 60 m rink: ``robots`` (<= 64) robots evenly spaced on a
     circle of ``radius`` metres (<= 27), facing the centre, antipodal goals; reward constants of circle_world.py.

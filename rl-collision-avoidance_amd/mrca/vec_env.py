@@ -351,6 +351,52 @@ class VecStageWorld:
                                                self._stream()), "mrca_hybrid_commit")
         return out
 
+    def plan_goals(self, goals=None, params=None):
+        """The planning call of the global planner (mrca_goal_fields): one integer field of shortest-path lengths over the
+        coarsened map per goal point -> a ``planner.GoalFields``.  ``goals``: a float32[G,2] tensor of goal points; every robot
+        then walks to goal ``n % G`` (set ``fields.slot`` for another assignment; -1: none).  Default: the distinct rows of
+        ``env.goal`` as they stand, one slot per robot.  ``params``: a ``planner.PlannerParams`` (default: the library's).
+        SYNCHRONISES the current stream while it looks for convergence; not capturable.  Plan again when the goals change."""
+        from .planner import GoalFields, PlannerParams
+        params = params if params is not None else PlannerParams()
+        if goals is None:
+            goals, slot = torch.unique(self.goal, dim=0, return_inverse=True)
+            goals, slot = goals.contiguous(), slot.to(torch.int32).contiguous()
+        else:
+            goals = torch.as_tensor(goals, dtype=torch.float32, device=self.device).reshape(-1, 2).contiguous()
+            slot = (torch.arange(self.N, device=self.device) % goals.shape[0]).to(torch.int32)
+        G = int(goals.shape[0])
+        st = params.struct()
+        pw, ph = C.c_int32(), C.c_int32()
+        _lib.check(self.lib.mrca_planner_grid(self._h, C.byref(st), C.byref(pw), C.byref(ph)), "mrca_planner_grid")
+        field = torch.empty((G, ph.value, pw.value), dtype=torch.int32, device=self.device)
+        rounds = C.c_int32()
+        _lib.check(self.lib.mrca_goal_fields(self._h, C.byref(st), self._ptr(goals, torch.float32, 2 * G), G,
+                                             C.c_void_p(field.data_ptr()), C.byref(rounds), self._stream()), "mrca_goal_fields")
+        return GoalFields(field, goals, slot, params, rounds.value)
+
+    def subgoals(self, fields, mask=None, out=None):
+        """The per-tick call (mrca_subgoals): every robot's subgoal a few steps down its slot's field ->
+        ``(local, subgoal, dist, status)``: the subgoal in the robot's frame (float32[N,2]: hand it to the controller in place
+        of ``env.local_goal``), in the world (float32[N,2]), the path length from where the robot stands in metres (float32[N],
+        inf: none) and int32[N] 1 (the goal itself) / 0 (a cell centre on the path) / -1 (no slot) / -2 (no path: the goal
+        itself).  One launch on the current stream, nothing synchronises, nothing of the env is written.  ``out``: the four
+        tensors to write into; ``mask``: a uint8[N] tensor, rows with 0 keep what ``out`` holds."""
+        if out is None:
+            out = (torch.zeros((self.N, 2), dtype=torch.float32, device=self.device),
+                   torch.zeros((self.N, 2), dtype=torch.float32, device=self.device),
+                   torch.zeros(self.N, dtype=torch.float32, device=self.device),
+                   torch.zeros(self.N, dtype=torch.int32, device=self.device))
+        local, subgoal, dist, status = out
+        G = fields.num_goals
+        st = fields.params.struct()
+        _lib.check(self.lib.mrca_subgoals(self._h, C.byref(st), C.c_void_p(fields.field.data_ptr()),
+                                          self._ptr(fields.goals, torch.float32, 2 * G), G, self._ptr(fields.slot, torch.int32, self.N),
+                                          self._ptr(mask, torch.uint8, self.N), self._ptr(local, torch.float32, 2 * self.N),
+                                          self._ptr(subgoal, torch.float32, 2 * self.N), self._ptr(dist, torch.float32, self.N),
+                                          self._ptr(status, torch.int32, self.N), self._stream()), "mrca_subgoals")
+        return local, subgoal, dist, status
+
     def scan_noise(self, params=None, mask=None):
         """The lidar noise model (mrca_scan_noise) applied IN PLACE to the newest scan row of every robot (``mask``: a uint8[N]
         tensor, rows with 0 are not touched): range noise, quantisation and dropout as ``params`` (a ``noise.ScanNoiseParams``;
