@@ -396,6 +396,51 @@ MRCA_HD float idle_axis_time(float raw, bool travels) {
 #endif
 }
 
+// The settlement of a jump's secondary axis, stated once (grid_march_skip and grid_march_skip_n): the jump leaves its
+// rectangle at time t through a face of the OTHER axis; which crossings b of this axis were consumed before it -- x exit: those
+// with tS(b) <= t, y exit: tS(b) < t, both as tS(b) < tle (at_or_before), tS(b) = (float(b) - fS) * invS the walk's own closed
+// form -- and so which boundary is the first one pending?  ONE candidate and one time decide:
+//
+//   * tS is monotone along the direction of travel sS (float(b) is exact, the subtraction and the product by a constant of
+//     sS's sign are monotone roundings), so the answer b* is the first b, counted from bS0 along sS, with !(tS(b) < tle).
+//   * Where the real line puts it: tS(b) = (b - fS) / dS * (1 + e), |e| <= 3 * 2^-24 (the roundings of 1 / dS, of the
+//     difference and of the product), and tle <= t * (1 + 2^-23).  With p* = fS + t * dS in real arithmetic and
+//     E1 = |t * dS| * 2^-21 (|t * dS| <= 170 cells, the bound this march has always stood on: E1 <= 8.2e-5) a crossing more
+//     than E1 before p* is consumed, and one more than E1 beyond p* is not.
+//   * The estimate is biased TOWARDS THE ORIGIN by delta = kSettleBias, and the `+ u` of "pending boundary = cell + u" rides in
+//     the same constant: pB = fSb + dS * t with fSb = RN(fS + (sS > 0 ? 1 - delta : delta)) formed once per beam
+//     (settle_origin).  Three roundings stand between pB and p* + (sS > 0 ? 1 - delta : delta): fSb's, the product's and the
+//     sum's, each at most 2^-24 of its result, and the results are no larger than |fS| + 1, 170 and
+//     |fS| + 171 -- Ep <= 2^-24 * (2 |fS| + 342) in all: 0.008 at |fS| = 2^16 and 0.0625 at |fS| = 2^19.
+//   * b = floor(pB), clamped to lie at or beyond bS0.  Going up (sS = +1): every boundary before b is an integer
+//     <= pB - 1 <= p* - delta + Ep, which is more than E1 before p* when delta > Ep + E1: CONSUMED; and b + 1 > pB >=
+//     p* + 1 - delta - Ep, which is more than E1 beyond p* when delta + Ep + E1 < 1: NEVER consumed.  Going down is the mirror
+//     image (b = floor(p* + delta +- Ep): boundaries before it are integers >= b + 1 > pB, b - 1 <= pB - 1).  So b* is b or
+//     b + sS, and tS(b) < tle says which.  The clamp keeps this: where the estimate falls short of bS0, every boundary before
+//     bS0 was consumed by earlier jumps and bS0 + sS lies beyond the unclamped b + sS, so is not consumed either.
+//   * Ep + E1 < delta < 1 - Ep - E1: delta = 2^-3 holds for every origin with |f| <= 2^19 cells (Ep + E1 <= 0.0627) -- every map
+//     mrca_create accepts (at most 2^14 cells a side) with the robot up to thirty map widths outside it.  An unbiased
+//     floor(pT) + u (delta = 0: build with -DMRCA_SETTLE_BIAS=0 to see it fail) lands one boundary either side of b* and
+//     needs the second candidate b - sS, which is what this function held until the bias: 8 more instructions per trip.
+//
+// A lane past its beam's end, and the idle axis of an axis-parallel ray on the device (origin -inf), send an infinity or a NaN
+// through here: the conversion saturates and the clamp is inline assembly (see grid_march_skip), the result is never used.
+#ifndef MRCA_SETTLE_BIAS
+#define MRCA_SETTLE_BIAS 0.125f
+#endif
+constexpr float kSettleBias = MRCA_SETTLE_BIAS;
+// the origin the estimate starts from on an axis travelled in the positive (pos) or the negative direction
+MRCA_HD float settle_origin(float f, bool pos) { return f + (pos ? 1.0f - kSettleBias : kSettleBias); }
+// -> the first pending boundary.  fS, fSb: the axis' origin and its biased twin; dS, invS: the direction's component and its
+// reciprocal; sS = +-1; bS0: the pending boundary before the jump; lim = sS * 2^30 (the clamp's far end, never reached)
+MRCA_HD int settle_secondary(float fS, float fSb, float dS, float invS, int sS, int bS0, int lim, float t, float tle) {
+    const float pB = fSb + dS * t;
+    // (a pending boundary only ever moves in the direction of travel: clamp(b, from bS0) = med3(b, bS0, +-2^30))
+    const int b = med3_i32((int)floorf(pB), bS0, lim);
+    const float tc = ((float)b - fS) * invS;          // b itself: consumed before t?
+    return tc < tle ? b + sS : b;
+}
+
 template <class Field>
 MRCA_HD float grid_march_skip(const Field& field, const GridGeom& g, const MarchOrigin& org, float dx, float dy,
                               float tmax) {
@@ -421,6 +466,7 @@ MRCA_HD float grid_march_skip(const Field& field, const GridGeom& g, const March
     const float inv_dy = ynz ? rdy : kInf;
     const int sx = xpos ? 1 : -1, sy = ypos ? 1 : -1;
     const int ux = xpos ? 1 : 0, uy = ypos ? 1 : 0;      // current cell = pending boundary - u, on each axis
+    const float fbx = settle_origin(fx, xpos), fby = settle_origin(fy, ypos);   // (once per beam: settle_secondary)
     // An axis-parallel ray never crosses a boundary of its zero axis -- which then is always the secondary
     // axis below (its exit time is +inf), so the whole estimate is skipped for such a ray.
     const bool bothnz = xnz & ynz;
@@ -463,28 +509,13 @@ MRCA_HD float grid_march_skip(const Field& field, const GridGeom& g, const March
         if (wave_any(go)) {
             // the other ("secondary") axis: which of its crossings were consumed before time t?
             // x exit: y crossings with ty(b) <= t;  y exit: x crossings with tx(b) < t.
-            const float fS = xe ? fy : fx;
-            const float invS = xe ? inv_dy : inv_dx;
+            // Settled branch-free from an estimate of the position at time t and ONE closed-form time (settle_secondary; a
+            // data-dependent "only when close to a boundary" test would make the whole wavefront take the slow path whenever
+            // one of its 64 rays is close).
             const int sS = xe ? sy : sx;
             const int bS0 = xe ? by : bx;
-            // position on the secondary axis at time t.  The consumed crossings are exactly those on
-            // the near side of p* = fS + t*dS*(1 +- 2.4e-7) (rounding of 1/dS and of the closed form),
-            // and pT differs from p* by far less than one cell (|t*dS| <= 170, |fS| <= 2^16: < 0.01),
-            // so the first pending boundary is floor(pT) (+1 going up) or one of its two neighbours.
-            // Which one is decided with the closed-form times themselves, branch-free (a data-dependent
-            // "only when close to a boundary" test would make the whole wavefront take the slow path
-            // whenever one of its 64 rays is close).
-            const float pT = fS + (xe ? dy : dx) * t;
-            // (a pending boundary only ever moves in the direction of travel: clamp(b, from bS0) = med3(b, bS0, +-2^30))
-            const int b = med3_i32((int)floorf(pT) + (xe ? uy : ux), bS0, (int)((uint32_t)sS << 30));
-            const int bprev = b - sS;
-            const float tp = ((float)bprev - fS) * invS;      // the crossing before b ...
-            const float tc = ((float)b - fS) * invS;          // ... and b itself: consumed before t?
-            const float tle = at_or_before(t, xe);            // x exit: "<= t", y exit: "< t"
-            const bool cons_p = tp < tle;
-            const bool cons_c = tc < tle;
-            int bS = cons_c ? b + sS : b;                     // cons_c implies cons_p (times are monotone)
-            bS = ((b != bS0) & !cons_p) ? bprev : bS;
+            int bS = settle_secondary(xe ? fy : fx, xe ? fby : fbx, xe ? dy : dx, xe ? inv_dy : inv_dx, sS, bS0,
+                                      (int)((uint32_t)sS << 30), t, at_or_before(t, xe));   // x exit: "<= t", y exit: "< t"
             // An axis-parallel ray never crosses a boundary of its zero axis -- which then is always the secondary
             // axis (its exit time is +inf): it keeps its pending boundary
             bS = bothnz ? bS : bS0;
@@ -574,17 +605,9 @@ MRCA_HD void grid_march_skip_n(const Field& field, const GridGeom& g, const Marc
             const int sS = xe ? sy : sx;
             const int bS0 = xe ? by[k] : bx[k];
             int bS = bS0;
-            if (xnz & ynz) {
-                const float pT = fS + (xe ? dy[k] : dx[k]) * tt;
-                const int b = med3_i32((int)floorf(pT) + (xe ? uy : ux), bS0, xe ? limy : limx);
-                const int bprev = b - sS;
-                const float tp = ((float)bprev - fS) * invS;
-                const float tc = ((float)b - fS) * invS;
-                const bool cons_p = (tp < tt) | ((tp == tt) & xe);
-                const bool cons_c = (tc < tt) | ((tc == tt) & xe);
-                bS = cons_c ? b + sS : b;
-                bS = ((b != bS0) & !cons_p) ? bprev : bS;
-            }
+            if (xnz & ynz)       // (tt is finite and >= 0 here: at_or_before's precondition)
+                bS = settle_secondary(fS, xe ? settle_origin(fy, ypos) : settle_origin(fx, xpos), xe ? dy[k] : dx[k], invS, sS,
+                                      bS0, xe ? limy : limx, tt, at_or_before(tt, xe));
             go[k] = act[k] && !(tt >= tmax_c);
             tn[k] = tt;
             nbx[k] = go[k] ? (xe ? Bx + sx : bS) : bx[k];
@@ -927,9 +950,27 @@ MRCA_HD bool obb_overlap(float xi, float yi, float si, float ci, float xj, float
     return !sep;
 }
 
+// rcp_exact for an argument KNOWN to lie inside its fast range, 2^-100 <= |d| <= 2^100: the same three instructions and the same
+// bits, without the test for "outside" and its wave-uniform branch (two compares, an OR, a mask move and a branch).  The
+// precondition is the caller's to state.  A NaN gives a NaN either way (the reciprocal, the Newton step and the quotient all
+// pass it on).  The host build is the plain quotient.
+MRCA_HD float rcp_exact_in_range(float d) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const float r = __builtin_amdgcn_rcpf(d);
+    const float e = __builtin_fmaf(-d, r, 1.0f);
+    return __builtin_fmaf(e, r, r);
+#else
+    return 1.0f / d;
+#endif
+}
+
 MRCA_HD void slab(float lo, float ld, float h, float* t0, float* t1) {
     const bool par = fabsf(ld) < 1e-12f;
-    const float inv = rcp_exact(par ? 1.0f : ld);
+    // The reciprocal's argument is 1 or an ld with |ld| >= 1e-12 > 2^-100; and ld = d . (a unit vector's rotation), |ld| <=
+    // |dx| |cj| + |dy| |sj| <= 2 + rounding for the unit directions and (sin, cos) pairs this is called with: inside
+    // rcp_exact_in_range's precondition.  A NaN direction cannot occur (a non-finite command is zeroed before it reaches a
+    // heading, sane_cmd); if one did, `par` is false for it and t0, t1 are NaNs with either reciprocal.
+    const float inv = rcp_exact_in_range(par ? 1.0f : ld);
     const float ta = (-h - lo) * inv;
     const float tb = (h - lo) * inv;
     const bool out = fabsf(lo) > h;
