@@ -1,5 +1,7 @@
 // mrca_abi.hip -- host side of include/mrca_env.h: config validation, the SoA device arena,
-// table / map upload, kernel sequencing and optional HIP-event timing.  No torch, no Python.
+// table / map upload, kernel sequencing and optional HIP-event timing.  No torch, no Python.  What an env is made of is in
+// mrca_env_state.h; the entry points of the renderer, the controllers, the noise model and the planner are in
+// mrca_abi_controllers.hip.
 #include <hip/hip_runtime.h>
 #include <string>
 #include <chrono>
@@ -21,15 +23,11 @@
 #include "mrca_host.h"
 #include "mrca_hostutil.h"
 #include "mrca_kernels.h"
-#include "mrca_orca.h"
-#include "mrca_dwa.h"
-#include "mrca_noise.h"
-#include "mrca_hybrid.h"
-#include "mrca_safe.h"
-#include "mrca_planner.h"
 #include "mrca_pass_plan.h"
-#include "mrca_render.h"
 #include "mrca_rollout_store.h"
+#include "mrca_env_state.h"      // (last: its `fail` is a macro)
+
+using namespace mrca::env_state;
 
 namespace {
 thread_local char g_err[512] = "";
@@ -49,28 +47,9 @@ namespace {
 
 using mrca::DeviceGuard;
 using mrca::kAheadTicks;
-#define fail(...) mrca::set_error(__VA_ARGS__)
-
-#define HIP_TRY(expr)                                                                               \
-    do {                                                                                            \
-        hipError_t _e = (expr);                                                                     \
-        if (_e != hipSuccess) return fail(MRCA_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(_e)); \
-    } while (0)
 
 constexpr size_t kAlign = 256;
 size_t align_up(size_t v) { return (v + kAlign - 1) / kAlign * kAlign; }
-
-struct Layout {
-    size_t field_off[MRCA_F_COUNT];
-    size_t field_bytes[MRCA_F_COUNT];
-    size_t off_reset_mode, off_goal_mode, off_group_id, off_init_table, off_goal_table;
-    size_t off_beam_cos, off_beam_sin, off_map, off_free_rect, off_cellfield, off_head, off_outline;
-    // big worlds (robots_per_world > 64) only
-    size_t off_bw_ticket, off_bw_prov, off_bw_state, off_bw_chead, off_bw_cnext, off_bw_lstart, off_bw_lcount, off_bw_lsorted, off_bw_lblock, off_bw_lcursor;
-    size_t off_status;
-    int32_t bw_cmask, bw_lmask;
-    size_t total;
-};
 
 int validate(const mrca_config* c) {
     if (!c) return fail(MRCA_ERR_INVALID, "config is NULL");
@@ -232,100 +211,7 @@ std::shared_ptr<const HostField> host_field(const mrca_config* c, bool octants) 
     return with_octants(f);
 }
 
-// Owners of what an env holds beside its arena.  A stream is synchronised before it is destroyed.
-struct StreamDeleter { void operator()(hipStream_t s) const { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } };
-struct EventDeleter { void operator()(hipEvent_t e) const { (void)hipEventDestroy(e); } };
-struct DeviceFree { void operator()(void* p) const { (void)hipFree(p); } };
-using Stream = std::unique_ptr<std::remove_pointer_t<hipStream_t>, StreamDeleter>;
-using Event = std::unique_ptr<std::remove_pointer_t<hipEvent_t>, EventDeleter>;
-template <class T> using DeviceBuffer = std::unique_ptr<T, DeviceFree>;
-
-hipError_t make_stream(Stream* s) {
-    hipStream_t h = nullptr;
-    const hipError_t e = hipStreamCreateWithFlags(&h, hipStreamNonBlocking);
-    if (e == hipSuccess) s->reset(h);
-    return e;
-}
-hipError_t make_event(Event* ev, unsigned flags = hipEventDisableTiming) {
-    hipEvent_t h = nullptr;
-    const hipError_t e = hipEventCreateWithFlags(&h, flags);
-    if (e == hipSuccess) ev->reset(h);
-    return e;
-}
-template <class T> hipError_t device_alloc(DeviceBuffer<T>* p, size_t bytes) {
-    void* d = nullptr;
-    const hipError_t e = hipMalloc(&d, bytes);
-    if (e == hipSuccess) p->reset(static_cast<T*>(d));
-    return e;
-}
-
-// mrca_step_many's run-ahead schedule: the move launches of a call's ticks run on a stream of their own,
-// AHEAD of the ray casts, each tick writing the five things a ray cast reads of a move launch -- pose, head record, goal,
-// fresh flag, outline -- into a slot of its own, so that no move launch ever waits for a ray cast.  Slot 0 is the env's
-// own fields (where a call starts and where its last tick ends); slots 1 .. slots live in `mem`.
-struct AheadRing {
-    DeviceBuffer<char> mem;
-    size_t slot_bytes = 0;
-    size_t off[5] = {0, 0, 0, 0, 0};  // pose, head, goal, fresh, outline inside a slot
-    int slots = 0;                    // 0: the ring could not be allocated -> the chained schedule
-    Stream move_stream;
-    std::vector<Event> moved;         // [kAheadTicks] "tick k's move launch is through"
-    // A range's ray casts go out as launches of up to ticks_per_launch consecutive ticks (mrca_raycast_ticks.hip; 1: a launch
-    // per tick).  Such a launch reads the ring heads from one array and leaves them in another -- the env's ring_head field
-    // and head_scratch [N] in turns, so that no workgroup reads what another one of its launch writes.
-    int ticks_per_launch = 1;
-    bool ticks_forced = false;        // MRCA_TICKS_PER_LAUNCH was set: that many wherever such launches are possible at all
-    DeviceBuffer<uint8_t> head_scratch;
-};
-
-// mrca_step_many with chains > 1: world range c >= 1's stream and the events that order it against the caller's -- `moved`:
-// range c - 1's first move launch is through (the chained schedule starts range c behind it), `done`: range c is through
-struct WorldRange { Stream stream; Event moved, done; };
-
-// stream choice (choose_streams below)
-struct StreamCheck {
-    // (at most 8, oldest first) the move stream and the streams of ranges 1 .. ranges - 1 overlap with `caller` and each other
-    struct Record { hipStream_t caller; int ranges; };
-    std::vector<Record> checked;                 // the caller's streams the env's CURRENT streams were checked against
-    DeviceBuffer<unsigned long long> stamps;     // [4] start / end of the two probe kernels
-    std::vector<Stream> parked;                  // found to share a hardware queue with another stream: kept until mrca_destroy
-    // has the caller's stream `s` been checked against the env's current streams for P ranges or more?
-    bool covers(hipStream_t s, int P) const {
-        return std::any_of(checked.begin(), checked.end(), [&](const Record& r) { return r.caller == s && r.ranges >= P; });
-    }
-};
-
 }  // namespace
-
-// Members are destroyed bottom-up: every stream (world ranges, the move stream, parked ones) is synchronised before the memory
-// above it that its launches may read (the ring, the probe stamps, the view copy, an owned arena) is freed.
-struct mrca_env {
-    DeviceBuffer<char> own_arena;         // the arena when the library allocated it
-    mrca_config cfg;
-    Layout layout;
-    char* arena = nullptr;
-    mrca::EnvView view;
-    DeviceBuffer<uint16_t> octant_rect;     // the octant free-rectangle array (outside the arena: the arena's size is ABI), or none
-    DeviceBuffer<mrca::EnvView> view_dev;   // `view` in device memory (outside the arena): what move_kernel / raycast_kernel read
-    DeviceBuffer<uint32_t> plan_counters;   // mrca_goal_fields' per-launch counters, from its first call on (it returns synchronised)
-    size_t lds_bytes = 0;
-    // timing
-    int timing = 0;      // 0 off, n > 0: record events on every n-th step
-    int step_count = 0;
-    std::vector<Event> ev;       // 4 per recorded step: begin / end of the move launch, begin / end of the ray cast
-    int ev_used = 0;
-    int last_ray_count = 0;   // workgroups of the last ray-cast launch (profiling build: whose stamps are current)
-    // robots_per_world > 64: does the lidar hash (bw_lstart / bw_lsorted) describe the poses as they stand behind everything
-    // enqueued so far?  In enqueue order: false after a move phase without its observe phase, true after launch_lidar_grid
-    // (mrca_reset, the observe phase).  Who reads the hash outside the tick asks here (mrca_orca_actions_any).
-    bool lidar_hash_current = false;
-    bool lidar_counts_pending = false;    // a move phase has left the next hash's bucket populations in bw_lcount
-    bool reset_seen = false;              // mrca_reset has been enqueued once: the ring holds scans (mrca_scan_noise asks)
-    StreamCheck check;                    // (these four: mrca_step_many)
-    AheadRing ahead;
-    std::vector<WorldRange> ranges;       // world ranges 1 .. P - 1
-    Event fork;                           // an early exit's join of the move stream
-};
 
 constexpr size_t kAheadMaxBytes = 256u << 20;
 // World range 1 gets its stream in mrca_create (chains <= 2, bench.py's default, may be captured at once); further ranges get
@@ -411,12 +297,6 @@ static hipError_t join_ranges(const mrca_env* env, hipStream_t s0, int upto) {
         if (err == hipSuccess) err = e1 != hipSuccess ? e1 : e2;
     }
     return err;
-}
-
-// is `s` being captured?  A query that fails counts as yes: what a capture cannot hold is not tried then
-static bool capturing(hipStream_t s) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    return hipStreamIsCapturing(s, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone;
 }
 
 // env->view -> its device copy (mrca_create; the profiling build's debug switches).  Synchronous: no launch that reads the
@@ -814,476 +694,6 @@ int mrca_newest_obs(mrca_env* env, float* out_dev, void* stream) {
     if (reinterpret_cast<uintptr_t>(out_dev) % 16) return fail(MRCA_ERR_INVALID, "out_dev must be 16-byte aligned");
     DeviceGuard guard(env->cfg.device);
     mrca::launch_newest_obs(env->view, out_dev, static_cast<hipStream_t>(stream));
-    HIP_TRY(hipGetLastError());
-    return MRCA_OK;
-}
-
-static_assert(sizeof(mrca_render_view) == sizeof(mrca::RenderView) && offsetof(mrca_render_view, m_per_px) == offsetof(mrca::RenderView, m),
-              "mrca_render_view and mrca::RenderView are one layout");
-
-int mrca_render(mrca_env* env, const mrca_render_view* views, int32_t num_views, int32_t width, int32_t height, uint32_t layers,
-                uint32_t* ids_dev, uint32_t* trail_dev, uint8_t* rgb_dev, void* stream) {
-    // (what can be judged without the env comes first: a caller's mistake is named whatever else is wrong)
-    if (num_views < 1 || num_views > 256) return fail(MRCA_ERR_INVALID, "mrca_render: num_views %d outside 1..256", num_views);
-    if (!views) return fail(MRCA_ERR_INVALID, "mrca_render: views is NULL");
-    if (width < 1 || width > 4096 || height < 1 || height > 4096)
-        return fail(MRCA_ERR_INVALID, "mrca_render: image size %d x %d outside 1..4096", width, height);
-    if (layers & ~(uint32_t)(MRCA_RENDER_MAP | MRCA_RENDER_GOALS | MRCA_RENDER_BODIES | MRCA_RENDER_BEAMS))
-        return fail(MRCA_ERR_INVALID, "mrca_render: unknown layer bits 0x%x", layers);
-    if (!ids_dev) return fail(MRCA_ERR_INVALID, "mrca_render: ids_dev is NULL");
-    if (reinterpret_cast<uintptr_t>(ids_dev) % 4 || reinterpret_cast<uintptr_t>(trail_dev) % 4 || reinterpret_cast<uintptr_t>(rgb_dev) % 4)
-        return fail(MRCA_ERR_INVALID, "mrca_render: ids_dev, trail_dev and rgb_dev must be 4-byte aligned");
-    for (int32_t v = 0; v < num_views; ++v)
-        if (!(views[v].m_per_px > 0.0f) || !std::isfinite(views[v].m_per_px) || !std::isfinite(views[v].cx) || !std::isfinite(views[v].cy))
-            return fail(MRCA_ERR_INVALID, "mrca_render: view %d needs a finite centre and a finite positive m_per_px", v);
-    if (!env) return fail(MRCA_ERR_INVALID, "env is NULL");
-    for (int32_t v = 0; v < num_views; ++v)
-        if (views[v].world < 0 || views[v].world >= env->cfg.num_worlds)
-            return fail(MRCA_ERR_INVALID, "mrca_render: view %d shows world %d of %d", v, views[v].world, env->cfg.num_worlds);
-    DeviceGuard guard(env->cfg.device);
-    mrca::launch_render(env->view, reinterpret_cast<const mrca::RenderView*>(views), num_views, width, height, layers, ids_dev,
-                        trail_dev, rgb_dev, static_cast<hipStream_t>(stream));
-    HIP_TRY(hipGetLastError());
-    return MRCA_OK;
-}
-
-static_assert(sizeof(mrca_orca_params) == sizeof(mrca::OrcaParams) && offsetof(mrca_orca_params, max_neighbors) == offsetof(mrca::OrcaParams, max_neighbors),
-              "mrca_orca_params and mrca::OrcaParams are one layout");
-
-int mrca_orca_default_params(mrca_orca_params* out) {
-    if (!out) return fail(MRCA_ERR_INVALID, "mrca_orca_default_params: out is NULL");
-    out->radius = 0.35f;            // the footprint's half diagonal 0.2907 m + a margin
-    out->neighbor_dist = 6.0f;
-    out->time_horizon = 2.0f;       // (time_horizon, k_omega): tuned on the three closed-loop gates, profiles/orca/defaults.txt
-    out->time_horizon_obst = 1.5f;
-    out->obst_dist = 3.0f;
-    out->v_pref = 1.0f;
-    out->max_speed = 1.0f;
-    out->responsibility = 0.5f;
-    out->k_omega = 6.0f;
-    out->jitter = 0.0f;
-    out->max_neighbors = 10;
-    return MRCA_OK;
-}
-
-// What mrca_orca_actions and mrca_orca_actions_any check alike, in one order and with one wording (`fn` names the caller):
-// everything that can be judged without the env, then the env.  -> *out: the params as the kernels take them
-static int orca_validate(const char* fn, const mrca_env* env, const mrca_orca_params* params, const float* actions_dev,
-                         const float* vel_dev, mrca::OrcaParams* out) {
-    mrca_orca_params p;
-    if (params) p = *params;
-    else mrca_orca_default_params(&p);
-    const float fl[10] = {p.radius, p.neighbor_dist, p.time_horizon, p.time_horizon_obst, p.obst_dist, p.v_pref, p.max_speed,
-                          p.responsibility, p.k_omega, p.jitter};
-    static const char* const names[10] = {"radius", "neighbor_dist", "time_horizon", "time_horizon_obst", "obst_dist", "v_pref",
-                                          "max_speed", "responsibility", "k_omega", "jitter"};
-    for (int i = 0; i < 10; ++i)
-        if (!std::isfinite(fl[i])) return fail(MRCA_ERR_INVALID, "%s: %s is not finite", fn, names[i]);
-    if (!(p.radius > 0.0f)) return fail(MRCA_ERR_INVALID, "%s: radius must be > 0", fn);
-    if (!(p.neighbor_dist > 0.0f)) return fail(MRCA_ERR_INVALID, "%s: neighbor_dist must be > 0", fn);
-    if (!(p.time_horizon > 0.0f)) return fail(MRCA_ERR_INVALID, "%s: time_horizon must be > 0", fn);
-    if (!(p.time_horizon_obst > 0.0f)) return fail(MRCA_ERR_INVALID, "%s: time_horizon_obst must be > 0", fn);
-    if (!(p.max_speed > 0.0f)) return fail(MRCA_ERR_INVALID, "%s: max_speed must be > 0", fn);
-    if (!(p.obst_dist >= 0.0f && p.obst_dist <= 6.0f)) return fail(MRCA_ERR_INVALID, "%s: obst_dist outside [0, 6]", fn);
-    if (!(p.responsibility >= 0.0f && p.responsibility <= 1.0f))
-        return fail(MRCA_ERR_INVALID, "%s: responsibility outside [0, 1]", fn);
-    if (p.max_neighbors < 0 || p.max_neighbors > mrca::kOrcaMaxNeighbors)
-        return fail(MRCA_ERR_INVALID, "%s: max_neighbors %d outside 0..%d", fn, p.max_neighbors, mrca::kOrcaMaxNeighbors);
-    if (!actions_dev) return fail(MRCA_ERR_INVALID, "%s: actions_dev is NULL", fn);
-    if (reinterpret_cast<uintptr_t>(actions_dev) % 8) return fail(MRCA_ERR_INVALID, "%s: actions_dev must be 8-byte aligned", fn);
-    if (reinterpret_cast<uintptr_t>(vel_dev) % 4) return fail(MRCA_ERR_INVALID, "%s: vel_dev must be 4-byte aligned", fn);
-    if (!env) return fail(MRCA_ERR_INVALID, "env is NULL");
-    static_assert(std::is_trivially_copyable<mrca::OrcaParams>::value, "");
-    memcpy(out, &p, sizeof *out);
-    return MRCA_OK;
-}
-
-int mrca_orca_actions(mrca_env* env, const mrca_orca_params* params, const uint8_t* mask_dev, float* actions_dev, float* vel_dev,
-                      void* stream) {
-    mrca::OrcaParams q;
-    if (int rc = orca_validate("mrca_orca_actions", env, params, actions_dev, vel_dev, &q)) return rc;
-    if (env->cfg.robots_per_world > mrca::kOrcaMaxRobots)
-        return fail(MRCA_ERR_UNSUPPORTED, "mrca_orca_actions: robots_per_world %d > %d", env->cfg.robots_per_world, mrca::kOrcaMaxRobots);
-    DeviceGuard guard(env->cfg.device);
-    mrca::launch_orca(env->view, q, mask_dev, actions_dev, vel_dev, static_cast<hipStream_t>(stream));
-    HIP_TRY(hipGetLastError());
-    return MRCA_OK;
-}
-
-int mrca_orca_actions_any(mrca_env* env, const mrca_orca_params* params, const uint8_t* mask_dev, float* actions_dev,
-                          float* vel_dev, void* stream) {
-    mrca::OrcaParams q;
-    if (int rc = orca_validate("mrca_orca_actions_any", env, params, actions_dev, vel_dev, &q)) return rc;
-    const bool big = env->cfg.robots_per_world > mrca::kOrcaMaxRobots;
-    if (big && mrca::orca_rings(q.neighbor_dist) == 0)
-        return fail(MRCA_ERR_UNSUPPORTED, "mrca_orca_actions_any: neighbor_dist %g > 19.3 with robots_per_world %d > %d (the search "
-                                          "looks at three rings of 6.5 m cells at most)",
-                    (double)q.neighbor_dist, env->cfg.robots_per_world, mrca::kOrcaMaxRobots);
-    if (big && !env->lidar_hash_current)
-        return fail(MRCA_ERR_INVALID, "mrca_orca_actions_any: the lidar hash does not describe the current poses -- call "
-                                      "mrca_observe_worlds (after mrca_move_worlds) or mrca_reset first (robots_per_world %d > %d)",
-                    env->cfg.robots_per_world, mrca::kOrcaMaxRobots);
-    DeviceGuard guard(env->cfg.device);
-    if (big) mrca::launch_orca_big(env->view, q, mask_dev, actions_dev, vel_dev, static_cast<hipStream_t>(stream));
-    else mrca::launch_orca(env->view, q, mask_dev, actions_dev, vel_dev, static_cast<hipStream_t>(stream));
-    HIP_TRY(hipGetLastError());
-    return MRCA_OK;
-}
-
-static_assert(sizeof(mrca_dwa_params) == sizeof(mrca::DwaParams) && offsetof(mrca_dwa_params, steps) == offsetof(mrca::DwaParams, steps) &&
-                  offsetof(mrca_dwa_params, nw) == offsetof(mrca::DwaParams, nw),
-              "mrca_dwa_params and mrca::DwaParams are one layout");
-
-int mrca_dwa_default_params(mrca_dwa_params* out) {
-    if (!out) return fail(MRCA_ERR_INVALID, "mrca_dwa_default_params: out is NULL");
-    out->radius = 0.35f;            // the footprint's half diagonal 0.2907 m + a margin (as the ORCA baseline)
-    out->horizon = 2.0f;            // (horizon, steps, the weights): tuned on the closed-loop gates, profiles/dwa/defaults.txt
-    out->obst_dist = 3.0f;
-    out->clear_cap = 1.0f;
-    out->max_speed = 1.0f;
-    out->max_omega = 1.0f;
-    out->acc_v = 10.0f;             // the env has no acceleration limit: one tick of these reaches the whole range
-    out->acc_w = 20.0f;
-    out->w_goal = 1.0f;
-    out->w_heading = 0.0f;          // (any weight here makes robots that meet head-on stop and face each other)
-    out->w_clear = 0.2f;
-    out->w_speed = 0.3f;
-    out->steps = 10;
-    out->nv = 5;
-    out->nw = 21;
-    return MRCA_OK;
-}
-
-int mrca_dwa_actions(mrca_env* env, const mrca_dwa_params* params, const uint8_t* mask_dev, float* actions_dev, int32_t* choice_dev,
-                     float* score_dev, void* stream) {
-    // everything that can be judged without the env, then the env
-    mrca_dwa_params p;
-    if (params) p = *params;
-    else mrca_dwa_default_params(&p);
-    const float fl[12] = {p.radius, p.horizon, p.obst_dist, p.clear_cap, p.max_speed, p.max_omega, p.acc_v, p.acc_w, p.w_goal, p.w_heading,
-                          p.w_clear, p.w_speed};
-    static const char* const names[12] = {"radius", "horizon", "obst_dist", "clear_cap", "max_speed", "max_omega", "acc_v", "acc_w",
-                                          "w_goal", "w_heading", "w_clear", "w_speed"};
-    for (int i = 0; i < 12; ++i)
-        if (!std::isfinite(fl[i])) return fail(MRCA_ERR_INVALID, "mrca_dwa_actions: %s is not finite", names[i]);
-    for (int i : {0, 1, 3, 4, 5})
-        if (!(fl[i] > 0.0f)) return fail(MRCA_ERR_INVALID, "mrca_dwa_actions: %s must be > 0", names[i]);
-    if (!(p.max_speed <= 1.0f)) return fail(MRCA_ERR_INVALID, "mrca_dwa_actions: max_speed must be <= 1");
-    if (!(p.max_omega <= 1.0f)) return fail(MRCA_ERR_INVALID, "mrca_dwa_actions: max_omega must be <= 1");
-    if (!(p.obst_dist >= 0.0f && p.obst_dist <= 6.0f)) return fail(MRCA_ERR_INVALID, "mrca_dwa_actions: obst_dist outside [0, 6]");
-    for (int i = 6; i < 12; ++i)
-        if (!(fl[i] >= 0.0f)) return fail(MRCA_ERR_INVALID, "mrca_dwa_actions: %s must be >= 0", names[i]);
-    if (p.steps < 1 || p.steps > mrca::kDwaMaxSteps)
-        return fail(MRCA_ERR_INVALID, "mrca_dwa_actions: steps %d outside 1..%d", p.steps, mrca::kDwaMaxSteps);
-    if (p.nv < 1 || p.nv > mrca::kDwaMaxNv) return fail(MRCA_ERR_INVALID, "mrca_dwa_actions: nv %d outside 1..%d", p.nv, mrca::kDwaMaxNv);
-    if (p.nw < 1 || p.nw > mrca::kDwaMaxNw) return fail(MRCA_ERR_INVALID, "mrca_dwa_actions: nw %d outside 1..%d", p.nw, mrca::kDwaMaxNw);
-    if (!actions_dev) return fail(MRCA_ERR_INVALID, "mrca_dwa_actions: actions_dev is NULL");
-    if (reinterpret_cast<uintptr_t>(actions_dev) % 8) return fail(MRCA_ERR_INVALID, "mrca_dwa_actions: actions_dev must be 8-byte aligned");
-    if (reinterpret_cast<uintptr_t>(choice_dev) % 4) return fail(MRCA_ERR_INVALID, "mrca_dwa_actions: choice_dev must be 4-byte aligned");
-    if (reinterpret_cast<uintptr_t>(score_dev) % 4) return fail(MRCA_ERR_INVALID, "mrca_dwa_actions: score_dev must be 4-byte aligned");
-    if (!env) return fail(MRCA_ERR_INVALID, "env is NULL");
-    mrca::DwaParams q;
-    static_assert(std::is_trivially_copyable<mrca::DwaParams>::value, "");
-    memcpy(&q, &p, sizeof q);
-    DeviceGuard guard(env->cfg.device);
-    mrca::launch_dwa(env->view, q, mask_dev, actions_dev, choice_dev, score_dev, static_cast<hipStream_t>(stream));
-    HIP_TRY(hipGetLastError());
-    return MRCA_OK;
-}
-
-static_assert(sizeof(mrca_scan_noise_params) == sizeof(mrca::ScanNoiseParams) &&
-                  offsetof(mrca_scan_noise_params, quantum) == offsetof(mrca::ScanNoiseParams, quantum),
-              "mrca_scan_noise_params and mrca::ScanNoiseParams are one layout");
-
-int mrca_scan_noise_default_params(mrca_scan_noise_params* out) {
-    if (!out) return fail(MRCA_ERR_INVALID, "mrca_scan_noise_default_params: out is NULL");
-    // a small indoor lidar's order of magnitude (a centimetre, a percent of the range, one beam in two hundred lost), NOT the
-    // reference's: Stage is configured without ranger noise
-    out->sigma_const = 0.01f;
-    out->sigma_prop = 0.01f;
-    out->dropout = 0.005f;
-    out->quantum = 0.0f;
-    return MRCA_OK;
-}
-
-int mrca_scan_noise(mrca_env* env, const mrca_scan_noise_params* params, const uint8_t* mask_dev, void* stream) {
-    // everything that can be judged without the env, then the env
-    mrca_scan_noise_params p;
-    if (params) p = *params;
-    else mrca_scan_noise_default_params(&p);
-    const float fl[4] = {p.sigma_const, p.sigma_prop, p.dropout, p.quantum};
-    static const char* const names[4] = {"sigma_const", "sigma_prop", "dropout", "quantum"};
-    static const float upper[4] = {6.0f, 1.0f, 1.0f, 1.0f};
-    for (int i = 0; i < 4; ++i)
-        if (!std::isfinite(fl[i])) return fail(MRCA_ERR_INVALID, "mrca_scan_noise: %s is not finite", names[i]);
-    for (int i = 0; i < 4; ++i)
-        if (!(fl[i] >= 0.0f && fl[i] <= upper[i]))
-            return fail(MRCA_ERR_INVALID, "mrca_scan_noise: %s outside [0, %g]", names[i], (double)upper[i]);
-    if (!env) return fail(MRCA_ERR_INVALID, "env is NULL");
-    if (!env->reset_seen) return fail(MRCA_ERR_INVALID, "mrca_scan_noise before the first mrca_reset: there is no scan yet");
-    if (p.sigma_const == 0.0f && p.sigma_prop == 0.0f && p.dropout == 0.0f && p.quantum == 0.0f) return MRCA_OK;   // nothing to do
-    mrca::ScanNoiseParams q;
-    static_assert(std::is_trivially_copyable<mrca::ScanNoiseParams>::value, "");
-    memcpy(&q, &p, sizeof q);
-    DeviceGuard guard(env->cfg.device);
-    mrca::launch_scan_noise(env->view, q, mask_dev, env->cfg.lazy_obs ? 0 : (MRCA_VIEW_SCAN | MRCA_VIEW_OBS), static_cast<hipStream_t>(stream));
-    HIP_TRY(hipGetLastError());
-    return MRCA_OK;
-}
-
-static_assert(sizeof(mrca_hybrid_params) == sizeof(mrca::HybridParams) &&
-                  offsetof(mrca_hybrid_params, max_speed) == offsetof(mrca::HybridParams, max_speed),
-              "mrca_hybrid_params and mrca::HybridParams are one layout");
-
-int mrca_hybrid_default_params(mrca_hybrid_params* out) {
-    if (!out) return fail(MRCA_ERR_INVALID, "mrca_hybrid_default_params: out is NULL");
-    // (safe_scale, corridor, look): tuned on the closed-loop circles, profiles/hybrid/defaults.txt
-    out->risk_dist = 0.6f;
-    out->stop_dist = 0.3f;          // (the footprint's half diagonal is 0.2907 m)
-    out->safe_scale = 0.75f;
-    out->corridor = 1.0f;
-    out->look = 6.0f;               // as far as the lidar sees
-    out->front_cos = 0.5f;          // the front 120 degrees
-    out->v_pid = 1.0f;
-    out->k_omega = 6.0f;            // ORCA's
-    out->max_speed = 1.0f;
-    return MRCA_OK;
-}
-
-// the table of mrca_hybrid_params, for `who` (mrca_hybrid_actions, mrca_hybrid_plan): MRCA_OK or the failure
-static int check_hybrid_params(const char* who, const mrca_hybrid_params& p) {
-    const float fl[9] = {p.risk_dist, p.stop_dist, p.safe_scale, p.corridor, p.look, p.front_cos, p.v_pid, p.k_omega, p.max_speed};
-    static const char* const names[9] = {"risk_dist", "stop_dist", "safe_scale", "corridor", "look", "front_cos", "v_pid", "k_omega",
-                                         "max_speed"};
-    for (int i = 0; i < 9; ++i)
-        if (!std::isfinite(fl[i])) return fail(MRCA_ERR_INVALID, "%s: %s is not finite", who, names[i]);
-    if (!(p.stop_dist >= 0.0f)) return fail(MRCA_ERR_INVALID, "%s: stop_dist must be >= 0", who);
-    if (!(p.stop_dist < p.risk_dist)) return fail(MRCA_ERR_INVALID, "%s: risk_dist must be > stop_dist", who);
-    if (!(p.risk_dist <= 6.0f)) return fail(MRCA_ERR_INVALID, "%s: risk_dist must be <= 6", who);
-    if (!(p.safe_scale >= 0.0f && p.safe_scale <= 1.0f)) return fail(MRCA_ERR_INVALID, "%s: safe_scale outside [0, 1]", who);
-    if (!(p.corridor > 0.0f)) return fail(MRCA_ERR_INVALID, "%s: corridor must be > 0", who);
-    if (!(p.look > 0.0f && p.look <= 6.0f)) return fail(MRCA_ERR_INVALID, "%s: look outside (0, 6]", who);
-    if (!(p.front_cos >= -1.0f && p.front_cos <= 1.0f)) return fail(MRCA_ERR_INVALID, "%s: front_cos outside [-1, 1]", who);
-    if (!(p.v_pid > 0.0f)) return fail(MRCA_ERR_INVALID, "%s: v_pid must be > 0", who);
-    if (!(p.k_omega >= 0.0f)) return fail(MRCA_ERR_INVALID, "%s: k_omega must be >= 0", who);
-    if (!(p.max_speed > 0.0f && p.max_speed <= 1.0f)) return fail(MRCA_ERR_INVALID, "%s: max_speed outside (0, 1]", who);
-    return MRCA_OK;
-}
-
-int mrca_hybrid_actions(mrca_env* env, const mrca_hybrid_params* params, const uint8_t* mask_dev, const float* policy_dev,
-                        float* actions_dev, int32_t* mode_dev, float* clear_dev, void* stream) {
-    // everything that can be judged without the env, then the env
-    mrca_hybrid_params p;
-    if (params) p = *params;
-    else mrca_hybrid_default_params(&p);
-    if (const int rc = check_hybrid_params("mrca_hybrid_actions", p)) return rc;
-    if (!policy_dev) return fail(MRCA_ERR_INVALID, "mrca_hybrid_actions: policy_dev is NULL");
-    if (reinterpret_cast<uintptr_t>(policy_dev) % 4) return fail(MRCA_ERR_INVALID, "mrca_hybrid_actions: policy_dev must be 4-byte aligned");
-    if (!actions_dev) return fail(MRCA_ERR_INVALID, "mrca_hybrid_actions: actions_dev is NULL");
-    if (reinterpret_cast<uintptr_t>(actions_dev) % 8) return fail(MRCA_ERR_INVALID, "mrca_hybrid_actions: actions_dev must be 8-byte aligned");
-    if (reinterpret_cast<uintptr_t>(mode_dev) % 4) return fail(MRCA_ERR_INVALID, "mrca_hybrid_actions: mode_dev must be 4-byte aligned");
-    if (reinterpret_cast<uintptr_t>(clear_dev) % 4) return fail(MRCA_ERR_INVALID, "mrca_hybrid_actions: clear_dev must be 4-byte aligned");
-    if (!env) return fail(MRCA_ERR_INVALID, "env is NULL");
-    if (!env->reset_seen) return fail(MRCA_ERR_INVALID, "mrca_hybrid_actions before the first mrca_reset: there is no scan yet");
-    mrca::HybridParams q;
-    static_assert(std::is_trivially_copyable<mrca::HybridParams>::value, "");
-    memcpy(&q, &p, sizeof q);
-    DeviceGuard guard(env->cfg.device);
-    mrca::launch_hybrid(env->view, q, mask_dev, policy_dev, actions_dev, mode_dev, clear_dev, static_cast<hipStream_t>(stream));
-    HIP_TRY(hipGetLastError());
-    return MRCA_OK;
-}
-
-static_assert(sizeof(mrca_safe_policy_params) == sizeof(mrca::SafeParams) &&
-                  offsetof(mrca_safe_policy_params, v_cap) == offsetof(mrca::SafeParams, v_cap),
-              "mrca_safe_policy_params and mrca::SafeParams are one layout");
-
-int mrca_safe_policy_default_params(mrca_safe_policy_params* out) {
-    if (!out) return fail(MRCA_ERR_INVALID, "mrca_safe_policy_default_params: out is NULL");
-    // tuned on the closed-loop circles, profiles/safe_policy/defaults.txt
-    out->scan_scale = 0.3f;
-    out->v_cap = 0.75f;
-    return MRCA_OK;
-}
-
-// the table of mrca_safe_policy_params, for `who`
-static int check_safe_params(const char* who, const mrca_safe_policy_params& p) {
-    if (!std::isfinite(p.scan_scale)) return fail(MRCA_ERR_INVALID, "%s: scan_scale is not finite", who);
-    if (!std::isfinite(p.v_cap)) return fail(MRCA_ERR_INVALID, "%s: v_cap is not finite", who);
-    if (!(p.scan_scale > 0.0f && p.scan_scale <= 1.0f)) return fail(MRCA_ERR_INVALID, "%s: scan_scale outside (0, 1]", who);
-    if (!(p.v_cap > 0.0f && p.v_cap <= 1.0f)) return fail(MRCA_ERR_INVALID, "%s: v_cap outside (0, 1]", who);
-    return MRCA_OK;
-}
-
-int mrca_hybrid_plan(mrca_env* env, const mrca_hybrid_params* hybrid_params, const mrca_safe_policy_params* safe_params,
-                     const uint8_t* mask_dev, int32_t* mode_dev, float* scale_dev, float* pid_dev, float* clear_dev, void* stream) {
-    // everything that can be judged without the env, then the env
-    mrca_hybrid_params p;
-    if (hybrid_params) p = *hybrid_params;
-    else mrca_hybrid_default_params(&p);
-    if (const int rc = check_hybrid_params("mrca_hybrid_plan", p)) return rc;
-    mrca_safe_policy_params sp;
-    if (safe_params) sp = *safe_params;
-    else mrca_safe_policy_default_params(&sp);
-    if (const int rc = check_safe_params("mrca_hybrid_plan", sp)) return rc;
-    if (!mode_dev) return fail(MRCA_ERR_INVALID, "mrca_hybrid_plan: mode_dev is NULL");
-    if (reinterpret_cast<uintptr_t>(mode_dev) % 4) return fail(MRCA_ERR_INVALID, "mrca_hybrid_plan: mode_dev must be 4-byte aligned");
-    if (!scale_dev) return fail(MRCA_ERR_INVALID, "mrca_hybrid_plan: scale_dev is NULL");
-    if (reinterpret_cast<uintptr_t>(scale_dev) % 4) return fail(MRCA_ERR_INVALID, "mrca_hybrid_plan: scale_dev must be 4-byte aligned");
-    if (!pid_dev) return fail(MRCA_ERR_INVALID, "mrca_hybrid_plan: pid_dev is NULL");
-    if (reinterpret_cast<uintptr_t>(pid_dev) % 8) return fail(MRCA_ERR_INVALID, "mrca_hybrid_plan: pid_dev must be 8-byte aligned");
-    if (reinterpret_cast<uintptr_t>(clear_dev) % 4) return fail(MRCA_ERR_INVALID, "mrca_hybrid_plan: clear_dev must be 4-byte aligned");
-    if (!env) return fail(MRCA_ERR_INVALID, "env is NULL");
-    if (!env->reset_seen) return fail(MRCA_ERR_INVALID, "mrca_hybrid_plan before the first mrca_reset: there is no scan yet");
-    mrca::HybridParams q;
-    mrca::SafeParams sq;
-    static_assert(std::is_trivially_copyable<mrca::SafeParams>::value, "");
-    memcpy(&q, &p, sizeof q);
-    memcpy(&sq, &sp, sizeof sq);
-    DeviceGuard guard(env->cfg.device);
-    mrca::launch_hybrid_plan(env->view, q, sq, mask_dev, mode_dev, scale_dev, pid_dev, clear_dev, static_cast<hipStream_t>(stream));
-    HIP_TRY(hipGetLastError());
-    return MRCA_OK;
-}
-
-int mrca_hybrid_commit(int32_t n_robots, const mrca_safe_policy_params* safe_params, const uint8_t* mask_dev, const int32_t* mode_dev,
-                       const float* pid_dev, const float* policy_dev, float* actions_dev, void* stream) {
-    mrca_safe_policy_params sp;
-    if (safe_params) sp = *safe_params;
-    else mrca_safe_policy_default_params(&sp);
-    if (const int rc = check_safe_params("mrca_hybrid_commit", sp)) return rc;
-    if (n_robots < 1) return fail(MRCA_ERR_INVALID, "mrca_hybrid_commit: n_robots %d (needs >= 1)", n_robots);
-    if (!mode_dev) return fail(MRCA_ERR_INVALID, "mrca_hybrid_commit: mode_dev is NULL");
-    if (reinterpret_cast<uintptr_t>(mode_dev) % 4) return fail(MRCA_ERR_INVALID, "mrca_hybrid_commit: mode_dev must be 4-byte aligned");
-    if (!pid_dev) return fail(MRCA_ERR_INVALID, "mrca_hybrid_commit: pid_dev is NULL");
-    if (reinterpret_cast<uintptr_t>(pid_dev) % 8) return fail(MRCA_ERR_INVALID, "mrca_hybrid_commit: pid_dev must be 8-byte aligned");
-    if (!policy_dev) return fail(MRCA_ERR_INVALID, "mrca_hybrid_commit: policy_dev is NULL");
-    if (reinterpret_cast<uintptr_t>(policy_dev) % 4) return fail(MRCA_ERR_INVALID, "mrca_hybrid_commit: policy_dev must be 4-byte aligned");
-    if (!actions_dev) return fail(MRCA_ERR_INVALID, "mrca_hybrid_commit: actions_dev is NULL");
-    if (reinterpret_cast<uintptr_t>(actions_dev) % 8) return fail(MRCA_ERR_INVALID, "mrca_hybrid_commit: actions_dev must be 8-byte aligned");
-    mrca::SafeParams sq;
-    memcpy(&sq, &sp, sizeof sq);
-    DeviceGuard guard(mrca::device_of(actions_dev));     // launch where the buffers live
-    mrca::launch_hybrid_commit(n_robots, sq, mask_dev, mode_dev, pid_dev, policy_dev, actions_dev, static_cast<hipStream_t>(stream));
-    HIP_TRY(hipGetLastError());
-    return MRCA_OK;
-}
-
-static_assert(sizeof(mrca_planner_params) == sizeof(mrca::PlannerParams) &&
-                  offsetof(mrca_planner_params, max_rounds) == offsetof(mrca::PlannerParams, max_rounds),
-              "mrca_planner_params and mrca::PlannerParams are one layout");
-
-int mrca_planner_default_params(mrca_planner_params* out) {
-    if (!out) return fail(MRCA_ERR_INVALID, "mrca_planner_default_params: out is NULL");
-    out->stride = 2;        // 0.1 m planning cells on the shipped 0.05 m maps
-    out->inflate = 7;       // 0.35 m: the footprint's half diagonal (0.29 m) and a cell of slack
-    out->lookahead = 15;    // 1.5 m down the path
-    out->max_rounds = 0;    // the bound of mrca_planner_device.h (plan_round_bound)
-    return MRCA_OK;
-}
-
-// the table of mrca_planner_params, for `who`: *q = the params to use (NULL: the defaults), MRCA_OK or the failure
-static int check_planner_params(const char* who, const mrca_planner_params* params, mrca::PlannerParams* q) {
-    mrca_planner_params p;
-    if (params) p = *params;
-    else mrca_planner_default_params(&p);
-    if (p.stride < 1 || p.stride > mrca::kPlanMaxStride) return fail(MRCA_ERR_INVALID, "%s: stride %d outside 1..%d", who, p.stride, mrca::kPlanMaxStride);
-    if (p.inflate < 0 || p.inflate > mrca::kPlanMaxInflate)
-        return fail(MRCA_ERR_INVALID, "%s: inflate %d outside 0..%d", who, p.inflate, mrca::kPlanMaxInflate);
-    if (p.lookahead < 1 || p.lookahead > mrca::kPlanMaxLookahead)
-        return fail(MRCA_ERR_INVALID, "%s: lookahead %d outside 1..%d", who, p.lookahead, mrca::kPlanMaxLookahead);
-    if (p.max_rounds < 0) return fail(MRCA_ERR_INVALID, "%s: max_rounds %d is negative", who, p.max_rounds);
-    static_assert(std::is_trivially_copyable<mrca::PlannerParams>::value, "");
-    memcpy(q, &p, sizeof *q);
-    return MRCA_OK;
-}
-
-int mrca_planner_grid(mrca_env* env, const mrca_planner_params* params, int32_t* pw_out, int32_t* ph_out) {
-    mrca::PlannerParams q;
-    if (const int rc = check_planner_params("mrca_planner_grid", params, &q)) return rc;
-    if (!pw_out || !ph_out) return fail(MRCA_ERR_INVALID, "mrca_planner_grid: pw_out / ph_out is NULL");
-    if (!env) return fail(MRCA_ERR_INVALID, "env is NULL");
-    *pw_out = mrca::plan_cells(env->view.g.width, q.stride);
-    *ph_out = mrca::plan_cells(env->view.g.height, q.stride);
-    return MRCA_OK;
-}
-
-int mrca_goal_fields(mrca_env* env, const mrca_planner_params* params, const float* goals_dev, int32_t G, uint32_t* field_dev,
-                     int32_t* rounds_out, void* stream) {
-    // everything that can be judged without the env, then the env
-    mrca::PlannerParams q;
-    if (const int rc = check_planner_params("mrca_goal_fields", params, &q)) return rc;
-    if (G < 1 || G > mrca::kPlanMaxGoals) return fail(MRCA_ERR_INVALID, "mrca_goal_fields: G %d outside 1..%d", G, mrca::kPlanMaxGoals);
-    if (!goals_dev) return fail(MRCA_ERR_INVALID, "mrca_goal_fields: goals_dev is NULL");
-    if (reinterpret_cast<uintptr_t>(goals_dev) % 4) return fail(MRCA_ERR_INVALID, "mrca_goal_fields: goals_dev must be 4-byte aligned");
-    if (!field_dev) return fail(MRCA_ERR_INVALID, "mrca_goal_fields: field_dev is NULL");
-    if (reinterpret_cast<uintptr_t>(field_dev) % 4) return fail(MRCA_ERR_INVALID, "mrca_goal_fields: field_dev must be 4-byte aligned");
-    if (!env) return fail(MRCA_ERR_INVALID, "env is NULL");
-    if (!env->reset_seen) return fail(MRCA_ERR_INVALID, "mrca_goal_fields before the first mrca_reset");
-    DeviceGuard guard(env->cfg.device);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (capturing(s))
-        return fail(MRCA_ERR_INVALID, "mrca_goal_fields inside a stream capture: it synchronises the stream while it looks for convergence");
-    constexpr int kEvery = 4;     // the counters are read every kEvery launches, each launch has its own
-    if (!env->plan_counters) HIP_TRY(device_alloc(&env->plan_counters, kEvery * sizeof(uint32_t)));
-    uint32_t* counters = env->plan_counters.get();
-    const int pw = mrca::plan_cells(env->view.g.width, q.stride), ph = mrca::plan_cells(env->view.g.height, q.stride);
-    const int64_t bound = q.max_rounds > 0 ? (int64_t)q.max_rounds : mrca::plan_round_bound(pw, ph);
-    HIP_TRY(hipMemsetAsync(counters, 0, kEvery * sizeof(uint32_t), s));
-    mrca::launch_goal_field_init(env->view, q, goals_dev, G, field_dev, s);
-    HIP_TRY(hipGetLastError());
-    int64_t quiet = -1;           // the first launch in which nothing fell
-    for (int64_t base = 0; base < bound && quiet < 0; base += kEvery) {
-        const int nb = (int)std::min<int64_t>(kEvery, bound - base);
-        for (int r = 0; r < nb; ++r) mrca::launch_goal_field_round(env->view, q, G, field_dev, counters + r, s);
-        HIP_TRY(hipGetLastError());
-        uint32_t seen[kEvery] = {0, 0, 0, 0};
-        HIP_TRY(hipMemcpyAsync(seen, counters, sizeof seen, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemsetAsync(counters, 0, sizeof seen, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        for (int r = nb - 1; r >= 0; --r)
-            if (seen[r] == 0) quiet = base + r;
-    }
-    mrca::launch_goal_field_finish(env->view, q, G, field_dev, s);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(s));
-    if (rounds_out) *rounds_out = (int32_t)std::min<int64_t>(quiet >= 0 ? quiet : bound, INT32_MAX);
-    if (quiet < 0)
-        return fail(MRCA_ERR_UNSUPPORTED, "mrca_goal_fields: not converged within max_rounds = %lld launches (the field holds upper bounds)",
-                    (long long)bound);
-    return MRCA_OK;
-}
-
-int mrca_subgoals(mrca_env* env, const mrca_planner_params* params, const uint32_t* field_dev, const float* goals_dev, int32_t G,
-                  const int32_t* slot_dev, const uint8_t* mask_dev, float* local_dev, float* subgoal_dev, float* dist_dev,
-                  int32_t* status_dev, void* stream) {
-    // everything that can be judged without the env, then the env
-    mrca::PlannerParams q;
-    if (const int rc = check_planner_params("mrca_subgoals", params, &q)) return rc;
-    if (G < 1 || G > mrca::kPlanMaxGoals) return fail(MRCA_ERR_INVALID, "mrca_subgoals: G %d outside 1..%d", G, mrca::kPlanMaxGoals);
-    if (!field_dev) return fail(MRCA_ERR_INVALID, "mrca_subgoals: field_dev is NULL");
-    if (reinterpret_cast<uintptr_t>(field_dev) % 4) return fail(MRCA_ERR_INVALID, "mrca_subgoals: field_dev must be 4-byte aligned");
-    if (!goals_dev) return fail(MRCA_ERR_INVALID, "mrca_subgoals: goals_dev is NULL");
-    if (reinterpret_cast<uintptr_t>(goals_dev) % 4) return fail(MRCA_ERR_INVALID, "mrca_subgoals: goals_dev must be 4-byte aligned");
-    if (reinterpret_cast<uintptr_t>(slot_dev) % 4) return fail(MRCA_ERR_INVALID, "mrca_subgoals: slot_dev must be 4-byte aligned");
-    if (!local_dev) return fail(MRCA_ERR_INVALID, "mrca_subgoals: local_dev is NULL");
-    if (reinterpret_cast<uintptr_t>(local_dev) % 8) return fail(MRCA_ERR_INVALID, "mrca_subgoals: local_dev must be 8-byte aligned");
-    if (reinterpret_cast<uintptr_t>(subgoal_dev) % 4) return fail(MRCA_ERR_INVALID, "mrca_subgoals: subgoal_dev must be 4-byte aligned");
-    if (reinterpret_cast<uintptr_t>(dist_dev) % 4) return fail(MRCA_ERR_INVALID, "mrca_subgoals: dist_dev must be 4-byte aligned");
-    if (reinterpret_cast<uintptr_t>(status_dev) % 4) return fail(MRCA_ERR_INVALID, "mrca_subgoals: status_dev must be 4-byte aligned");
-    if (!env) return fail(MRCA_ERR_INVALID, "env is NULL");
-    if (!slot_dev && G != env->cfg.robots_per_world)
-        return fail(MRCA_ERR_INVALID, "mrca_subgoals: slot_dev NULL (slot = n %% robots_per_world) needs G == robots_per_world (%d), got %d",
-                    env->cfg.robots_per_world, G);
-    if (!env->reset_seen) return fail(MRCA_ERR_INVALID, "mrca_subgoals before the first mrca_reset: there is no head record yet");
-    // (a measurement switch, tools/planner_probe.py: a robot per thread in place of eight lanes per robot -- the same outputs)
-    static const int lanes = [] {
-        const char* v = getenv("MRCA_SUBGOAL_LANES");
-        return (v && v[0] == '1' && !v[1]) ? 1 : 8;
-    }();
-    DeviceGuard guard(env->cfg.device);
-    mrca::launch_subgoals(env->view, q, field_dev, goals_dev, G, slot_dev, mask_dev, local_dev, subgoal_dev, dist_dev, status_dev, lanes,
-                          static_cast<hipStream_t>(stream));
     HIP_TRY(hipGetLastError());
     return MRCA_OK;
 }

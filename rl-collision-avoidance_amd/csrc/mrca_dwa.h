@@ -1,4 +1,4 @@
-// mrca_dwa.h -- launch interface of the DWA baseline controller (mrca_dwa.hip) for the C ABI (mrca_abi.hip: mrca_dwa_actions).
+// mrca_dwa.h -- launch interface of the DWA baseline controller (mrca_dwa.hip) for the C ABI (mrca_abi_controllers.hip: mrca_dwa_actions).
 #pragma once
 #include "mrca_kernels.h"
 #include "mrca_dwa_device.h"

@@ -1,5 +1,5 @@
 // mrca_hostutil.h -- host-side helpers shared by the translation units of libmrca_env.so (mrca_abi.hip,
-// mrca_policy.hip, mrca_policy_bwd.hip): the error string behind mrca_last_error(), and running a launch on the device
+// mrca_abi_controllers.hip, mrca_policy.hip, mrca_policy_bwd.hip): the error string behind mrca_last_error(), and running a launch on the device
 // its buffers live on whatever the caller's current device is.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -1,4 +1,4 @@
-// mrca_hybrid.h -- launch interface of the hybrid control wrapper (mrca_hybrid.hip) for the C ABI (mrca_abi.hip: mrca_hybrid_actions).
+// mrca_hybrid.h -- launch interface of the hybrid control wrapper (mrca_hybrid.hip) for the C ABI (mrca_abi_controllers.hip: mrca_hybrid_actions).
 #pragma once
 #include "mrca_kernels.h"
 #include "mrca_hybrid_device.h"

@@ -1,4 +1,4 @@
-// mrca_noise.h -- launch interface of the lidar noise model (mrca_noise.hip) for the C ABI (mrca_abi.hip: mrca_scan_noise).
+// mrca_noise.h -- launch interface of the lidar noise model (mrca_noise.hip) for the C ABI (mrca_abi_controllers.hip: mrca_scan_noise).
 #pragma once
 #include "mrca_kernels.h"
 #include "mrca_noise_device.h"

@@ -1,4 +1,4 @@
-// mrca_orca.h -- launch interface of the ORCA baseline controller (mrca_orca.hip) for the C ABI (mrca_abi.hip: mrca_orca_actions).
+// mrca_orca.h -- launch interface of the ORCA baseline controller (mrca_orca.hip) for the C ABI (mrca_abi_controllers.hip: mrca_orca_actions).
 #pragma once
 #include "mrca_kernels.h"
 #include "mrca_orca_device.h"

@@ -1,4 +1,4 @@
-// mrca_planner.h -- launch interface of the global planner (mrca_planner.hip) for the C ABI (mrca_abi.hip: mrca_goal_fields,
+// mrca_planner.h -- launch interface of the global planner (mrca_planner.hip) for the C ABI (mrca_abi_controllers.hip: mrca_goal_fields,
 // mrca_subgoals).
 #pragma once
 #include "mrca_kernels.h"

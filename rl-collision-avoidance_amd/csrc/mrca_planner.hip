@@ -10,7 +10,7 @@
 // halo word read while its owner lowers it is an older upper bound; lanes of the workgroup read LDS words their neighbours are
 // lowering in the same sweep, likewise.  A workgroup in which something fell, or whose sweeps ran out, adds one to the round's
 // counter.  There is no grid-wide barrier, no cooperative launch, no wait on memory: the host relaunches and reads counters
-// (mrca_abi.hip).  Every loop has a fixed trip count.
+// (mrca_abi_controllers.hip: mrca_goal_fields).  Every loop has a fixed trip count.
 //
 // PER TICK (subgoal_kernel).  EIGHT LANES PER ROBOT: lane k loads D of neighbour k -- the eight loads of a step are one
 // instruction -- takes the two cells a diagonal squeezes between from the lanes beside it, and three butterfly steps over a

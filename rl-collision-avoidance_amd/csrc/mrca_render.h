@@ -1,4 +1,4 @@
-// mrca_render.h -- launch interface of the top-down renderer (mrca_render.hip) for the C ABI (mrca_abi.hip: mrca_render).
+// mrca_render.h -- launch interface of the top-down renderer (mrca_render.hip) for the C ABI (mrca_abi_controllers.hip: mrca_render).
 #pragma once
 #include "mrca_kernels.h"
 #include "mrca_render_device.h"

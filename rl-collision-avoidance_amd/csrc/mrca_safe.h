@@ -1,4 +1,4 @@
-// mrca_safe.h -- launch interface of hybrid control in the paper's form (mrca_safe.hip) for the C ABI (mrca_abi.hip:
+// mrca_safe.h -- launch interface of hybrid control in the paper's form (mrca_safe.hip) for the C ABI (mrca_abi_controllers.hip:
 // mrca_hybrid_plan, mrca_hybrid_commit).
 #pragma once
 #include "mrca_kernels.h"

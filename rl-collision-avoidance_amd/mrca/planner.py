@@ -1,42 +1,24 @@
 """The global planner's Python side (include/mrca_env.h: mrca_planner_params, mrca_goal_fields, mrca_subgoals).  The defaults are
 the library's own (mrca_planner_default_params): they are stated once, in C."""
-import ctypes as C
 import dataclasses
 import math
 
 from . import _lib
-
-_FIELDS = [name for name, _t in _lib.PlannerParamsStruct._fields_]
+from .params import ParamsMirror
 
 INF = 0xFFFFFFFF                 # a field word: blocked, or no path
 ON_GOAL, ON_PATH, NO_SLOT, NO_PATH = 1, 0, -1, -2
 STATUS_NAMES = {ON_GOAL: "on_goal", ON_PATH: "on_path", NO_SLOT: "no_slot", NO_PATH: "no_path"}
 
 
-def _library_defaults():
-    st = _lib.PlannerParamsStruct()
-    _lib.check(_lib.load().mrca_planner_default_params(C.byref(st)), "mrca_planner_default_params")
-    return {k: getattr(st, k) for k in _FIELDS}
-
-
 @dataclasses.dataclass
-class PlannerParams:
+class PlannerParams(ParamsMirror):
     """Mirror of mrca_planner_params; a field left ``None`` takes the library's default."""
+    _STRUCT, _DEFAULTS, _FLAG = _lib.PlannerParamsStruct, "mrca_planner_default_params", "--planner-param"
     stride: int = None                  # map cells per planning cell and axis, 1..8
     inflate: int = None                 # obstacles are grown by this many map cells, 0..64
     lookahead: int = None               # steps of the walk down the field, 1..256
     max_rounds: int = None              # at most this many relaxation launches; 0 = the library's derived bound
-
-    def __post_init__(self):
-        for k, v in _library_defaults().items():
-            if getattr(self, k) is None:
-                setattr(self, k, v)
-
-    def struct(self):
-        return _lib.PlannerParamsStruct(**{k: int(getattr(self, k)) for k in _FIELDS})
-
-    def as_dict(self):
-        return {k: int(getattr(self, k)) for k in _FIELDS}
 
     @classmethod
     def for_grid(cls, grid, radius=0.35, lookahead_m=1.5, cell_m=0.1, max_rounds=0):
@@ -50,13 +32,7 @@ class PlannerParams:
     @classmethod
     def from_assignments(cls, items, base=None):
         """``["stride=1", "lookahead=20"]`` (the evaluator's --planner-param) on top of ``base`` -> PlannerParams."""
-        kw = {} if base is None else base.as_dict()
-        for it in items or ():
-            k, _eq, v = it.partition("=")
-            if k not in _FIELDS or not _eq:
-                raise ValueError(f"--planner-param {it!r}: expected name=value with name in {_FIELDS}")
-            kw[k] = int(v)
-        return cls(**kw)
+        return super().from_assignments(items, start=base and base.as_dict())
 
 
 @dataclasses.dataclass

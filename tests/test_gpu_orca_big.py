@@ -262,6 +262,10 @@ def test_errors(hip):
         rc = call(env._h, C.byref(st), None, out.data_ptr(), None, env._stream())
         if env is big:
             assert rc == -4 and b"neighbor_dist" in env.lib.mrca_last_error()
+            assert env.lib.mrca_last_error().decode() == "mrca_orca_actions_any: neighbor_dist 19.4 > 19.3 with robots_per_world 66 > 64 " \
+                                                         "(the search looks at three rings of 6.5 m cells at most)"
+            assert env.lib.mrca_orca_actions(env._h, None, None, out.data_ptr(), None, env._stream()) == -4
+            assert env.lib.mrca_last_error().decode() == "mrca_orca_actions: robots_per_world 66 > 64"
             assert not out.any()
             st.neighbor_dist = 19.3
             assert call(env._h, C.byref(st), None, out.data_ptr(), None, env._stream()) == 0
@@ -277,6 +281,8 @@ def test_errors(hip):
     big.move(act, (0, 1))
     rc = big.lib.mrca_orca_actions_any(big._h, None, None, out.data_ptr(), None, big._stream())
     assert rc == -1 and b"mrca_observe_worlds" in big.lib.mrca_last_error()
+    assert big.lib.mrca_last_error().decode() == "mrca_orca_actions_any: the lidar hash does not describe the current poses -- call " \
+                                                 "mrca_observe_worlds (after mrca_move_worlds) or mrca_reset first (robots_per_world 66 > 64)"
     big.check()
     assert not out.any()
     big.observe((0, 1))
