@@ -1,6 +1,6 @@
 // mrca_abi.hip -- host side of include/mrca_env.h: config validation, the SoA device arena,
 // table / map upload, kernel sequencing and optional HIP-event timing.  No torch, no Python.  What an env is made of is in
-// mrca_env_state.h; the entry points of the renderer, the controllers, the noise model and the planner are in
+// mrca_env_state.h, where its memory lies in mrca_arena.h; the entry points of the renderer, the controllers, the noise model and the planner are in
 // mrca_abi_controllers.hip.
 #include <hip/hip_runtime.h>
 #include <string>
@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "../../include/mrca_env.h"
+#include "mrca_arena.h"
 #include "mrca_host.h"
 #include "mrca_hostutil.h"
 #include "mrca_kernels.h"
@@ -47,9 +48,7 @@ namespace {
 
 using mrca::DeviceGuard;
 using mrca::kAheadTicks;
-
-constexpr size_t kAlign = 256;
-size_t align_up(size_t v) { return (v + kAlign - 1) / kAlign * kAlign; }
+namespace arena = mrca::arena;
 
 int validate(const mrca_config* c) {
     if (!c) return fail(MRCA_ERR_INVALID, "config is NULL");
@@ -102,77 +101,6 @@ int validate(const mrca_config* c) {
     return MRCA_OK;
 }
 
-void make_layout(const mrca_config* c, Layout* L) {
-    const size_t N = (size_t)c->num_worlds * c->robots_per_world;
-    const size_t B = c->beams, F = c->frames, R = c->robots_per_world;
-    size_t sz[MRCA_F_COUNT];
-    sz[MRCA_F_POSE] = N * 3 * 4;
-    sz[MRCA_F_SPEED] = N * 2 * 4;
-    sz[MRCA_F_SPEED_GT] = N * 2 * 4;
-    sz[MRCA_F_GOAL] = N * 2 * 4;
-    sz[MRCA_F_INIT_POSE] = N * 3 * 4;
-    sz[MRCA_F_SCAN] = N * B * 4;
-    sz[MRCA_F_OBS] = N * F * B * 4;
-    sz[MRCA_F_LOCAL_GOAL] = N * 2 * 4;
-    sz[MRCA_F_REWARD] = N * 4;
-    sz[MRCA_F_DONE] = N;
-    sz[MRCA_F_RESULT] = N;
-    sz[MRCA_F_FIRST_RESULT] = N;
-    sz[MRCA_F_CRASHED] = N;
-    sz[MRCA_F_LIVE] = N;
-    sz[MRCA_F_FRESH] = N;
-    sz[MRCA_F_T] = N * 4;
-    sz[MRCA_F_EPISODE] = N * 4;
-    sz[MRCA_F_PREV_DIST] = N * 4;
-    sz[MRCA_F_SCAN_RING] = N * F * B * 4;
-    sz[MRCA_F_RING_HEAD] = N;
-    sz[MRCA_F_HIT_BITS] = N * F * (B / 64) * 8;
-    size_t off = 0;
-    for (int f = 0; f < MRCA_F_COUNT; ++f) {
-        L->field_off[f] = off;
-        L->field_bytes[f] = sz[f];
-        off += align_up(sz[f]);
-    }
-    auto take = [&](size_t bytes) {
-        size_t o = off;
-        off += align_up(bytes);
-        return o;
-    };
-    L->off_reset_mode = take(R * 4);
-    L->off_goal_mode = take(R * 4);
-    L->off_group_id = take(R * 4);
-    L->off_init_table = take(R * 3 * 4);
-    L->off_goal_table = take(R * 2 * 4);
-    L->off_beam_cos = take(B * 4);
-    L->off_beam_sin = take(B * 4);
-    L->off_map = take((size_t)c->map_height * c->map_words_per_row * 4);
-    L->off_free_rect = take((size_t)(c->map_width + 2 * mrca::kFieldPadX) * (c->map_height + 2 * mrca::kFieldPadY) *
-                            4 * sizeof(uint16_t));
-    L->off_cellfield = take((size_t)c->map_width * c->map_height);
-    L->off_head = take(N * sizeof(float4));
-    L->off_outline = take(c->collision_raster > 0.0f ? N * sizeof(mrca::OutlineBits) : 0);   // fidelity mode only
-    L->bw_cmask = L->bw_lmask = 0;
-    if (c->robots_per_world > 64) {
-        size_t mc = 1, ml = 1;
-        while (mc < 4 * N) mc <<= 1;      // 2N entries (pose at tick start + provisional pose): load factor <= 0.5
-        while (ml < 2 * N) ml <<= 1;
-        L->bw_cmask = (int32_t)(mc - 1);
-        L->bw_lmask = (int32_t)(ml - 1);
-        L->off_bw_ticket = take(4);
-        L->off_bw_prov = take(N * 2 * sizeof(float4));
-        L->off_bw_state = take(N * 4);
-        L->off_bw_chead = take(mc * 4);
-        L->off_bw_cnext = take(2 * N * 4);
-        L->off_bw_lstart = take((ml + 2) * 4);
-        L->off_bw_lcount = take((ml + 1) * 4);
-        L->off_bw_lsorted = take(N * 4);
-        L->off_bw_lblock = take((ml / 1024 + 2) * 4);
-        L->off_bw_lcursor = take((ml + 1) * 4);
-    }
-    L->off_status = take(4);
-    L->total = off;
-}
-
 constexpr int kTimingRing = 1024;
 
 // The free-rectangle field depends on the map only and takes ~1 s of host time for an 800 x 800 map:
@@ -222,15 +150,8 @@ constexpr int kChainStreamsAtCreate = 1;
 // the env's view with slot b's buffers in place of the five fields (b = 0: the env's own)
 static mrca::EnvView slot_view(const mrca_env* env, int b) {
     mrca::EnvView v = env->view;
-    if (b > 0) {
-        const AheadRing& r = env->ahead;
-        char* base = r.mem.get() + (size_t)(b - 1) * r.slot_bytes;
-        v.pose = reinterpret_cast<float*>(base + r.off[0]);
-        v.head = reinterpret_cast<float4*>(base + r.off[1]);
-        v.goal = reinterpret_cast<float*>(base + r.off[2]);
-        v.fresh = reinterpret_cast<uint8_t*>(base + r.off[3]);
-        if (env->view.outline) v.outline = reinterpret_cast<mrca::OutlineBits*>(base + r.off[4]);
-    }
+    const AheadRing& r = env->ahead;
+    if (b > 0) arena::bind_slot(r.slot, r.mem.get() + (size_t)(b - 1) * r.slot.bytes, &v);
     return v;
 }
 
@@ -246,12 +167,13 @@ static mrca::RayTicks slot_ticks(const mrca_env* env, int b, int ticks, bool las
     mrca::RayTicks t{};
     t.ticks = ticks;
     t.last_is_env = last_is_env;
-    t.slot0 = r.mem.get() + (size_t)(b - 1) * r.slot_bytes + r.off[0];
-    t.stride = -(int32_t)r.slot_bytes;
-    t.off_head = (uint32_t)(r.off[1] - r.off[0]);
-    t.in.off_goal = (uint32_t)(r.off[2] - r.off[0]);
-    t.in.off_fresh = (uint32_t)(r.off[3] - r.off[0]);
-    t.in.off_outline = (uint32_t)(r.off[4] - r.off[0]);
+    const size_t* off = r.slot.off;
+    t.slot0 = r.mem.get() + (size_t)(b - 1) * r.slot.bytes + off[arena::kSlotPose];
+    t.stride = -(int32_t)r.slot.bytes;
+    t.off_head = (uint32_t)(off[arena::kSlotHead] - off[arena::kSlotPose]);
+    t.in.off_goal = (uint32_t)(off[arena::kSlotGoal] - off[arena::kSlotPose]);
+    t.in.off_fresh = (uint32_t)(off[arena::kSlotFresh] - off[arena::kSlotPose]);
+    t.in.off_outline = (uint32_t)(off[arena::kSlotOutline] - off[arena::kSlotPose]);
     t.in.head_in = head_in;
     t.in.head_out = head_out;
     return t;
@@ -314,7 +236,7 @@ static int attach_arena(mrca_env* env, void* arena_dev, size_t arena_bytes) {
     const size_t total = env->layout.total;
     if (arena_dev) {
         if (arena_bytes < total) return fail(MRCA_ERR_NOMEM, "arena of %zu bytes < required %zu", arena_bytes, total);
-        if (reinterpret_cast<uintptr_t>(arena_dev) % kAlign) return fail(MRCA_ERR_INVALID, "arena must be %zu-byte aligned", kAlign);
+        if (reinterpret_cast<uintptr_t>(arena_dev) % arena::kAlign) return fail(MRCA_ERR_INVALID, "arena must be %zu-byte aligned", arena::kAlign);
         env->arena = static_cast<char*>(arena_dev);
         return MRCA_OK;
     }
@@ -324,9 +246,16 @@ static int attach_arena(mrca_env* env, void* arena_dev, size_t arena_bytes) {
     return MRCA_OK;
 }
 
-// the arena's contents at construction (tables, poses, beams, map) -> the free-rectangle field's pitch, the robot groups
-static int upload_tables(const mrca_config* cfg, const Layout& L, char* arena, int* free_rect_pitch, int* num_groups_out) {
-    HIP_TRY(hipMemset(arena, 0, L.total));
+// a host array into the part of the arena that a view's pointer is bound to (the tables' pointers are const: kernels only read them)
+template <class T, class U> static hipError_t to_arena(const T* part, const std::vector<U>& src) {
+    return hipMemcpy(const_cast<T*>(part), src.data(), src.size() * sizeof(U), hipMemcpyHostToDevice);
+}
+
+// the arena's contents at construction (tables, poses, beams, map), written through the pointers of the env's view -> the
+// view's free-rectangle pitch and robot groups
+static int upload_tables(const mrca_config* cfg, mrca_env* env) {
+    mrca::EnvView& v = env->view;
+    HIP_TRY(hipMemset(env->arena, 0, env->layout.total));
     const int R = cfg->robots_per_world, B = cfg->beams;
     const size_t N = (size_t)cfg->num_worlds * R;
     // scenario tables
@@ -340,7 +269,7 @@ static int upload_tables(const mrca_config* cfg, const Layout& L, char* arena, i
     if (cfg->goal_table) memcpy(goal_tab.data(), cfg->goal_table, R * 2 * 4);
     int num_groups = 0;
     for (int i = 0; i < R; ++i) num_groups = group[i] + 1 > num_groups ? group[i] + 1 : num_groups;
-    *num_groups_out = num_groups;
+    v.num_groups = num_groups;
     // beam directions: bearing_i = -pi/2 + i*pi/(B-1) (stageros.cpp:495-497), evaluated in
     // double, rounded once to fp32
     std::vector<float> bcos(B), bsin(B);
@@ -349,11 +278,11 @@ static int upload_tables(const mrca_config* cfg, const Layout& L, char* arena, i
         bcos[i] = (float)std::cos(b);
         bsin[i] = (float)std::sin(b);
     }
-    HIP_TRY(hipMemcpy(arena + L.off_reset_mode, reset_mode.data(), R * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(arena + L.off_goal_mode, goal_mode.data(), R * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(arena + L.off_group_id, group.data(), R * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(arena + L.off_init_table, init_tab.data(), R * 3 * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(arena + L.off_goal_table, goal_tab.data(), R * 2 * 4, hipMemcpyHostToDevice));
+    HIP_TRY(to_arena(v.reset_mode, reset_mode));
+    HIP_TRY(to_arena(v.goal_mode, goal_mode));
+    HIP_TRY(to_arena(v.group_id, group));
+    HIP_TRY(to_arena(v.init_table, init_tab));
+    HIP_TRY(to_arena(v.goal_table, goal_tab));
     {
         // before the first reset the robots stand at their table poses (= the agent lines of the world file): a start
         // sampled in Stage-2's region keeps 7 m away from the robot's CURRENT position, its first one included
@@ -361,31 +290,22 @@ static int upload_tables(const mrca_config* cfg, const Layout& L, char* arena, i
         std::vector<float> pose0((size_t)N * 3);
         for (size_t n = 0; n < N; ++n)
             for (int k = 0; k < 3; ++k) pose0[n * 3 + k] = init_tab[(n % (size_t)R) * 3 + k];
-        HIP_TRY(hipMemcpy(arena + L.field_off[MRCA_F_POSE], pose0.data(), pose0.size() * 4, hipMemcpyHostToDevice));
+        HIP_TRY(to_arena(v.pose, pose0));
     }
-    HIP_TRY(hipMemcpy(arena + L.off_beam_cos, bcos.data(), B * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(arena + L.off_beam_sin, bsin.data(), B * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(arena + L.off_map, cfg->map_bits, (size_t)cfg->map_height * cfg->map_words_per_row * 4,
-                      hipMemcpyHostToDevice));
-    {
-        const std::shared_ptr<const HostField> hf = host_field(cfg, false);
-        *free_rect_pitch = hf->pitch;
-        HIP_TRY(hipMemcpy(arena + L.off_free_rect, hf->entries.data(), hf->entries.size() * sizeof(uint16_t),
-                          hipMemcpyHostToDevice));
-    }
-    {
-        std::vector<uint8_t> cf;
-        mrca::build_cell_field(cfg->map_bits, cfg->map_width, cfg->map_height, cfg->map_words_per_row, &cf);
-        HIP_TRY(hipMemcpy(arena + L.off_cellfield, cf.data(), cf.size(), hipMemcpyHostToDevice));
-    }
-    if (R > 64)    // the collision hash starts empty; every tick leaves it empty again (bw_finish_kernel)
-        HIP_TRY(hipMemset(arena + L.off_bw_chead, 0xFF, ((size_t)L.bw_cmask + 1) * 4));
+    HIP_TRY(to_arena(v.beam_cos, bcos));
+    HIP_TRY(to_arena(v.beam_sin, bsin));
+    HIP_TRY(hipMemcpy(const_cast<uint32_t*>(v.map_bits), cfg->map_bits, arena::part_bytes(*cfg, &mrca::EnvView::map_bits), hipMemcpyHostToDevice));
+    const std::shared_ptr<const HostField> hf = host_field(cfg, false);
+    v.free_rect_pitch = hf->pitch;
+    HIP_TRY(to_arena(v.free_rect, hf->entries));
+    std::vector<uint8_t> cf;
+    mrca::build_cell_field(cfg->map_bits, cfg->map_width, cfg->map_height, cfg->map_words_per_row, &cf);
+    HIP_TRY(to_arena(v.cellfield, cf));
+    if (v.big)     // the collision hash starts empty; every tick leaves it empty again (bw_finish_kernel)
+        HIP_TRY(hipMemset(v.bw_chead, 0xFF, arena::part_bytes(*cfg, &mrca::EnvView::bw_chead)));
     // live = 1, t = 1 at construction (a robot exists and is idle before the first reset)
-    HIP_TRY(hipMemset(arena + L.field_off[MRCA_F_LIVE], 1, N));
-    {
-        std::vector<int32_t> ones(N, 1);
-        HIP_TRY(hipMemcpy(arena + L.field_off[MRCA_F_T], ones.data(), N * 4, hipMemcpyHostToDevice));
-    }
+    HIP_TRY(hipMemset(v.live, 1, N));
+    HIP_TRY(to_arena(v.t, std::vector<int32_t>(N, 1)));
     return MRCA_OK;
 }
 
@@ -423,8 +343,9 @@ static int upload_octants(const mrca_config* cfg, mrca_env* env) {
     return MRCA_OK;
 }
 
-// the view of the arena `a` and of the config that every launch takes
-static mrca::EnvView make_view(const mrca_config* cfg, const Layout& L, char* a, int free_rect_pitch, int num_groups) {
+// the view of the arena `a` and of the config that every launch takes (the free-rectangle field's pitch and the robot groups:
+// upload_tables)
+static mrca::EnvView make_view(const mrca_config* cfg, char* a) {
     const int R = cfg->robots_per_world, B = cfg->beams;
     const size_t N = (size_t)cfg->num_worlds * R;
     mrca::EnvView v = mrca::EnvView();
@@ -433,61 +354,13 @@ static mrca::EnvView make_view(const mrca_config* cfg, const Layout& L, char* a,
     v.W = cfg->num_worlds;
     v.B = B;
     v.F = cfg->frames;
-    v.pose = reinterpret_cast<float*>(a + L.field_off[MRCA_F_POSE]);
-    v.speed = reinterpret_cast<float*>(a + L.field_off[MRCA_F_SPEED]);
-    v.speed_gt = reinterpret_cast<float*>(a + L.field_off[MRCA_F_SPEED_GT]);
-    v.goal = reinterpret_cast<float*>(a + L.field_off[MRCA_F_GOAL]);
-    v.init_pose = reinterpret_cast<float*>(a + L.field_off[MRCA_F_INIT_POSE]);
-    v.scan = reinterpret_cast<float*>(a + L.field_off[MRCA_F_SCAN]);
-    v.obs = reinterpret_cast<float*>(a + L.field_off[MRCA_F_OBS]);
-    v.scan_ring = reinterpret_cast<float*>(a + L.field_off[MRCA_F_SCAN_RING]);
-    v.ring_head = reinterpret_cast<uint8_t*>(a + L.field_off[MRCA_F_RING_HEAD]);
-    v.hit_bits = reinterpret_cast<unsigned long long*>(a + L.field_off[MRCA_F_HIT_BITS]);
-    v.local_goal = reinterpret_cast<float*>(a + L.field_off[MRCA_F_LOCAL_GOAL]);
-    v.reward = reinterpret_cast<float*>(a + L.field_off[MRCA_F_REWARD]);
-    v.prev_dist = reinterpret_cast<float*>(a + L.field_off[MRCA_F_PREV_DIST]);
-    v.done = reinterpret_cast<uint8_t*>(a + L.field_off[MRCA_F_DONE]);
-    v.result = reinterpret_cast<uint8_t*>(a + L.field_off[MRCA_F_RESULT]);
-    v.first_result = reinterpret_cast<uint8_t*>(a + L.field_off[MRCA_F_FIRST_RESULT]);
-    v.crashed = reinterpret_cast<uint8_t*>(a + L.field_off[MRCA_F_CRASHED]);
-    v.live = reinterpret_cast<uint8_t*>(a + L.field_off[MRCA_F_LIVE]);
-    v.fresh = reinterpret_cast<uint8_t*>(a + L.field_off[MRCA_F_FRESH]);
-    v.t = reinterpret_cast<int32_t*>(a + L.field_off[MRCA_F_T]);
-    v.episode = reinterpret_cast<int32_t*>(a + L.field_off[MRCA_F_EPISODE]);
-    v.reset_mode = reinterpret_cast<const int32_t*>(a + L.off_reset_mode);
-    v.goal_mode = reinterpret_cast<const int32_t*>(a + L.off_goal_mode);
-    v.group_id = reinterpret_cast<const int32_t*>(a + L.off_group_id);
-    v.init_table = reinterpret_cast<const float*>(a + L.off_init_table);
-    v.goal_table = reinterpret_cast<const float*>(a + L.off_goal_table);
-    v.beam_cos = reinterpret_cast<const float*>(a + L.off_beam_cos);
-    v.beam_sin = reinterpret_cast<const float*>(a + L.off_beam_sin);
+    arena::bind(*cfg, a, &v);
     v.beam_step = mrca::kPi / (float)(B - 1);
     v.beam_inv_step = (float)(B - 1) / mrca::kPi;
-    v.map_bits = reinterpret_cast<const uint32_t*>(a + L.off_map);
-    v.free_rect = reinterpret_cast<const uint16_t*>(a + L.off_free_rect);
-    v.free_rect_pitch = free_rect_pitch;
     v.march_rect = v.free_rect;      // (mrca_create: upload_octants points the march at the octant array where it is on)
     v.march_shift = 3;
     v.march_major = 0;
-    v.cellfield = reinterpret_cast<const uint8_t*>(a + L.off_cellfield);
-    v.head = reinterpret_cast<float4*>(a + L.off_head);
-    v.outline = cfg->collision_raster > 0.0f ? reinterpret_cast<mrca::OutlineBits*>(a + L.off_outline) : nullptr;
     v.big = R > 64 ? 1 : 0;
-    if (v.big) {
-        v.bw_ticket = reinterpret_cast<uint32_t*>(a + L.off_bw_ticket);
-        v.bw_prov = reinterpret_cast<float4*>(a + L.off_bw_prov);
-        v.bw_state = reinterpret_cast<int32_t*>(a + L.off_bw_state);
-        v.bw_chead = reinterpret_cast<int32_t*>(a + L.off_bw_chead);
-        v.bw_cnext = reinterpret_cast<int32_t*>(a + L.off_bw_cnext);
-        v.bw_lstart = reinterpret_cast<int32_t*>(a + L.off_bw_lstart);
-        v.bw_lcount = reinterpret_cast<int32_t*>(a + L.off_bw_lcount);
-        v.bw_lsorted = reinterpret_cast<int32_t*>(a + L.off_bw_lsorted);
-        v.bw_lblock = reinterpret_cast<int32_t*>(a + L.off_bw_lblock);
-        v.bw_lcursor = reinterpret_cast<int32_t*>(a + L.off_bw_lcursor);
-        v.bw_cmask = L.bw_cmask;
-        v.bw_lmask = L.bw_lmask;
-    }
-    v.status = reinterpret_cast<uint32_t*>(a + L.off_status);
     v.ray_first = 0;
     v.ray_count = (int32_t)N;
     v.world_first = 0;
@@ -504,7 +377,6 @@ static mrca::EnvView make_view(const mrca_config* cfg, const Layout& L, char* a,
     v.pre_dist_zero = cfg->pre_dist_zero;
     v.hold_velocity = cfg->hold_velocity ? 1 : 0;
     v.auto_reset = cfg->auto_reset;
-    v.num_groups = num_groups;
     v.key0 = (uint32_t)(cfg->seed & 0xFFFFFFFFull);
     v.key1 = (uint32_t)(cfg->seed >> 32);
     v.foot_hc = (int32_t)std::ceil(0.2907 * (double)v.g.inv_cell) + 1;
@@ -557,16 +429,10 @@ static int check_lds(mrca_env* env) {
 static void init_step_many(mrca_env* env) {
     AheadRing& r = env->ahead;
     const size_t N = (size_t)env->view.N;
-    size_t off = 0;
-    const size_t part[5] = {N * 3 * 4, N * sizeof(float4), N * 2 * 4, N, env->view.outline ? N * sizeof(mrca::OutlineBits) : 0};
-    for (int i = 0; i < 5; ++i) {
-        r.off[i] = off;
-        off += align_up(part[i]);
-    }
-    r.slot_bytes = off;
-    size_t slots = kAheadMaxBytes / off;
+    r.slot = arena::make_slot(env->cfg);
+    size_t slots = kAheadMaxBytes / r.slot.bytes;
     if (slots > (size_t)kAheadTicks - 1) slots = kAheadTicks - 1;
-    if (slots >= 1 && device_alloc(&r.mem, slots * off) == hipSuccess) r.slots = (int)slots;
+    if (slots >= 1 && device_alloc(&r.mem, slots * r.slot.bytes) == hipSuccess) r.slots = (int)slots;
     else (void)hipGetLastError();
     bool ok = make_stream(&r.move_stream) == hipSuccess;
     r.moved.resize(kAheadTicks);
@@ -590,7 +456,7 @@ static void init_step_many(mrca_env* env) {
     }
     // (such a launch addresses the fresh flags of its ticks -- up to 8 slots apart -- from one base with a 32-bit offset:
     // beyond that, a launch per tick)
-    if (7ull * r.slot_bytes + (unsigned long long)N > 0xffffffffull) ticks = 1;
+    if (7ull * r.slot.bytes + (unsigned long long)r.slot.part_bytes[arena::kSlotFresh] > 0xffffffffull) ticks = 1;
     if (ticks > 1 && r.slots > 0 && device_alloc(&r.head_scratch, N) == hipSuccess) r.ticks_per_launch = ticks;
     else (void)hipGetLastError();
 }
@@ -604,9 +470,7 @@ const char* mrca_last_error(void) { return g_err; }
 int mrca_arena_bytes(const mrca_config* cfg, size_t* bytes_out) {
     if (int rc = validate(cfg)) return rc;
     if (!bytes_out) return fail(MRCA_ERR_INVALID, "bytes_out is NULL");
-    Layout L;
-    make_layout(cfg, &L);
-    *bytes_out = L.total;
+    *bytes_out = arena::make_layout(*cfg).total;
     return MRCA_OK;
 }
 
@@ -623,15 +487,14 @@ int mrca_create(const mrca_config* cfg, void* arena_dev, size_t arena_bytes, mrc
     std::unique_ptr<mrca_env> env(new (std::nothrow) mrca_env());   // (an early return frees what it holds by then)
     if (!env) return fail(MRCA_ERR_NOMEM, "host allocation failed");
     env->cfg = *cfg;
-    make_layout(cfg, &env->layout);
+    env->layout = arena::make_layout(*cfg);
     if (int rc = attach_arena(env.get(), arena_dev, arena_bytes)) return rc;
-    int free_rect_pitch = 0, num_groups = 0;
-    if (int rc = upload_tables(cfg, env->layout, env->arena, &free_rect_pitch, &num_groups)) return rc;
+    env->view = make_view(cfg, env->arena);
+    if (int rc = upload_tables(cfg, env.get())) return rc;
     const bool octants = field_octants(cfg);
     env->cfg.map_bits = nullptr;  // host pointers are not retained
     env->cfg.reset_mode = env->cfg.goal_mode = env->cfg.group_id = nullptr;
     env->cfg.init_table = env->cfg.goal_table = nullptr;
-    env->view = make_view(cfg, env->layout, env->arena, free_rect_pitch, num_groups);
     if (octants)
         if (int rc = upload_octants(cfg, env.get())) return rc;
     if (int rc = check_lds(env.get())) return rc;

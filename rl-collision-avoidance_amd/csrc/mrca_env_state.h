@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/mrca_env.h"
+#include "mrca_arena.h"
 #include "mrca_hostutil.h"
 #include "mrca_kernels.h"
 
@@ -24,18 +25,6 @@
 // (hidden: the library's exports are include/mrca_env.h's, not the env's inside)
 namespace mrca {
 namespace env_state __attribute__((visibility("hidden"))) {
-
-struct Layout {
-    size_t field_off[MRCA_F_COUNT];
-    size_t field_bytes[MRCA_F_COUNT];
-    size_t off_reset_mode, off_goal_mode, off_group_id, off_init_table, off_goal_table;
-    size_t off_beam_cos, off_beam_sin, off_map, off_free_rect, off_cellfield, off_head, off_outline;
-    // big worlds (robots_per_world > 64) only
-    size_t off_bw_ticket, off_bw_prov, off_bw_state, off_bw_chead, off_bw_cnext, off_bw_lstart, off_bw_lcount, off_bw_lsorted, off_bw_lblock, off_bw_lcursor;
-    size_t off_status;
-    int32_t bw_cmask, bw_lmask;
-    size_t total;
-};
 
 // Owners of what an env holds beside its arena.  A stream is synchronised before it is destroyed.
 struct StreamDeleter { void operator()(hipStream_t s) const { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } };
@@ -70,8 +59,7 @@ template <class T> hipError_t device_alloc(DeviceBuffer<T>* p, size_t bytes) {
 // own fields (where a call starts and where its last tick ends); slots 1 .. slots live in `mem`.
 struct AheadRing {
     DeviceBuffer<char> mem;
-    size_t slot_bytes = 0;
-    size_t off[5] = {0, 0, 0, 0, 0};  // pose, head, goal, fresh, outline inside a slot
+    mrca::arena::Slot slot{};         // where the five lie inside a slot, and a slot's bytes (mrca_arena.h)
     int slots = 0;                    // 0: the ring could not be allocated -> the chained schedule
     Stream move_stream;
     std::vector<Event> moved;         // [kAheadTicks] "tick k's move launch is through"
@@ -116,7 +104,7 @@ struct mrca_env {
     using Event = mrca::env_state::Event;
     DeviceBuffer<char> own_arena;         // the arena when the library allocated it
     mrca_config cfg;
-    mrca::env_state::Layout layout;
+    mrca::arena::Layout layout;
     char* arena = nullptr;
     mrca::EnvView view;
     DeviceBuffer<uint16_t> octant_rect;     // the octant free-rectangle array (outside the arena: the arena's size is ABI), or none
