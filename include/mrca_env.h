@@ -33,7 +33,10 @@
 extern "C" {
 #endif
 
-/* 6, additive: mrca_goal_fields, mrca_subgoals, mrca_planner_grid, mrca_planner_default_params (a global planner: integer goal
+/* 6, additive: mrca_subgoals_los, mrca_los_default_params (the planner's per-tick call with line-of-sight smoothing);
+ * mrca_dwa_actions_goal, mrca_hybrid_actions_goal, mrca_hybrid_plan_goal (the sensor-level controllers steered at rows the caller
+ * gives, a planner's subgoals for instance, in place of MRCA_F_LOCAL_GOAL).
+ * 6, additive: mrca_goal_fields, mrca_subgoals, mrca_planner_grid, mrca_planner_default_params (a global planner: integer goal
  * fields over the map, a subgoal per robot and tick).
  * 6, additive: mrca_hybrid_plan, mrca_hybrid_commit, mrca_safe_policy_default_params, mrca_lidar_features_scaled,
  * mrca_lidar_features_bf16_scaled (hybrid control in the paper's form: the safe policy is the network on a rescaled scan).
@@ -384,6 +387,15 @@ int mrca_dwa_default_params(mrca_dwa_params* out);
 int mrca_dwa_actions(mrca_env* env, const mrca_dwa_params* params /* host, NULL = defaults */, const uint8_t* mask_dev,
                      float* actions_dev /* f32[N,2] */, int32_t* choice_dev /* i32[N] or NULL */,
                      float* score_dev /* f32[N] or NULL */, void* stream);
+/* mrca_dwa_actions steered at the caller's rows: goal_dev f32[N,2], 8-byte aligned, in each robot's own frame (what mrca_subgoals
+ * / mrca_subgoals_los write to local_dev), stands wherever the rule above says "the goal" -- the 0.5 m stop, the progress and
+ * heading terms, the side it turns to when nothing is admissible.  NULL = MRCA_F_LOCAL_GOAL: the launch and the bits are
+ * mrca_dwa_actions'.  The same kernel, the same validation (the messages name this call).  A SUBGOAL WITHIN 0.5 m STOPS THE ROBOT:
+ * feed it subgoals with lookahead * stride * map_cell > 0.5 m.  (mrca_orca_actions steers at MRCA_F_GOAL in the world frame and
+ * has no such sibling.) */
+int mrca_dwa_actions_goal(mrca_env* env, const mrca_dwa_params* params /* host, NULL = defaults */, const uint8_t* mask_dev,
+                          float* actions_dev /* f32[N,2] */, int32_t* choice_dev /* i32[N] or NULL */,
+                          float* score_dev /* f32[N] or NULL */, const float* goal_dev /* f32[N,2] or NULL */, void* stream);
 
 /* A lidar noise model on the device: turns the exact ranges the ray cast has just stored into what a real ranger would have
  * reported -- IN PLACE, in MRCA_F_SCAN_RING, so that everything sensor-level (the policy's fused front end, mrca_dwa_actions,
@@ -476,6 +488,13 @@ int mrca_hybrid_actions(mrca_env* env, const mrca_hybrid_params* params /* host,
                         float* actions_dev /* f32[N,2] out; may be policy_dev itself */,
                         int32_t* mode_dev /* i32[N] or NULL */, float* clear_dev /* f32[N,3] or NULL: d_min, d_front, d_block */,
                         void* stream);
+/* mrca_hybrid_actions steered at the caller's rows: goal_dev f32[N,2], 8-byte aligned, in each robot's own frame, is g above --
+ * the 0.5 m stop, the corridor and the PID law.  NULL = MRCA_F_LOCAL_GOAL: the launch and the bits are mrca_hybrid_actions'.  The
+ * same kernel and validation.  A subgoal within 0.5 m stops the robot: lookahead * stride * map_cell must exceed 0.5 m. */
+int mrca_hybrid_actions_goal(mrca_env* env, const mrca_hybrid_params* params /* host, NULL = defaults */,
+                             const uint8_t* mask_dev /* u8[N] or NULL */, const float* policy_dev /* f32[N,2] in */,
+                             float* actions_dev /* f32[N,2] out; may be policy_dev itself */, int32_t* mode_dev /* i32[N] or NULL */,
+                             float* clear_dev /* f32[N,3] or NULL */, const float* goal_dev /* f32[N,2] or NULL */, void* stream);
 
 /* Hybrid control in the PAPER'S FORM (Fan, Long, Liu, Pan, IJRR 2020, Sec. 5): the safe policy is the NETWORK run on a scan in
  * which obstacles look nearer, its speed capped.  The mode of mrca_hybrid_actions does not depend on the incoming command, so it
@@ -517,6 +536,13 @@ int mrca_hybrid_plan(mrca_env* env, const mrca_hybrid_params* hybrid_params /* h
                      const mrca_safe_policy_params* safe_params /* host, NULL = defaults */,
                      const uint8_t* mask_dev /* u8[N] or NULL */, int32_t* mode_dev /* i32[N] */, float* scale_dev /* f32[N] */,
                      float* pid_dev /* f32[N,2] */, float* clear_dev /* f32[N,3] or NULL */, void* stream);
+/* mrca_hybrid_plan steered at the caller's rows (goal_dev f32[N,2], 8-byte aligned, each robot's own frame; NULL =
+ * MRCA_F_LOCAL_GOAL, then the launch and the bits are mrca_hybrid_plan's): as mrca_hybrid_actions_goal, the 0.5 m note included. */
+int mrca_hybrid_plan_goal(mrca_env* env, const mrca_hybrid_params* hybrid_params /* host, NULL = defaults */,
+                          const mrca_safe_policy_params* safe_params /* host, NULL = defaults */,
+                          const uint8_t* mask_dev /* u8[N] or NULL */, int32_t* mode_dev /* i32[N] */, float* scale_dev /* f32[N] */,
+                          float* pid_dev /* f32[N,2] */, float* clear_dev /* f32[N,3] or NULL */,
+                          const float* goal_dev /* f32[N,2] or NULL */, void* stream);
 int mrca_hybrid_commit(int32_t n_robots, const mrca_safe_policy_params* safe_params /* host, NULL = defaults */,
                        const uint8_t* mask_dev /* u8[N] or NULL */, const int32_t* mode_dev /* i32[N] */,
                        const float* pid_dev /* f32[N,2] */, const float* policy_dev /* f32[N,2] in */,
@@ -548,9 +574,9 @@ int mrca_hybrid_commit(int32_t n_robots, const mrca_safe_policy_params* safe_par
  *                  MRCA_F_LOCAL_GOAL: wherever the subgoal has the goal's bits, local has MRCA_F_LOCAL_GOAL[n]'s
  *   dist_dev       (float)D(first cell) * ((map_cell * (float)s) / 5.0f) metres; +inf for 0xFFFFFFFF, off grid and no slot
  * WHAT THE NUMBERS ARE NOT.  The chamfer 5 / 7 metric OVER-ESTIMATES the Euclidean length of a path by a few percent (up to 8 %
- * at 26.6 degrees; a pure diagonal is 1 % short), on top of the 8-connected path's own detour.  There is NO line-of-sight
- * smoothing: the subgoal is a cell centre on the 8-connected path, `lookahead` steps ahead.  One map for all worlds; other
- * robots are not obstacles of the plan.
+ * at 26.6 degrees; a pure diagonal is 1 % short), on top of the 8-connected path's own detour.  mrca_subgoals does NO
+ * line-of-sight smoothing: its subgoal is a cell centre on the 8-connected path, `lookahead` steps ahead (mrca_subgoals_los
+ * below looks further and takes the farthest cell in sight).  One map for all worlds; other robots are not obstacles of the plan.
  *
  * mrca_goal_fields  the PLANNING call: field_dev[g] for goal point goals_dev[g].  One launch initialises the field, then ONE
  *   launch per round relaxes every (goal, tile of 64 x 64 cells) in LDS from the field as it stands; the host reads a counter
@@ -589,6 +615,42 @@ int mrca_subgoals(mrca_env* env, const mrca_planner_params* params /* host, NULL
                   const float* goals_dev /* f32[G,2] */, int32_t G, const int32_t* slot_dev /* i32[N] or NULL */,
                   const uint8_t* mask_dev /* u8[N] or NULL */, float* local_dev /* f32[N,2] */, float* subgoal_dev /* f32[N,2] or NULL */,
                   float* dist_dev /* f32[N] or NULL */, int32_t* status_dev /* i32[N] or NULL */, void* stream);
+
+/* mrca_subgoals WITH LINE OF SIGHT: the subgoal is the FARTHEST cell of the path, up to `reach` steps down it, that the robot's
+ * planning cell sees -- so the lookahead no longer has to be short to stay on this side of the next corner.  Integers only
+ * (csrc/mrca_planner_device.h, LINE OF SIGHT; tests/planner_los_ref.py restates it).  For a robot with a slot and on the grid,
+ * L = params.lookahead:
+ *   walk      exactly as mrca_subgoals, for up to max(L, reach) steps: the cells c_0 .. c_W (W steps taken)
+ *   open      a cell in the planning grid whose field word is not 0xFFFFFFFF
+ *   visible   visible(c_0, c_m): the integer supercover line between the two cell centres.  dx = |di|, dy = |dj|, err = dx - dy,
+ *             then dx and dy doubled; err > 0: step in x, err -= dy; err < 0: step in y, err += dx; err == 0 (the line passes
+ *             exactly through a lattice corner): both side cells (i + sx, j) and (i, j + sy) must be open -- the walk's
+ *             no-corner-cut rule -- then step diagonally, err += dx - dy.  Every cell entered must be open, the last one
+ *             included; c_0 itself is not tested
+ *   choose    m_vis = the LARGEST m in 1..W with visible(c_0, c_m), or 0 (visibility along a path is not monotone: the largest,
+ *             not the last before the first failure);  m = max(m_vis, min(L, W)): never nearer than mrca_subgoals' subgoal
+ *   outputs   local_dev, subgoal_dev, dist_dev, status_dev exactly as mrca_subgoals gives them for a walk that ended in c_m
+ *             (status 1 with the goal point's bits at the seed; -1 / -2 with MRCA_F_GOAL);  ahead_dev[n] = (m, m_vis), (0, 0) for
+ *             status -1 / -2 and for W = 0
+ * Two consequences: reach <= lookahead gives mrca_subgoals' four outputs bit for bit; and where D(c_0) is finite and W >= 1,
+ * m_vis >= 1.  Line of sight is from the CELL CENTRE, not from the robot's exact position (that keeps the rule in integers);
+ * other robots are not obstacles; one map for all worlds.
+ *   los_params  host; NULL = mrca_los_default_params: reach 60 (6 m on the default 0.1 m planning cells: the lidar's range)
+ *   ahead_dev   i32[N,2] out or NULL;  every other argument as mrca_subgoals
+ * Asynchronous on `stream`, ONE launch (the walk as mrca_subgoals, its cells kept in LDS, then the robot's lanes test candidates
+ * from the far end; a wavefront per robot up to 8192 robots, eight lanes beyond: the same outputs), capturable; writes nothing of
+ * the env.  Validated before the first HIP call
+ * (MRCA_ERR_INVALID): mrca_subgoals' table, then reach 1..256, then mrca_subgoals' pointers and ahead_dev's alignment. */
+typedef struct mrca_los_params {
+    int32_t reach;       /* steps of the path the line of sight may skip to, 1..256 */
+} mrca_los_params;
+int mrca_los_default_params(mrca_los_params* out);
+int mrca_subgoals_los(mrca_env* env, const mrca_planner_params* params /* host, NULL = defaults */,
+                      const mrca_los_params* los_params /* host, NULL = defaults */, const uint32_t* field_dev,
+                      const float* goals_dev /* f32[G,2] */, int32_t G, const int32_t* slot_dev /* i32[N] or NULL */,
+                      const uint8_t* mask_dev /* u8[N] or NULL */, float* local_dev /* f32[N,2] */, float* subgoal_dev /* f32[N,2] or NULL */,
+                      float* dist_dev /* f32[N] or NULL */, int32_t* status_dev /* i32[N] or NULL */,
+                      int32_t* ahead_dev /* i32[N,2] or NULL */, void* stream);
 
 /* (mrca_goal_fields above synchronises its stream too, while it looks for convergence.)
  * Synchronises `stream` and reports (then clears) the env's sticky device-side status word: MRCA_OK, or MRCA_ERR_HIP with

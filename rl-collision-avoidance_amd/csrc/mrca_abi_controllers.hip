@@ -140,6 +140,12 @@ const Rule kPlannerRules[] = {
     ROW(Planner, lookahead, kIntRange, 1, mrca::kPlanMaxLookahead), ROW(Planner, max_rounds, kIntAtLeast0)};
 int check(const char* fn, const Planner& p) { return check_rules(fn, &p, kPlannerRules); }
 
+using Los = mrca_los_params;
+static_assert(offsetof(Los, reach) == offsetof(mrca::LosParams, reach), "mrca_los_params and mrca::LosParams are one layout");
+// (mrca_subgoals_los keeps a planning cell as two 16-bit halves of a word: mrca_create takes no map side above 16384 cells)
+const Rule kLosRules[] = {ROW(Los, reach, kIntRange, 1, mrca::kLosMaxReach)};
+int check(const char* fn, const Los& p) { return check_rules(fn, &p, kLosRules); }
+
 // The params of a call as the kernels take them: the caller's (NULL: the defaults), if their table above accepts them
 template <class P, class Q> int take_params(const char* fn, const P* given, int (*defaults)(P*), Q* out) {
     static_assert(sizeof(P) == sizeof(Q) && std::is_trivially_copyable<P>::value && std::is_trivially_copyable<Q>::value,
@@ -258,17 +264,29 @@ int mrca_dwa_default_params(mrca_dwa_params* out) {
     return MRCA_OK;
 }
 
-int mrca_dwa_actions(mrca_env* env, const mrca_dwa_params* params, const uint8_t* mask_dev, float* actions_dev, int32_t* choice_dev,
-                     float* score_dev, void* stream) {
-    const char* fn = "mrca_dwa_actions";
+// mrca_dwa_actions and mrca_dwa_actions_goal (`fn` names the caller; goal_dev NULL: MRCA_F_LOCAL_GOAL)
+static int dwa_actions(const char* fn, mrca_env* env, const mrca_dwa_params* params, const float* goal_dev, const uint8_t* mask_dev,
+                       float* actions_dev, int32_t* choice_dev, float* score_dev, void* stream) {
     mrca::DwaParams q;
     CHECK(take_params(fn, params, mrca_dwa_default_params, &q));
     CHECK(check_ptr(fn, "actions_dev", actions_dev, 8, true));
     CHECK(check_ptr(fn, "choice_dev", choice_dev, 4, false));
     CHECK(check_ptr(fn, "score_dev", score_dev, 4, false));
+    CHECK(check_ptr(fn, "goal_dev", goal_dev, 8, false));
     if (!env) return fail(MRCA_ERR_INVALID, "env is NULL");
-    return launched(env->cfg.device,
-                    [&] { mrca::launch_dwa(env->view, q, mask_dev, actions_dev, choice_dev, score_dev, static_cast<hipStream_t>(stream)); });
+    return launched(env->cfg.device, [&] {
+        mrca::launch_dwa(env->view, q, goal_dev, mask_dev, actions_dev, choice_dev, score_dev, static_cast<hipStream_t>(stream));
+    });
+}
+
+int mrca_dwa_actions(mrca_env* env, const mrca_dwa_params* params, const uint8_t* mask_dev, float* actions_dev, int32_t* choice_dev,
+                     float* score_dev, void* stream) {
+    return dwa_actions("mrca_dwa_actions", env, params, nullptr, mask_dev, actions_dev, choice_dev, score_dev, stream);
+}
+
+int mrca_dwa_actions_goal(mrca_env* env, const mrca_dwa_params* params, const uint8_t* mask_dev, float* actions_dev, int32_t* choice_dev,
+                          float* score_dev, const float* goal_dev, void* stream) {
+    return dwa_actions("mrca_dwa_actions_goal", env, params, goal_dev, mask_dev, actions_dev, choice_dev, score_dev, stream);
 }
 
 int mrca_scan_noise_default_params(mrca_scan_noise_params* out) {
@@ -308,20 +326,31 @@ int mrca_hybrid_default_params(mrca_hybrid_params* out) {
     return MRCA_OK;
 }
 
-int mrca_hybrid_actions(mrca_env* env, const mrca_hybrid_params* params, const uint8_t* mask_dev, const float* policy_dev,
-                        float* actions_dev, int32_t* mode_dev, float* clear_dev, void* stream) {
-    const char* fn = "mrca_hybrid_actions";
+// mrca_hybrid_actions and mrca_hybrid_actions_goal (`fn` names the caller; goal_dev NULL: MRCA_F_LOCAL_GOAL)
+static int hybrid_actions(const char* fn, mrca_env* env, const mrca_hybrid_params* params, const float* goal_dev, const uint8_t* mask_dev,
+                          const float* policy_dev, float* actions_dev, int32_t* mode_dev, float* clear_dev, void* stream) {
     mrca::HybridParams q;
     CHECK(take_params(fn, params, mrca_hybrid_default_params, &q));
     CHECK(check_ptr(fn, "policy_dev", policy_dev, 4, true));
     CHECK(check_ptr(fn, "actions_dev", actions_dev, 8, true));
     CHECK(check_ptr(fn, "mode_dev", mode_dev, 4, false));
     CHECK(check_ptr(fn, "clear_dev", clear_dev, 4, false));
+    CHECK(check_ptr(fn, "goal_dev", goal_dev, 8, false));
     if (!env) return fail(MRCA_ERR_INVALID, "env is NULL");
-    if (!env->reset_seen) return fail(MRCA_ERR_INVALID, "mrca_hybrid_actions before the first mrca_reset: there is no scan yet");
+    if (!env->reset_seen) return fail(MRCA_ERR_INVALID, "%s before the first mrca_reset: there is no scan yet", fn);
     return launched(env->cfg.device, [&] {
-        mrca::launch_hybrid(env->view, q, mask_dev, policy_dev, actions_dev, mode_dev, clear_dev, static_cast<hipStream_t>(stream));
+        mrca::launch_hybrid(env->view, q, goal_dev, mask_dev, policy_dev, actions_dev, mode_dev, clear_dev, static_cast<hipStream_t>(stream));
     });
+}
+
+int mrca_hybrid_actions(mrca_env* env, const mrca_hybrid_params* params, const uint8_t* mask_dev, const float* policy_dev,
+                        float* actions_dev, int32_t* mode_dev, float* clear_dev, void* stream) {
+    return hybrid_actions("mrca_hybrid_actions", env, params, nullptr, mask_dev, policy_dev, actions_dev, mode_dev, clear_dev, stream);
+}
+
+int mrca_hybrid_actions_goal(mrca_env* env, const mrca_hybrid_params* params, const uint8_t* mask_dev, const float* policy_dev,
+                             float* actions_dev, int32_t* mode_dev, float* clear_dev, const float* goal_dev, void* stream) {
+    return hybrid_actions("mrca_hybrid_actions_goal", env, params, goal_dev, mask_dev, policy_dev, actions_dev, mode_dev, clear_dev, stream);
 }
 
 int mrca_safe_policy_default_params(mrca_safe_policy_params* out) {
@@ -332,9 +361,10 @@ int mrca_safe_policy_default_params(mrca_safe_policy_params* out) {
     return MRCA_OK;
 }
 
-int mrca_hybrid_plan(mrca_env* env, const mrca_hybrid_params* hybrid_params, const mrca_safe_policy_params* safe_params,
-                     const uint8_t* mask_dev, int32_t* mode_dev, float* scale_dev, float* pid_dev, float* clear_dev, void* stream) {
-    const char* fn = "mrca_hybrid_plan";
+// mrca_hybrid_plan and mrca_hybrid_plan_goal (`fn` names the caller; goal_dev NULL: MRCA_F_LOCAL_GOAL)
+static int hybrid_plan(const char* fn, mrca_env* env, const mrca_hybrid_params* hybrid_params, const mrca_safe_policy_params* safe_params,
+                       const float* goal_dev, const uint8_t* mask_dev, int32_t* mode_dev, float* scale_dev, float* pid_dev, float* clear_dev,
+                       void* stream) {
     mrca::HybridParams q;
     mrca::SafeParams sq;
     CHECK(take_params(fn, hybrid_params, mrca_hybrid_default_params, &q));
@@ -343,11 +373,24 @@ int mrca_hybrid_plan(mrca_env* env, const mrca_hybrid_params* hybrid_params, con
     CHECK(check_ptr(fn, "scale_dev", scale_dev, 4, true));
     CHECK(check_ptr(fn, "pid_dev", pid_dev, 8, true));
     CHECK(check_ptr(fn, "clear_dev", clear_dev, 4, false));
+    CHECK(check_ptr(fn, "goal_dev", goal_dev, 8, false));
     if (!env) return fail(MRCA_ERR_INVALID, "env is NULL");
-    if (!env->reset_seen) return fail(MRCA_ERR_INVALID, "mrca_hybrid_plan before the first mrca_reset: there is no scan yet");
+    if (!env->reset_seen) return fail(MRCA_ERR_INVALID, "%s before the first mrca_reset: there is no scan yet", fn);
     return launched(env->cfg.device, [&] {
-        mrca::launch_hybrid_plan(env->view, q, sq, mask_dev, mode_dev, scale_dev, pid_dev, clear_dev, static_cast<hipStream_t>(stream));
+        mrca::launch_hybrid_plan(env->view, q, sq, goal_dev, mask_dev, mode_dev, scale_dev, pid_dev, clear_dev, static_cast<hipStream_t>(stream));
     });
+}
+
+int mrca_hybrid_plan(mrca_env* env, const mrca_hybrid_params* hybrid_params, const mrca_safe_policy_params* safe_params,
+                     const uint8_t* mask_dev, int32_t* mode_dev, float* scale_dev, float* pid_dev, float* clear_dev, void* stream) {
+    return hybrid_plan("mrca_hybrid_plan", env, hybrid_params, safe_params, nullptr, mask_dev, mode_dev, scale_dev, pid_dev, clear_dev, stream);
+}
+
+int mrca_hybrid_plan_goal(mrca_env* env, const mrca_hybrid_params* hybrid_params, const mrca_safe_policy_params* safe_params,
+                          const uint8_t* mask_dev, int32_t* mode_dev, float* scale_dev, float* pid_dev, float* clear_dev,
+                          const float* goal_dev, void* stream) {
+    return hybrid_plan("mrca_hybrid_plan_goal", env, hybrid_params, safe_params, goal_dev, mask_dev, mode_dev, scale_dev, pid_dev, clear_dev,
+                       stream);
 }
 
 int mrca_hybrid_commit(int32_t n_robots, const mrca_safe_policy_params* safe_params, const uint8_t* mask_dev, const int32_t* mode_dev,
@@ -428,12 +471,10 @@ int mrca_goal_fields(mrca_env* env, const mrca_planner_params* params, const flo
     return MRCA_OK;
 }
 
-int mrca_subgoals(mrca_env* env, const mrca_planner_params* params, const uint32_t* field_dev, const float* goals_dev, int32_t G,
-                  const int32_t* slot_dev, const uint8_t* mask_dev, float* local_dev, float* subgoal_dev, float* dist_dev,
-                  int32_t* status_dev, void* stream) {
-    const char* fn = "mrca_subgoals";
-    mrca::PlannerParams q;
-    CHECK(take_params(fn, params, mrca_planner_default_params, &q));
+// What mrca_subgoals and mrca_subgoals_los check alike after their params (`fn` names the caller)
+static int subgoals_validate(const char* fn, const mrca_env* env, const uint32_t* field_dev, const float* goals_dev, int32_t G,
+                             const int32_t* slot_dev, const float* local_dev, const float* subgoal_dev, const float* dist_dev,
+                             const int32_t* status_dev, const int32_t* ahead_dev) {
     CHECK(check_int_range(fn, "G", G, 1, mrca::kPlanMaxGoals));
     CHECK(check_ptr(fn, "field_dev", field_dev, 4, true));
     CHECK(check_ptr(fn, "goals_dev", goals_dev, 4, true));
@@ -442,11 +483,22 @@ int mrca_subgoals(mrca_env* env, const mrca_planner_params* params, const uint32
     CHECK(check_ptr(fn, "subgoal_dev", subgoal_dev, 4, false));
     CHECK(check_ptr(fn, "dist_dev", dist_dev, 4, false));
     CHECK(check_ptr(fn, "status_dev", status_dev, 4, false));
+    CHECK(check_ptr(fn, "ahead_dev", ahead_dev, 4, false));
     if (!env) return fail(MRCA_ERR_INVALID, "env is NULL");
     if (!slot_dev && G != env->cfg.robots_per_world)
-        return fail(MRCA_ERR_INVALID, "mrca_subgoals: slot_dev NULL (slot = n %% robots_per_world) needs G == robots_per_world (%d), got %d",
+        return fail(MRCA_ERR_INVALID, "%s: slot_dev NULL (slot = n %% robots_per_world) needs G == robots_per_world (%d), got %d", fn,
                     env->cfg.robots_per_world, G);
-    if (!env->reset_seen) return fail(MRCA_ERR_INVALID, "mrca_subgoals before the first mrca_reset: there is no head record yet");
+    if (!env->reset_seen) return fail(MRCA_ERR_INVALID, "%s before the first mrca_reset: there is no head record yet", fn);
+    return MRCA_OK;
+}
+
+int mrca_subgoals(mrca_env* env, const mrca_planner_params* params, const uint32_t* field_dev, const float* goals_dev, int32_t G,
+                  const int32_t* slot_dev, const uint8_t* mask_dev, float* local_dev, float* subgoal_dev, float* dist_dev,
+                  int32_t* status_dev, void* stream) {
+    const char* fn = "mrca_subgoals";
+    mrca::PlannerParams q;
+    CHECK(take_params(fn, params, mrca_planner_default_params, &q));
+    CHECK(subgoals_validate(fn, env, field_dev, goals_dev, G, slot_dev, local_dev, subgoal_dev, dist_dev, status_dev, nullptr));
     // (a measurement switch, tools/planner_probe.py: a robot per thread in place of eight lanes per robot -- the same outputs)
     static const int lanes = [] {
         const char* v = getenv("MRCA_SUBGOAL_LANES");
@@ -455,6 +507,33 @@ int mrca_subgoals(mrca_env* env, const mrca_planner_params* params, const uint32
     return launched(env->cfg.device, [&] {
         mrca::launch_subgoals(env->view, q, field_dev, goals_dev, G, slot_dev, mask_dev, local_dev, subgoal_dev, dist_dev, status_dev, lanes,
                               static_cast<hipStream_t>(stream));
+    });
+}
+
+int mrca_los_default_params(mrca_los_params* out) {
+    if (!out) return fail(MRCA_ERR_INVALID, "mrca_los_default_params: out is NULL");
+    out->reach = 60;        // 6 m on the default 0.1 m planning cells: the lidar's range
+    return MRCA_OK;
+}
+
+int mrca_subgoals_los(mrca_env* env, const mrca_planner_params* params, const mrca_los_params* los_params, const uint32_t* field_dev,
+                      const float* goals_dev, int32_t G, const int32_t* slot_dev, const uint8_t* mask_dev, float* local_dev,
+                      float* subgoal_dev, float* dist_dev, int32_t* status_dev, int32_t* ahead_dev, void* stream) {
+    const char* fn = "mrca_subgoals_los";
+    mrca::PlannerParams q;
+    mrca::LosParams lq;
+    CHECK(take_params(fn, params, mrca_planner_default_params, &q));
+    CHECK(take_params(fn, los_params, mrca_los_default_params, &lq));
+    CHECK(subgoals_validate(fn, env, field_dev, goals_dev, G, slot_dev, local_dev, subgoal_dev, dist_dev, status_dev, ahead_dev));
+    // A robot's group of lanes: a wavefront where every robot's is resident at once in that shape (256 CUs x 8 workgroups of four:
+    // 8192 robots), eight lanes beyond -- what tools/planner_probe.py measured on either side.  The same outputs;
+    // MRCA_SUBGOAL_LOS_LANES=8 / 64 forces a shape (read at every call: the probe and the tests run both in one process).
+    const char* forced = getenv("MRCA_SUBGOAL_LOS_LANES");
+    const bool f8 = forced && forced[0] == '8' && !forced[1], f64 = forced && forced[0] == '6' && forced[1] == '4' && !forced[2];
+    const int lanes = f8 ? 8 : f64 ? 64 : (env->view.N <= mrca::kLosWaveRobots ? 64 : 8);
+    return launched(env->cfg.device, [&] {
+        mrca::launch_subgoals_los(env->view, q, lq, field_dev, goals_dev, G, slot_dev, mask_dev, local_dev, subgoal_dev, dist_dev, status_dev,
+                                  ahead_dev, lanes, static_cast<hipStream_t>(stream));
     });
 }
 

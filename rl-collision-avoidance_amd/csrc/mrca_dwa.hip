@@ -101,10 +101,11 @@ __global__ __launch_bounds__(kBlock) void dwa_kernel(const DwaArgs a, const uint
 
 }  // namespace
 
-void launch_dwa(const EnvView& e, const DwaParams& p, const uint8_t* mask, float* actions, int32_t* choice, float* score, hipStream_t s) {
+void launch_dwa(const EnvView& e, const DwaParams& p, const float* goal, const uint8_t* mask, float* actions, int32_t* choice, float* score,
+                hipStream_t s) {
     DwaArgs a;
     a.N = e.N; a.B = e.B; a.F = e.F;
-    a.local_goal = e.local_goal; a.speed = e.speed;
+    a.local_goal = goal ? goal : e.local_goal; a.speed = e.speed;
     a.scan_ring = e.scan_ring; a.ring_head = e.ring_head;
     a.beam_cos = e.beam_cos; a.beam_sin = e.beam_sin;
     a.p = p;

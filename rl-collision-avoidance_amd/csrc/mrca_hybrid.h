@@ -11,7 +11,8 @@ namespace mrca {
 // ONE launch on `s`, the params travel as kernel arguments and the env's fields through its device-side view (e.dev).  Reads
 // e's local_goal, scan_ring, ring_head and beam tables as they stand on `s`, writes nothing of e.  Worlds of any size: a robot
 // needs nothing of another.  Arguments are the ABI's, already validated.
-void launch_hybrid(const EnvView& e, const HybridParams& p, const uint8_t* mask, const float* policy, float* actions, int32_t* mode,
+// goal: f32[N,2] rows in the robots' frames that stand where e's local_goal would (mrca_hybrid_actions_goal), nullptr = e's local_goal.
+void launch_hybrid(const EnvView& e, const HybridParams& p, const float* goal, const uint8_t* mask, const float* policy, float* actions, int32_t* mode,
                    float* clear, hipStream_t s);
 
 }  // namespace mrca

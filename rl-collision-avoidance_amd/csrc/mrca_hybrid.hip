@@ -8,8 +8,9 @@
 // (its head, its goal) is loaded once and made wave-uniform.  No atomics, no LDS, no barrier, no scratch, nothing of the env
 // written.
 //
-// The arguments are 88 bytes: the env's fields come through its device-side view (as in the two kernels of the tick), so that
-// the nine params fit beside the five caller pointers below the 104 bytes at which a launch gets dearer for the host
+// The arguments are 96 bytes: the env's fields come through its device-side view (as in the two kernels of the tick) -- all but
+// the goal, a pointer of its own (MRCA_F_LOCAL_GOAL, or the caller's rows: mrca_hybrid_actions_goal) -- so that
+// the nine params fit beside the six pointers below the 104 bytes at which a launch gets dearer for the host
 // (include/mrca_env.h at mrca_create).
 #include "mrca_hybrid.h"
 
@@ -35,7 +36,7 @@ __device__ __forceinline__ HybridAcc wave_merge(HybridAcc a) {
 
 // (policy and actions may be one buffer: neither is __restrict__, and lane 0 reads its robot's row before it writes it)
 __global__ __launch_bounds__(kBlock) void hybrid_kernel(const EnvView* __restrict__ view_p, const HybridParams q, const int32_t N,
-                                                        const uint8_t* __restrict__ mask, const float* policy, float* actions,
+                                                        const float* __restrict__ goal, const uint8_t* __restrict__ mask, const float* policy, float* actions,
                                                         int32_t* __restrict__ mode, float* __restrict__ clear) {
     const int lane = threadIdx.x & (kWave - 1);
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -47,7 +48,7 @@ __global__ __launch_bounds__(kBlock) void hybrid_kernel(const EnvView* __restric
     const int head = __builtin_amdgcn_readfirstlane((int)e.ring_head[n]);
     if (head >= F) return;                   // (never in an env the library keeps: a head outside the ring must not become an address)
 
-    const HybridRobot rb = hybrid_robot_begin(q, e.local_goal[2 * (size_t)n], e.local_goal[2 * (size_t)n + 1]);
+    const HybridRobot rb = hybrid_robot_begin(q, goal[2 * (size_t)n], goal[2 * (size_t)n + 1]);
     const float* row = e.scan_ring + ((size_t)n * (size_t)F + (size_t)head) * (size_t)B;
     const float* bc = e.beam_cos;
     const float* bs = e.beam_sin;
@@ -72,9 +73,10 @@ __global__ __launch_bounds__(kBlock) void hybrid_kernel(const EnvView* __restric
 
 }  // namespace
 
-void launch_hybrid(const EnvView& e, const HybridParams& p, const uint8_t* mask, const float* policy, float* actions, int32_t* mode,
+void launch_hybrid(const EnvView& e, const HybridParams& p, const float* goal, const uint8_t* mask, const float* policy, float* actions, int32_t* mode,
                    float* clear, hipStream_t s) {
-    hipLaunchKernelGGL(hybrid_kernel, dim3((e.N + kRobotsPerBlock - 1) / kRobotsPerBlock), dim3(kBlock), 0, s, e.dev, p, (int32_t)e.N, mask,
+    hipLaunchKernelGGL(hybrid_kernel, dim3((e.N + kRobotsPerBlock - 1) / kRobotsPerBlock), dim3(kBlock), 0, s, e.dev, p, (int32_t)e.N,
+                       goal ? goal : e.local_goal, mask,
                        policy, actions, mode, clear);
 }
 

@@ -1,5 +1,5 @@
 // mrca_planner.h -- launch interface of the global planner (mrca_planner.hip) for the C ABI (mrca_abi_controllers.hip: mrca_goal_fields,
-// mrca_subgoals).
+// mrca_subgoals, mrca_subgoals_los).
 #pragma once
 #include "mrca_kernels.h"
 #include "mrca_planner_device.h"
@@ -21,5 +21,12 @@ void launch_goal_field_finish(const EnvView& e, const PlannerParams& p, int G, u
 // the ABI's, already validated.
 void launch_subgoals(const EnvView& e, const PlannerParams& p, const uint32_t* field, const float* goals, int G, const int32_t* slot,
                      const uint8_t* mask, float* local, float* subgoal, float* dist, int32_t* status, int lanes, hipStream_t s);
+
+// The per-tick call with line of sight (the rule: mrca_planner_device.h, LINE OF SIGHT): launch_subgoals' arguments, the reach
+// and ahead (i32[N,2] = (m, m_vis), or nullptr).  ONE launch.  lanes: a robot's group, 8 or 64 (the same outputs).
+constexpr int kLosWaveRobots = 8192;      // up to here the library gives a robot a wavefront (mrca_abi_controllers.hip)
+void launch_subgoals_los(const EnvView& e, const PlannerParams& p, const LosParams& lp, const uint32_t* field, const float* goals, int G,
+                         const int32_t* slot, const uint8_t* mask, float* local, float* subgoal, float* dist, int32_t* status,
+                         int32_t* ahead, int lanes, hipStream_t s);
 
 }  // namespace mrca

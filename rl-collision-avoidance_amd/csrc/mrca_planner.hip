@@ -20,6 +20,23 @@
 // Eight lanes ship; the library launches the other only where MRCA_SUBGOAL_LANES=1 asks.  No atomics, no LDS, no
 // barrier, plain vector stores, nothing of the env written.  The arguments are 96 bytes (below the 104 at which a launch gets
 // dearer for the host, include/mrca_env.h at mrca_create): the env's fields come through its device-side view.
+//
+// PER TICK WITH LINE OF SIGHT (subgoal_los_kernel).  Two phases with different shapes.  The WALK is a chain of
+// dependent loads, up to max(lookahead, reach) long: the eight lanes of subgoal_kernel, unchanged, and the first lane of the
+// robot's group drops every cell reached into LDS (one word, j << 16 | i: a map side is at most 16384 cells; 1 KiB per robot).
+// The VISIBILITY TESTS of the cells c_W .. c_1 are independent of each other: the group's lanes take candidates from the far end,
+// lane l the l-th farthest, one ballot per group of candidates, and the robot leaves at the first group that holds a visible
+// one -- its lowest lane is the largest m.  A lane's test is plan_visible as it stands (a divergent loop of loads, at most
+// 2 * 256 trips).  The group is a template parameter: 8 lanes (32 robots and 33 KB of LDS per workgroup) or a whole wavefront
+// (4 robots, 4 KB; the walk then runs eight times over in the same instructions).  tools/planner_probe.py measured both and
+// neither wins everywhere (profiles/planner_los/planner_los_probe.json, medians, Stage-2 map, reach 15 / 60 / 256): at 4092
+// robots a wavefront takes 22 / 87 / 285 us against 24 / 154 / 1029 us for eight lanes -- the launch is latency-bound and a
+// wavefront tests 64 candidates in the time eight lanes test 8 -- at 49 984 robots 144 / 450 / 935 us against 53 / 307 / 1878:
+// there the redundant walks and the 16 times as many workgroups cost more than the wider search saves, except at reach 256.
+// The library gives a robot a wavefront while every robot's fits on the chip at once in that shape (8192 robots) and eight
+// lanes beyond (mrca_abi_controllers.hip); the same words either way.  A group never spans wavefronts: the LDS row of a robot is written and read by one wave, so a
+// wavefront-scope fence stands where a barrier would.  No atomics, no spinning, every loop has a fixed bound, nothing of the
+// env written.  The arguments are 96 bytes as subgoal_kernel's: stride, lookahead and reach travel packed in one word.
 #include "mrca_planner.h"
 
 namespace mrca {
@@ -211,6 +228,105 @@ __global__ __launch_bounds__(kBlock) void subgoal_thread_kernel(const EnvView* _
     robot_out(plan_robot(g, q, rb.f, sg, gl, rb.x, rb.y, rb.sn, rb.cs), n, local, subgoal, dist, status);
 }
 
+constexpr int kLosPitch = kLosMaxPath + 1;          // (odd: robots of a wave that store step W alike hit different banks)
+
+template <int LPR>
+__global__ __launch_bounds__(kBlock) void subgoal_los_kernel(const EnvView* __restrict__ view_p, const uint32_t packed, const int32_t N,
+                                                             const int32_t G, const uint32_t* __restrict__ field,
+                                                             const float* __restrict__ goals, const int32_t* __restrict__ slot,
+                                                             const uint8_t* __restrict__ mask, float* __restrict__ local,
+                                                             float* __restrict__ subgoal, float* __restrict__ dist,
+                                                             int32_t* __restrict__ status, int32_t* __restrict__ ahead) {
+    static_assert(LPR == 8 || LPR == 64, "a robot's group is eight lanes or a wavefront");
+    constexpr int kRobots = kBlock / LPR;
+    __shared__ uint32_t path[kRobots * kLosPitch];
+    const int s = (int)(packed & 0xFu), L = (int)((packed >> 8) & 0x1FFu), reach = (int)((packed >> 20) & 0x1FFu);
+    const int gl = threadIdx.x & (LPR - 1);             // the lane within the robot's group
+    const int k = gl & 7;
+    uint32_t* my_path = path + (threadIdx.x / LPR) * kLosPitch;
+    const int n = (int)((blockIdx.x * (unsigned)kBlock + threadIdx.x) / (unsigned)LPR);
+    // a robot that is not there or not asked for keeps its lanes in the shuffles and ballots below and touches no memory
+    const bool active = n < N && (!mask || mask[n < N ? n : 0]);
+    const EnvView& e = *view_p;
+    const GridGeom g = e.g;
+    const int pw = plan_cells(g.width, s), ph = plan_cells(g.height, s);
+    RobotIn rb = {};
+    if (active) rb = robot_in(e, n, G, (size_t)pw * (size_t)ph, field, goals, slot);
+    int ix = 0, iy = 0;
+    const bool walked = active && plan_map_cell(g, rb.x, rb.y, &ix, &iy) && rb.f != nullptr;
+    const int i0 = ix / s, j0 = iy / s;
+    int ci = i0, cj = j0;
+    uint32_t dc = walked ? rb.f[(size_t)cj * (size_t)pw + (size_t)ci] : kPlanInf;
+    const uint32_t d0 = dc;
+    bool nocand = false, live = walked;
+    int W = 0;
+    const int dxk = plan_dx(k), dyk = plan_dy(k);
+    const int steps = imin(imax(L, reach), kLosMaxPath);
+    // ---- the walk: subgoal_kernel's, every group of eight lanes of the robot's group alike
+    for (int step = 0; step < steps; ++step) {
+        live = live && dc != 0u;
+        if (__builtin_amdgcn_ballot_w64(live) == 0ull) break;       // (wave-uniform: every lane stays in the shuffles)
+        const int ni = ci + dxk, nj = cj + dyk;
+        const bool in = live && ni >= 0 && nj >= 0 && ni < pw && nj < ph;
+        const uint32_t dn = in ? rb.f[(size_t)nj * (size_t)pw + (size_t)ni] : kPlanInf;
+        const uint32_t da = (uint32_t)__shfl((int)dn, (k + 7) & 7, 8);
+        const uint32_t db = (uint32_t)__shfl((int)dn, (k + 1) & 7, 8);
+        unsigned long long key = plan_key(dc, dn, da, db, k);
+#pragma unroll
+        for (int o = 1; o < 8; o <<= 1) key = plan_key_min(key, __shfl_xor(key, o, 8));
+        if (live) {
+            if (key == ~0ull) {
+                nocand = step == 0;
+                live = false;
+            } else {
+                live = plan_take(key, &ci, &cj, &dc);
+                if (live) {
+                    if (gl == 0) my_path[W] = ((uint32_t)cj << 16) | (uint32_t)ci;      // (W < steps <= kLosMaxPath)
+                    ++W;
+                }
+            }
+        }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    // ---- the largest visible m: candidates from the far end, LPR at a time
+    const int shift = (int)(threadIdx.x & (kWave - 1)) & ~(LPR - 1);
+    const unsigned long long group = LPR == 64 ? ~0ull : ((1ull << (LPR & 63)) - 1ull);
+    int m_vis = 0;
+    bool searching = W >= 1;
+    for (int base = 0; base < kLosMaxPath; base += LPR) {
+        if (__builtin_amdgcn_ballot_w64(searching) == 0ull) break;  // (wave-uniform)
+        const int m = W - base - gl;
+        bool vis = false;
+        if (searching && m >= 1) {
+            const uint32_t c = my_path[m - 1];
+            vis = plan_visible(rb.f, pw, ph, i0, j0, (int)(c & 0xFFFFu), (int)(c >> 16));
+        }
+        const unsigned long long seen = (__builtin_amdgcn_ballot_w64(vis) >> shift) & group;
+        if (searching && seen != 0ull) {
+            m_vis = W - base - (int)__builtin_ctzll(seen);
+            searching = false;
+        }
+        searching = searching && base + LPR < W;
+    }
+    if (active && gl == 0) {
+        const int m = plan_los_choose(m_vis, L, W);
+        if (m >= 1) {
+            const uint32_t c = my_path[m - 1];
+            ci = (int)(c & 0xFFFFu);
+            cj = (int)(c >> 16);
+            dc = rb.f[(size_t)cj * (size_t)pw + (size_t)ci];
+        }
+        const PlanResult r = plan_result(g, s, rb.f != nullptr, walked, nocand, ci, cj, dc, d0, rb.sgx, rb.sgy, rb.gx, rb.gy, rb.x, rb.y,
+                                         rb.sn, rb.cs);
+        robot_out(r, n, local, subgoal, dist, status);
+        if (ahead) {
+            ahead[2 * (size_t)n] = m;
+            ahead[2 * (size_t)n + 1] = m_vis;
+        }
+    }
+}
+
 }  // namespace
 
 void launch_goal_field_init(const EnvView& e, const PlannerParams& p, const float* goals, int G, uint32_t* field, hipStream_t s) {
@@ -240,6 +356,21 @@ void launch_subgoals(const EnvView& e, const PlannerParams& p, const uint32_t* f
     constexpr int kRobotsPerBlock = kBlock / 8;
     hipLaunchKernelGGL(subgoal_kernel, dim3((e.N + kRobotsPerBlock - 1) / kRobotsPerBlock), dim3(kBlock), 0, s, e.dev, p, (int32_t)e.N,
                        (int32_t)G, field, goals, slot, mask, local, subgoal, dist, status);
+}
+
+void launch_subgoals_los(const EnvView& e, const PlannerParams& p, const LosParams& lp, const uint32_t* field, const float* goals, int G,
+                         const int32_t* slot, const uint8_t* mask, float* local, float* subgoal, float* dist, int32_t* status,
+                         int32_t* ahead, int lanes, hipStream_t s) {
+    const uint32_t packed = (uint32_t)p.stride | ((uint32_t)p.lookahead << 8) | ((uint32_t)lp.reach << 20);
+    if (lanes == 64) {
+        constexpr int kRobotsPerBlock = kBlock / 64;
+        hipLaunchKernelGGL(subgoal_los_kernel<64>, dim3((e.N + kRobotsPerBlock - 1) / kRobotsPerBlock), dim3(kBlock), 0, s, e.dev, packed,
+                           (int32_t)e.N, (int32_t)G, field, goals, slot, mask, local, subgoal, dist, status, ahead);
+        return;
+    }
+    constexpr int kRobotsPerBlock = kBlock / 8;
+    hipLaunchKernelGGL(subgoal_los_kernel<8>, dim3((e.N + kRobotsPerBlock - 1) / kRobotsPerBlock), dim3(kBlock), 0, s, e.dev, packed,
+                       (int32_t)e.N, (int32_t)G, field, goals, slot, mask, local, subgoal, dist, status, ahead);
 }
 
 }  // namespace mrca

@@ -23,8 +23,9 @@
 // D(c) = min over allowed steps of D(n) + w -- unique, so ANY order of relaxation, with values of any age, ends in the same words.
 // Lengths fit: a path visits a cell once, 7 * 2^28 cells < 2^32.
 // The chamfer 5/7 metric OVER-ESTIMATES the Euclidean length of a path by up to 8 % (a step at 26.6 degrees costs 5 + 7 = 12
-// for sqrt(5) * 5 = 11.18) and under-estimates a pure diagonal by 1 % (7 for 7.07).  There is NO line-of-sight smoothing: the
-// subgoal is a cell centre on the 8-connected path.
+// for sqrt(5) * 5 = 11.18) and under-estimates a pure diagonal by 1 % (7 for 7.07).  mrca_subgoals does NO line-of-sight
+// smoothing: its subgoal is a cell centre `lookahead` steps down the 8-connected path.  mrca_subgoals_los (LINE OF SIGHT, below)
+// looks further down the same path and takes the farthest cell the robot's cell sees.
 //
 // While mrca_goal_fields relaxes, blocked cells hold kPlanWall, which no candidate reads as a length; its last launch turns them
 // into kPlanInf.  In the finished field a cell beside a finite unblocked cell is blocked iff it holds kPlanInf (it would
@@ -42,8 +43,21 @@
 // the ray cast uses for MRCA_F_LOCAL_GOAL (mrca_raycast_body.h).  dist = (float)D(c_start) * ((g.cell * (float)s) / 5.0f), +inf
 // for kPlanInf, off grid and no slot.
 //
+// LINE OF SIGHT (mrca_subgoals_los).  Integers only.  With `reach` (1..256) beside L: walk as above for up to
+// max(L, reach) steps and keep the cells c_0 .. c_W (W steps taken).  A cell is OPEN iff it is in the planning grid and its word
+// is not kPlanInf.  visible(c_0, c_m) is the integer supercover line between the two cell centres (McNeill's form): dx = |di|,
+// dy = |dj|, err = dx - dy, then dx and dy doubled; err > 0: step in x, err -= dy; err < 0: step in y, err += dx; err == 0: the
+// line passes exactly through a lattice corner -- both side cells (i + sx, j) and (i, j + sy) must be open (the walk's
+// no-corner-cut rule), then step diagonally, err += dx - dy.  Every cell entered must be open, the last one included; c_0 itself
+// is not tested (a robot inside the inflation still sees).  m_vis = the LARGEST m in 1..W with visible(c_0, c_m), 0 if none
+// (visibility along a path is not monotone: the largest, not the last before the first failure); m = max(m_vis, min(L, W)), so
+// the subgoal is never nearer than the plain walk's.  The four outputs are plan_result's for a walk that ended in c_m; a fifth,
+// ahead = (m, m_vis), is (0, 0) for status -1 / -2 and for W = 0.  Two consequences: reach <= L gives mrca_subgoals' four
+// outputs bit for bit (W <= L, so m = W); and where D(c_0) is finite and W >= 1, m_vis >= 1 (c_1 is an allowed step: open, and
+// if diagonal between two open cells).
+//
 // Like mrca_device.h: integers, or separately rounded IEEE fp32 steps in a fixed order (-ffp-contract=off).  A NumPy / heapq
-// restatement (tests/planner_ref.py) gives the same words and bits.
+// restatement (tests/planner_ref.py, tests/planner_los_ref.py) gives the same words and bits.
 #pragma once
 #include "mrca_device.h"
 
@@ -53,6 +67,10 @@ namespace mrca {
 struct PlannerParams {
     int32_t stride, inflate, lookahead, max_rounds;
 };
+// same layout as mrca_los_params
+struct LosParams {
+    int32_t reach;
+};
 
 constexpr uint32_t kPlanInf = 0xFFFFFFFFu;    // blocked, or no path
 constexpr uint32_t kPlanWall = 0xFFFFFFFEu;   // blocked, while mrca_goal_fields relaxes (never in a finished field)
@@ -60,6 +78,9 @@ constexpr uint32_t kPlanStraight = 5u, kPlanDiagonal = 7u;
 constexpr int kPlanTile = 64;                 // a workgroup relaxes kPlanTile x kPlanTile planning cells
 constexpr int kPlanSweeps = 64;               // at most this many times per launch
 constexpr int kPlanMaxStride = 8, kPlanMaxInflate = 64, kPlanMaxLookahead = 256, kPlanMaxGoals = 4096;
+constexpr int kLosMaxReach = 256;             // mrca_los_params::reach, 1..kLosMaxReach
+constexpr int kLosMaxPath = 256;              // the longest walk mrca_subgoals_los keeps: max(lookahead, reach)
+static_assert(kLosMaxPath >= kPlanMaxLookahead && kLosMaxPath >= kLosMaxReach, "the kept path holds the longest walk");
 constexpr int kPlanOnGoal = 1, kPlanOnPath = 0, kPlanNoSlot = -1, kPlanNoPath = -2;
 
 // direction k = 0..7: E, NE, N, NW, W, SW, S, SE (two bits per direction, offset by one)
@@ -201,6 +222,96 @@ MRCA_HD PlanResult plan_robot(const GridGeom& g, const PlannerParams& q, const u
     }
     return plan_result(g, s, f != nullptr, walked, nocand, ci, cj, dc, d0, f ? slot_goal[0] : 0.0f, f ? slot_goal[1] : 0.0f, goal[0], goal[1],
                        x, y, sn, cs);
+}
+
+// ---- line of sight
+
+MRCA_HD bool plan_open(const uint32_t* f, int pw, int ph, int i, int j) {
+    return i >= 0 && j >= 0 && i < pw && j < ph && f[(size_t)j * (size_t)pw + (size_t)i] != kPlanInf;
+}
+
+// visible(c_0 = (i0, j0), (i1, j1)): the supercover line of the rule.  At most |di| + |dj| cells are entered.
+MRCA_HD bool plan_visible(const uint32_t* f, int pw, int ph, int i0, int j0, int i1, int j1) {
+    int dx = i1 > i0 ? i1 - i0 : i0 - i1, dy = j1 > j0 ? j1 - j0 : j0 - j1;
+    const int sx = i1 > i0 ? 1 : -1, sy = j1 > j0 ? 1 : -1;
+    int left = dx + dy;                 // unit steps still to go; a diagonal step is two of them
+    int err = dx - dy;
+    dx *= 2;
+    dy *= 2;
+    int i = i0, j = j0;
+    bool ok = true;
+    for (int t = 0; t < 2 * kLosMaxPath && ok && left > 0; ++t) {
+        if (err > 0) {
+            i += sx;
+            err -= dy;
+            left -= 1;
+        } else if (err < 0) {
+            j += sy;
+            err += dx;
+            left -= 1;
+        } else {
+            ok = plan_open(f, pw, ph, i + sx, j) && plan_open(f, pw, ph, i, j + sy);
+            i += sx;
+            j += sy;
+            err += dx - dy;
+            left -= 2;
+        }
+        ok = ok && plan_open(f, pw, ph, i, j);
+    }
+    return ok;
+}
+
+// m of the rule from m_vis, L and W
+MRCA_HD int plan_los_choose(int m_vis, int L, int W) { return imax(m_vis, imin(L, W)); }
+
+struct LosResult {
+    PlanResult r;
+    int m, m_vis;
+};
+
+// The whole line-of-sight rule for one robot; the arguments of plan_robot and the reach.  path: 2 * kLosMaxPath ints of scratch.
+MRCA_HD LosResult plan_robot_los(const GridGeom& g, const PlannerParams& q, const LosParams& lq, const uint32_t* f, const float* slot_goal,
+                                 const float* goal, float x, float y, float sn, float cs, int* path) {
+    const int s = q.stride, pw = plan_cells(g.width, s), ph = plan_cells(g.height, s);
+    int ix, iy;
+    const bool walked = plan_map_cell(g, x, y, &ix, &iy) && f != nullptr;
+    const int i0 = ix / s, j0 = iy / s;
+    int ci = i0, cj = j0;
+    uint32_t dc = walked ? f[(size_t)cj * (size_t)pw + (size_t)ci] : kPlanInf;
+    const uint32_t d0 = dc;
+    bool nocand = false, live = walked;
+    int W = 0;
+    const int steps = imax(q.lookahead, lq.reach);
+    for (int step = 0; step < steps; ++step) {
+        live = live && dc != 0u;
+        if (!live) break;
+        const uint64_t key = plan_best_step(f, pw, ph, ci, cj, dc);
+        if (key == ~(uint64_t)0) {
+            nocand = step == 0;
+            live = false;
+        } else {
+            live = plan_take(key, &ci, &cj, &dc);
+            if (live) {
+                path[2 * W] = ci;
+                path[2 * W + 1] = cj;
+                ++W;
+            }
+        }
+    }
+    int m_vis = 0;
+    for (int m = W; m >= 1 && m_vis == 0; --m)
+        if (plan_visible(f, pw, ph, i0, j0, path[2 * (m - 1)], path[2 * (m - 1) + 1])) m_vis = m;
+    LosResult out;
+    out.m = plan_los_choose(m_vis, q.lookahead, W);
+    out.m_vis = m_vis;
+    if (out.m >= 1) {
+        ci = path[2 * (out.m - 1)];
+        cj = path[2 * (out.m - 1) + 1];
+        dc = f[(size_t)cj * (size_t)pw + (size_t)ci];
+    }
+    out.r = plan_result(g, s, f != nullptr, walked, nocand, ci, cj, dc, d0, f ? slot_goal[0] : 0.0f, f ? slot_goal[1] : 0.0f, goal[0],
+                        goal[1], x, y, sn, cs);
+    return out;
 }
 
 // One workgroup's share of a launch of mrca_goal_fields, as a loop: tile (ti, tj) of field f [ph][pw] relaxed at most `sweeps`

@@ -9,8 +9,8 @@ namespace mrca {
 // mode[n], scale[n], pid[n] and clear[n] (or nullptr) := what safe_plan_robot (mrca_safe_device.h) makes of robot n's newest scan
 // row and local goal, for every robot whose mask byte is not 0 (mask nullptr: all); other rows are not touched.  ONE launch on
 // `s`; reads e's local_goal, scan_ring, ring_head and beam tables as they stand on `s`, writes nothing of e.  Arguments are the
-// ABI's, already validated.
-void launch_hybrid_plan(const EnvView& e, const HybridParams& p, const SafeParams& sp, const uint8_t* mask, int32_t* mode, float* scale,
+// ABI's, already validated.  goal: f32[N,2] rows that stand where e's local_goal would (mrca_hybrid_plan_goal), nullptr = e's local_goal.
+void launch_hybrid_plan(const EnvView& e, const HybridParams& p, const SafeParams& sp, const float* goal, const uint8_t* mask, int32_t* mode, float* scale,
                         float* pid, float* clear, hipStream_t s);
 
 // actions[n] := safe_commit of policy[n] under mode[n] and pid[n], for every robot whose mask byte is not 0; actions may be

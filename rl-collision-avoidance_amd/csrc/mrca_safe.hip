@@ -5,7 +5,8 @@
 // index of hybrid_kernel (mrca_hybrid.hip): in round k lane l owns beam 64 k + l, a lane folds its beams into its own partial
 // minima and count, one butterfly merges the 64 partial results, lane 0 writes mode, scale, pid and the clearances with
 // ordinary vector stores.  It reads no command.  No atomics, no LDS, no barrier, no scratch, nothing of the env written.
-// The arguments are 96 bytes (the env's fields come through its device-side view), below the 104 at which a launch gets
+// The arguments are 104 bytes (the env's fields come through its device-side view, all but the goal: MRCA_F_LOCAL_GOAL or the
+// caller's rows, mrca_hybrid_plan_goal), not above the 104 beyond which a launch gets
 // dearer for the host (include/mrca_env.h at mrca_create).
 //
 // COMMIT: one thread per robot, a handful of loads, a select and one 8-byte store.
@@ -32,8 +33,8 @@ __device__ __forceinline__ HybridAcc wave_merge(HybridAcc a) {
 }
 
 __global__ __launch_bounds__(kBlock) void hybrid_plan_kernel(const EnvView* __restrict__ view_p, const HybridParams q, const SafeParams sp,
-                                                             const int32_t N, const uint8_t* __restrict__ mask,
-                                                             int32_t* __restrict__ mode, float* __restrict__ scale,
+                                                             const int32_t N, const float* __restrict__ goal,
+                                                             const uint8_t* __restrict__ mask, int32_t* __restrict__ mode, float* __restrict__ scale,
                                                              float* __restrict__ pid, float* __restrict__ clear) {
     const int lane = threadIdx.x & (kWave - 1);
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -45,7 +46,7 @@ __global__ __launch_bounds__(kBlock) void hybrid_plan_kernel(const EnvView* __re
     const int head = __builtin_amdgcn_readfirstlane((int)e.ring_head[n]);
     if (head >= F) return;                   // (never in an env the library keeps: a head outside the ring must not become an address)
 
-    const HybridRobot rb = hybrid_robot_begin(q, e.local_goal[2 * (size_t)n], e.local_goal[2 * (size_t)n + 1]);
+    const HybridRobot rb = hybrid_robot_begin(q, goal[2 * (size_t)n], goal[2 * (size_t)n + 1]);
     const float* row = e.scan_ring + ((size_t)n * (size_t)F + (size_t)head) * (size_t)B;
     const float* bc = e.beam_cos;
     const float* bs = e.beam_sin;
@@ -84,10 +85,10 @@ __global__ __launch_bounds__(kBlock) void hybrid_commit_kernel(const int32_t N, 
 
 }  // namespace
 
-void launch_hybrid_plan(const EnvView& e, const HybridParams& p, const SafeParams& sp, const uint8_t* mask, int32_t* mode, float* scale,
+void launch_hybrid_plan(const EnvView& e, const HybridParams& p, const SafeParams& sp, const float* goal, const uint8_t* mask, int32_t* mode, float* scale,
                         float* pid, float* clear, hipStream_t s) {
     hipLaunchKernelGGL(hybrid_plan_kernel, dim3((e.N + kRobotsPerBlock - 1) / kRobotsPerBlock), dim3(kBlock), 0, s, e.dev, p, sp,
-                       (int32_t)e.N, mask, mode, scale, pid, clear);
+                       (int32_t)e.N, goal ? goal : e.local_goal, mask, mode, scale, pid, clear);
 }
 
 void launch_hybrid_commit(int32_t n_robots, const SafeParams& sp, const uint8_t* mask, const int32_t* mode, const float* pid,

@@ -35,7 +35,8 @@ EXPORTS = ["mrca_abi_version", "mrca_last_error", "mrca_arena_bytes", "mrca_crea
            "mrca_dwa_default_params", "mrca_dwa_actions", "mrca_scan_noise_default_params", "mrca_scan_noise",
            "mrca_hybrid_default_params", "mrca_hybrid_actions",
            "mrca_safe_policy_default_params", "mrca_hybrid_plan", "mrca_hybrid_commit", "mrca_lidar_features_scaled",
-           "mrca_planner_default_params", "mrca_planner_grid", "mrca_goal_fields", "mrca_subgoals"]
+           "mrca_planner_default_params", "mrca_planner_grid", "mrca_goal_fields", "mrca_subgoals",
+           "mrca_los_default_params", "mrca_subgoals_los", "mrca_dwa_actions_goal", "mrca_hybrid_actions_goal", "mrca_hybrid_plan_goal"]
 # declared in include/mrca_env.h like the names above, listed apart: tests/test_abi.py's header scan reads names of letters
 # and underscores only (tests/test_policy_bf16_host.py checks these against the header and the library)
 EXPORTS_WITH_DIGITS = ["mrca_lidar_features_bf16", "mrca_lidar_features_bf16_rows", "mrca_lidar_features_bf16_backward",
@@ -85,6 +86,11 @@ class SafePolicyParamsStruct(C.Structure):
 class PlannerParamsStruct(C.Structure):
     """include/mrca_env.h: mrca_planner_params"""
     _fields_ = [(k, C.c_int32) for k in ("stride", "inflate", "lookahead", "max_rounds")]
+
+
+class LosParamsStruct(C.Structure):
+    """include/mrca_env.h: mrca_los_params"""
+    _fields_ = [("reach", C.c_int32)]
 
 
 class MrcaConfig(C.Structure):
@@ -199,6 +205,12 @@ def load(path=None):
     lib.mrca_goal_fields.argtypes = [C.c_void_p, C.POINTER(PlannerParamsStruct), C.c_void_p, C.c_int32, C.c_void_p,
                                      C.POINTER(C.c_int32), C.c_void_p]
     lib.mrca_subgoals.argtypes = [C.c_void_p, C.POINTER(PlannerParamsStruct), C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 7
+    lib.mrca_los_default_params.argtypes = [C.POINTER(LosParamsStruct)]
+    lib.mrca_subgoals_los.argtypes = [C.c_void_p, C.POINTER(PlannerParamsStruct), C.POINTER(LosParamsStruct), C.c_void_p, C.c_void_p,
+                                      C.c_int32] + [C.c_void_p] * 8
+    lib.mrca_dwa_actions_goal.argtypes = lib.mrca_dwa_actions.argtypes[:-1] + [C.c_void_p, C.c_void_p]
+    lib.mrca_hybrid_actions_goal.argtypes = lib.mrca_hybrid_actions.argtypes[:-1] + [C.c_void_p, C.c_void_p]
+    lib.mrca_hybrid_plan_goal.argtypes = lib.mrca_hybrid_plan.argtypes[:-1] + [C.c_void_p, C.c_void_p]
     lib.mrca_enable_timing.argtypes = [C.c_void_p, C.c_int32]
     if hasattr(lib, "mrca_set_debug_flags"):      # profiling build only
         lib.mrca_set_debug_flags.argtypes = [C.c_void_p, C.c_int32]

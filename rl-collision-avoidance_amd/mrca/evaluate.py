@@ -84,39 +84,42 @@ def orca_policy_fn(env, params=None, first=None, other=None):
     return mixed
 
 
-def dwa_policy_fn(env, params=None, first=None, other=None, other_name="policy"):
+def dwa_policy_fn(env, params=None, first=None, other=None, other_name="policy", steer=False):
     """The DWA baseline controller on the device (``VecStageWorld.dwa_actions``): it reads the env's own fields (each robot's
     scan, local goal and speed), so it wants no observation stack.  ``first = K`` with ``other``: robots with local index < K
     are driven by DWA (through the mask), the rest by the policy function ``other`` (a checkpoint, the stand-in or ORCA), whose
-    group is reported as ``other_name`` -- or, where ``other`` is itself a mixed run, as its own groups without DWA's robots."""
+    group is reported as ``other_name`` -- or, where ``other`` is itself a mixed run, as its own groups without DWA's robots.
+    ``steer``: DWA steers at the ``local_goal`` it is handed (a planner's subgoals) in place of the env's own."""
     if first is None:
         def fn(obs, local_goal, speed):
-            return env.dwa_actions(params)
+            return env.dwa_actions(params, goal=local_goal if steer else None)
         fn.wants_obs = False
         return fn
     mask = (torch.arange(env.N, device=env.device) % env.R < int(first)).to(torch.uint8).contiguous()
 
     def mixed(obs, local_goal, speed):
         a = other(obs, local_goal, speed).float().contiguous().clone()
-        return env.dwa_actions(params, mask=mask, out=a)
+        return env.dwa_actions(params, mask=mask, out=a, goal=local_goal if steer else None)
     mixed.wants_obs = getattr(other, "wants_obs", True)
     rest = getattr(other, "groups", None) or {other_name: torch.ones(env.N, dtype=torch.bool, device=env.device)}
     mixed.groups = {"dwa": mask.bool(), **{k: v & ~mask.bool() for k, v in rest.items()}}
     return mixed
 
 
-def hybrid_policy_fn(env, other, params=None):
+def hybrid_policy_fn(env, other, params=None, steer=False):
     """Hybrid control (``VecStageWorld.hybrid_actions``) behind the controller function ``other``, whatever it is: per robot and
     tick a PID law where the way to the goal is free, ``other``'s command with v scaled down where something is dangerously
     close, ``other``'s command elsewhere.  ``fn.mode_shares()`` -> the share of the live robot-ticks (robots without a
-    terminal event yet) spent in each mode; the counts are kept on the device and read when that is called."""
+    terminal event yet) spent in each mode; the counts are kept on the device and read when that is called.  ``steer``: the
+    wrapper's goal is the ``local_goal`` it is handed (a planner's subgoals) in place of the env's own."""
     from .hybrid import MODE_NAMES
     codes = torch.tensor(list(MODE_NAMES), dtype=torch.int32, device=env.device)
     counts = torch.zeros(len(MODE_NAMES), dtype=torch.int64, device=env.device)
     mode = torch.zeros(env.N, dtype=torch.int32, device=env.device)
 
     def fn(obs, local_goal, speed):
-        a = env.hybrid_actions(other(obs, local_goal, speed).float().contiguous(), params, mode=mode)
+        a = env.hybrid_actions(other(obs, local_goal, speed).float().contiguous(), params, mode=mode,
+                               goal=local_goal if steer else None)
         live = env.first_result == 0
         counts.add_(((mode.unsqueeze(1) == codes) & live.unsqueeze(1)).sum(dim=0))
         return a
@@ -132,12 +135,13 @@ def hybrid_policy_fn(env, other, params=None):
     return fn
 
 
-def safe_policy_fn(policy, env, params=None, safe=None, fused_bf16=False, skip_first=0):
+def safe_policy_fn(policy, env, params=None, safe=None, fused_bf16=False, skip_first=0, steer=False):
     """Hybrid control in the paper's form around the checkpoint ``policy`` (fused inference on the env's ring of raw scans):
     per tick ``env.hybrid_plan`` -> ONE forward in which the robots of mode 2 see their scan through the plan's scale ->
     ``env.hybrid_commit``.  ``skip_first = K``: robots with local index < K belong to another controller (--orca-first,
     --dwa-first): they are masked out of the plan and the commit, so they stay in mode 0 with scale 1.  ``fn.mode_shares()`` as
-    ``hybrid_policy_fn``'s (the planned robots' live robot-ticks; counted on the device, read when that is called)."""
+    ``hybrid_policy_fn``'s (the planned robots' live robot-ticks; counted on the device, read when that is called).  ``steer``:
+    the plan's goal is the ``local_goal`` handed in (a planner's subgoals) in place of the env's own."""
     from .hybrid import MODE_NAMES
     codes = torch.tensor(list(MODE_NAMES), dtype=torch.int32, device=env.device)
     counts = torch.zeros(len(MODE_NAMES), dtype=torch.int64, device=env.device)
@@ -150,7 +154,7 @@ def safe_policy_fn(policy, env, params=None, safe=None, fused_bf16=False, skip_f
         mask = planned.to(torch.uint8).contiguous()
 
     def fn(obs, local_goal, speed):
-        env.hybrid_plan(params, safe, mask=mask, mode=mode, scale=scale, pid=pid)
+        env.hybrid_plan(params, safe, mask=mask, mode=mode, scale=scale, pid=pid, goal=local_goal if steer else None)
         ring, head = ppo.policy_input(env, True)
         _mean, scaled = ppo.generate_action_no_sampling(policy, ring, local_goal, speed, ACTION_BOUND, fused=True, obs_head=head,
                                                         fused_bf16=fused_bf16, scan_scale=scale)
@@ -170,21 +174,33 @@ def safe_policy_fn(policy, env, params=None, safe=None, fused_bf16=False, skip_f
     return fn
 
 
-def planner_policy_fn(env, other, params=None):
+def planner_policy_fn(env, other, params=None, los=None):
     """The global planner under the controller function ``other`` (a checkpoint or a stand-in): the goal fields are planned at
     the first tick (``VecStageWorld.plan_goals``: the distinct goals of the env as they stand behind the reset), and every tick
     ``other`` is handed the robots' subgoals in their own frames (``VecStageWorld.subgoals``) in place of ``env.local_goal``.
-    ``fn.report()`` -> the params, the status counts of the last tick and the mean path length at the first tick."""
+    ``los`` (a ``planner.LosParams``): the subgoals with line of sight (``VecStageWorld.subgoals_los``) -- then ``other`` may
+    be any controller that steers at the local goal it is handed (DWA and hybrid control with ``steer=True`` included).
+    ``fn.report()`` -> the params, the status counts of the last tick and the mean path length at the first tick; with ``los``
+    also its params and the mean (m, m_vis) over the live robot-ticks of the run (summed on the device, read when called)."""
     from .planner import STATUS_NAMES, PlannerParams
     params = params if params is not None else PlannerParams.for_grid(env.scenario.grid)
     state = {"fields": None, "first_dist": None}
     out = (torch.zeros((env.N, 2), dtype=torch.float32, device=env.device), torch.zeros((env.N, 2), dtype=torch.float32, device=env.device),
            torch.zeros(env.N, dtype=torch.float32, device=env.device), torch.zeros(env.N, dtype=torch.int32, device=env.device))
+    if los is not None:
+        out = out + (torch.zeros((env.N, 2), dtype=torch.int32, device=env.device),)
+    ahead_sum = torch.zeros(3, dtype=torch.int64, device=env.device)         # m, m_vis, live robot-ticks
 
     def fn(obs, local_goal, speed):
         if state["fields"] is None:
             state["fields"] = env.plan_goals(params=params)
-        local, _sub, dist, _status = env.subgoals(state["fields"], out=out)
+        if los is None:
+            local, _sub, dist, _status = env.subgoals(state["fields"], out=out)
+        else:
+            local, _sub, dist, _status, ahead = env.subgoals_los(state["fields"], los, out=out)
+            live = (env.first_result == 0).to(torch.int64)
+            ahead_sum[:2].add_((ahead.to(torch.int64) * live.unsqueeze(1)).sum(dim=0))
+            ahead_sum[2].add_(live.sum())
         if state["first_dist"] is None:
             finite = dist[torch.isfinite(dist)]
             state["first_dist"] = float(finite.mean()) if finite.numel() else None
@@ -193,7 +209,11 @@ def planner_policy_fn(env, other, params=None):
 
     def report():
         f = state["fields"]
-        return {"planner_params": params.as_dict(),
+        extra = {}
+        if los is not None:
+            m, m_vis, ticks = ahead_sum.tolist()
+            extra = {"los_params": los.as_dict(), "planner_mean_ahead": [m / ticks, m_vis / ticks] if ticks else None}
+        return {**extra, "planner_params": params.as_dict(),
                 "planner_goals": None if f is None else f.num_goals, "planner_rounds": None if f is None else f.rounds,
                 "planner_status_last_tick": {name: int((out[3] == code).sum()) for code, name in STATUS_NAMES.items()},
                 "planner_mean_initial_path_m": state["first_dist"]}
@@ -316,6 +336,13 @@ def main():
                     help="the global planner under --policy P [--fused | --fused-bf16] or the stand-in: goal fields planned once "
                          "(mrca_goal_fields), the controller handed each robot's subgoal (mrca_subgoals) in place of the local goal; "
                          "the result line gains planner_params, the status counts of the last tick and the mean initial path length")
+    ap.add_argument("--planner-los", action="store_true",
+                    help="the global planner with line of sight (mrca_subgoals_los): implies --planner, takes --planner-param too, and "
+                         "goes under --dwa / --dwa-first / --hybrid / --hybrid-safe as well (their kernels are handed the subgoal: "
+                         "mrca_dwa_actions_goal, mrca_hybrid_actions_goal, mrca_hybrid_plan_goal), not under --orca / --orca-first; "
+                         "the result line gains los_params and planner_mean_ahead = the mean (m, m_vis) over the run")
+    ap.add_argument("--los-param", action="append", default=[], metavar="NAME=VALUE",
+                    help="a field of mrca_los_params on top of LosParams.for_grid of the map, e.g. reach=40 (repeatable)")
     ap.add_argument("--planner-param", action="append", default=[], metavar="NAME=VALUE",
                     help="a field of mrca_planner_params on top of PlannerParams.for_grid of the map, e.g. lookahead=10 (repeatable)")
     ap.add_argument("--radius", type=float, default=25.0)
@@ -380,9 +407,15 @@ def main():
         ap.error("--scenario doorway excludes --radius / --one-circle / --stage-resolution")
     if a.robots is None:
         a.robots = 12 if doorway else 50
-    if a.planner_param and not a.planner:
+    if a.planner_param and not (a.planner or a.planner_los):
         ap.error("--planner-param goes with --planner")
-    if a.planner and (a.orca or a.dwa or a.hybrid or a.hybrid_safe or a.orca_first is not None or a.dwa_first is not None):
+    if a.los_param and not a.planner_los:
+        ap.error("--los-param goes with --planner-los")
+    if a.planner_los and (a.orca or a.orca_first is not None):
+        ap.error("--planner-los: ORCA steers at the goal in the world frame (MRCA_F_GOAL), it takes no subgoal: not with --orca / "
+                 "--orca-first")
+    steer = a.planner_los
+    if a.planner and not a.planner_los and (a.orca or a.dwa or a.hybrid or a.hybrid_safe or a.orca_first is not None or a.dwa_first is not None):
         ap.error("--planner hands the subgoal to a controller that takes the local goal as an argument (--policy, the stand-in): the "
                  "kernels of --orca / --dwa / --hybrid / --hybrid-safe read the env's own local goal")
     if a.hybrid_safe_param and not a.hybrid_safe:
@@ -437,18 +470,26 @@ def main():
             except ValueError as e:
                 ap.error(str(e))
             fn = safe_policy_fn(pol, env, hybrid_params, safe_params, fused_bf16=a.fused_bf16,
-                                skip_first=max(a.orca_first or 0, a.dwa_first or 0))
+                                skip_first=max(a.orca_first or 0, a.dwa_first or 0), steer=steer)
             safe_fn, name = fn, f"hybrid control in the paper's form (mrca_hybrid_plan, mrca_hybrid_commit) around {name}"
     elif doorway:
         fn, name = go_to_goal_policy, "go-to-goal stand-in (no checkpoint given)"
     else:
         fn, name = staggered_roundabout_policy(env.N), "staggered-roundabout stand-in (no checkpoint given)"
-    if a.planner:
-        from .planner import PlannerParams
+    los_params = None
+    if a.planner or a.planner_los:
+        from .planner import LosParams, PlannerParams
         try:
             planner_params = PlannerParams.from_assignments(a.planner_param, base=PlannerParams.for_grid(sc.grid))
+            if a.planner_los:
+                los_params = LosParams.from_assignments(a.los_param, base=LosParams.for_grid(sc.grid))
         except ValueError as e:
             ap.error(str(e))
+        ahead_m = planner_params.lookahead * planner_params.stride * sc.grid.cell
+        if a.planner_los and (a.dwa or a.dwa_first is not None or a.hybrid or a.hybrid_safe) and ahead_m <= 0.5:
+            ap.error(f"--planner-los under --dwa / --hybrid: a subgoal within 0.5 m stops these controllers, and lookahead x cell "
+                     f"is {ahead_m:g} m: raise --planner-param lookahead")
+    if a.planner and not a.planner_los:
         fn = planner_fn = planner_policy_fn(env, fn, planner_params)
         name = f"global planner (mrca_goal_fields, mrca_subgoals) under {name}"
     orca_call = "mrca_orca_actions_any" if env.R > 64 else "mrca_orca_actions"
@@ -465,9 +506,9 @@ def main():
         from .dwa import DwaParams
         dwa_params = DwaParams.from_assignments(a.dwa_param)
         if a.dwa_first is None:
-            fn, name = dwa_policy_fn(env, dwa_params), "DWA baseline (mrca_dwa_actions)"
+            fn, name = dwa_policy_fn(env, dwa_params, steer=steer), "DWA baseline (mrca_dwa_actions)"
         else:
-            fn = dwa_policy_fn(env, dwa_params, first=a.dwa_first, other=fn, other_name="orca" if a.orca else "policy")
+            fn = dwa_policy_fn(env, dwa_params, first=a.dwa_first, other=fn, other_name="orca" if a.orca else "policy", steer=steer)
             name = f"DWA for local index < {a.dwa_first}, else {name}"
     if a.hybrid_param and not (a.hybrid or a.hybrid_safe):
         ap.error("--hybrid-param goes with --hybrid or --hybrid-safe")
@@ -477,7 +518,15 @@ def main():
             hybrid_params = HybridParams.from_assignments(a.hybrid_param)
         except ValueError as e:
             ap.error(str(e))
-        fn, name = hybrid_policy_fn(env, fn, hybrid_params), f"hybrid control (mrca_hybrid_actions) behind {name}"
+        fn, name = hybrid_policy_fn(env, fn, hybrid_params, steer=steer), f"hybrid control (mrca_hybrid_actions) behind {name}"
+    if a.planner_los:
+        # outermost: every controller below is handed the subgoal where it would read the env's local goal
+        inner = fn
+        fn = planner_fn = planner_policy_fn(env, inner, planner_params, los_params)
+        for attr in ("groups", "mode_shares"):
+            if hasattr(inner, attr):
+                setattr(fn, attr, getattr(inner, attr))
+        name = f"global planner with line of sight (mrca_goal_fields, mrca_subgoals_los) under {name}"
     perturb = tuple(float(v) for v in a.perturb.split(",")) if a.perturb else None
     recorder = None
     if a.render:
@@ -504,7 +553,7 @@ def main():
         out["hybrid_safe_params"] = dataclasses.asdict(safe_params)
         out["hybrid_params"] = dataclasses.asdict(hybrid_params)
         out["hybrid_modes"] = safe_fn.mode_shares()
-    if a.planner:
+    if a.planner or a.planner_los:
         out.update(planner_fn.report())
     if doorway:
         out["scenario"] = a.scenario

@@ -1,4 +1,5 @@
-"""The global planner's Python side (include/mrca_env.h: mrca_planner_params, mrca_goal_fields, mrca_subgoals).  The defaults are
+"""The global planner's Python side (include/mrca_env.h: mrca_planner_params, mrca_goal_fields, mrca_subgoals, and
+mrca_los_params, mrca_subgoals_los: the per-tick call with line of sight).  The defaults are
 the library's own (mrca_planner_default_params): they are stated once, in C."""
 import dataclasses
 import math
@@ -32,6 +33,25 @@ class PlannerParams(ParamsMirror):
     @classmethod
     def from_assignments(cls, items, base=None):
         """``["stride=1", "lookahead=20"]`` (the evaluator's --planner-param) on top of ``base`` -> PlannerParams."""
+        return super().from_assignments(items, start=base and base.as_dict())
+
+
+@dataclasses.dataclass
+class LosParams(ParamsMirror):
+    """Mirror of mrca_los_params; a field left ``None`` takes the library's default."""
+    _STRUCT, _DEFAULTS, _FLAG = _lib.LosParamsStruct, "mrca_los_default_params", "--los-param"
+    reach: int = None                   # steps of the path the line of sight may skip to, 1..256
+
+    @classmethod
+    def for_grid(cls, grid, reach_m=6.0, cell_m=0.1):
+        """Metres -> cells on ``grid``: ``reach_m`` down the path in planning cells of about ``cell_m`` (the stride
+        ``PlannerParams.for_grid`` picks for the same ``cell_m``)."""
+        stride = min(8, max(1, int(round(cell_m / grid.cell))))
+        return cls(reach=min(256, max(1, int(round(reach_m / (grid.cell * stride))))))
+
+    @classmethod
+    def from_assignments(cls, items, base=None):
+        """``["reach=40"]`` (the evaluator's --los-param) on top of ``base`` -> LosParams."""
         return super().from_assignments(items, start=base and base.as_dict())
 
 

@@ -280,23 +280,29 @@ class VecStageWorld:
                                            self._stream()), name)
         return out
 
-    def dwa_actions(self, params=None, mask=None, out=None, choice=None, score=None):
+    def dwa_actions(self, params=None, mask=None, out=None, choice=None, score=None, goal=None):
         """(v, omega) of the DWA baseline controller (mrca_dwa_actions) for every robot, as a float32[N,2] tensor on the env's
         device: the sensor-level counterpart of ``orca_actions`` -- it reads each robot's newest scan, local goal and own speed
         and nothing of any other robot, so it takes worlds of any size.  One launch on the current stream, nothing
         synchronises, nothing of the env is written: ``env.step(env.dwa_actions())`` is a closed-loop scripted tick.
         ``params``: a ``dwa.DwaParams`` (default: the library's); ``mask``: a uint8[N] tensor, rows with 0 keep what ``out``
         (and ``choice`` / ``score``) hold; ``choice``: an int32[N] tensor that takes the candidate chosen (-1: none was
-        admissible, -2: at the goal); ``score``: a float32[N] tensor that takes its score."""
+        admissible, -2: at the goal); ``score``: a float32[N] tensor that takes its score; ``goal``: a float32[N,2] tensor in
+        the robots' frames to steer at in place of ``env.local_goal`` (mrca_dwa_actions_goal) -- ``subgoals_los(...)[0]``; a
+        subgoal within 0.5 m stops the robot, so the planner's lookahead must reach further than that."""
         if out is None:
             out = torch.zeros((self.N, 2), dtype=torch.float32, device=self.device)
         st = None if params is None else params.struct()
-        _lib.check(self.lib.mrca_dwa_actions(self._h, None if st is None else C.byref(st), self._ptr(mask, torch.uint8, self.N),
-                                             self._ptr(out, torch.float32, 2 * self.N), self._ptr(choice, torch.int32, self.N),
-                                             self._ptr(score, torch.float32, self.N), self._stream()), "mrca_dwa_actions")
+        args = (self._h, None if st is None else C.byref(st), self._ptr(mask, torch.uint8, self.N),
+                self._ptr(out, torch.float32, 2 * self.N), self._ptr(choice, torch.int32, self.N), self._ptr(score, torch.float32, self.N))
+        if goal is None:
+            _lib.check(self.lib.mrca_dwa_actions(*args, self._stream()), "mrca_dwa_actions")
+        else:
+            _lib.check(self.lib.mrca_dwa_actions_goal(*args, self._ptr(goal, torch.float32, 2 * self.N), self._stream()),
+                       "mrca_dwa_actions_goal")
         return out
 
-    def hybrid_actions(self, actions, params=None, mask=None, out=None, mode=None, clear=None):
+    def hybrid_actions(self, actions, params=None, mask=None, out=None, mode=None, clear=None, goal=None):
         """Hybrid control behind a policy (mrca_hybrid_actions): per robot, ``actions`` (float32[N,2], the policy's (v, omega))
         replaced by a PID law where nothing stands between the robot and its goal, scaled down in v where something is
         dangerously close, kept as it is elsewhere -- decided from each robot's newest scan and local goal alone.  One launch
@@ -304,17 +310,22 @@ class VecStageWorld:
         tick.  ``out=None`` works IN PLACE on ``actions`` and returns it.  ``params``: a ``hybrid.HybridParams`` (default: the
         library's); ``mask``: a uint8[N] tensor, rows with 0 keep what ``out`` (and ``mode`` / ``clear``) hold; ``mode``: an
         int32[N] tensor that takes 0 (the policy), 1 (PID), 2 (the policy made careful) or -2 (at the goal); ``clear``: a
-        float32[N,3] tensor that takes (d_min, d_front, d_block)."""
+        float32[N,3] tensor that takes (d_min, d_front, d_block); ``goal``: a float32[N,2] tensor in the robots' frames that
+        stands where ``env.local_goal`` would (mrca_hybrid_actions_goal), as for ``dwa_actions``."""
         if out is None:
             out = actions
         st = None if params is None else params.struct()
-        _lib.check(self.lib.mrca_hybrid_actions(self._h, None if st is None else C.byref(st), self._ptr(mask, torch.uint8, self.N),
-                                                self._ptr(actions, torch.float32, 2 * self.N), self._ptr(out, torch.float32, 2 * self.N),
-                                                self._ptr(mode, torch.int32, self.N), self._ptr(clear, torch.float32, 3 * self.N),
-                                                self._stream()), "mrca_hybrid_actions")
+        args = (self._h, None if st is None else C.byref(st), self._ptr(mask, torch.uint8, self.N),
+                self._ptr(actions, torch.float32, 2 * self.N), self._ptr(out, torch.float32, 2 * self.N),
+                self._ptr(mode, torch.int32, self.N), self._ptr(clear, torch.float32, 3 * self.N))
+        if goal is None:
+            _lib.check(self.lib.mrca_hybrid_actions(*args, self._stream()), "mrca_hybrid_actions")
+        else:
+            _lib.check(self.lib.mrca_hybrid_actions_goal(*args, self._ptr(goal, torch.float32, 2 * self.N), self._stream()),
+                       "mrca_hybrid_actions_goal")
         return out
 
-    def hybrid_plan(self, params=None, safe=None, mask=None, mode=None, scale=None, pid=None, clear=None):
+    def hybrid_plan(self, params=None, safe=None, mask=None, mode=None, scale=None, pid=None, clear=None, goal=None):
         """The first half of hybrid control in the paper's form (mrca_hybrid_plan): per robot, from its newest scan and local
         goal alone -- no command is read -- the mode ``hybrid_actions`` would report (int32[N]: 0, 1, 2, -2), the factor its
         scan is to be seen through (float32[N]: ``safe.scan_scale`` in mode 2, else 1) and the PID command (float32[N,2]: mode
@@ -322,7 +333,8 @@ class VecStageWorld:
         (``CNNPolicy.act_fused``) -> ``hybrid_commit`` -> ``step``.  One launch on the current stream, nothing synchronises,
         nothing of the env is written.  ``params``: a ``hybrid.HybridParams``, ``safe``: a ``hybrid.SafePolicyParams`` (default:
         the library's); ``mask``: a uint8[N] tensor, rows with 0 keep what the outputs hold (fresh outputs start as mode 0,
-        scale 1, pid 0); ``clear``: a float32[N,3] tensor that takes (d_min, d_front, d_block)."""
+        scale 1, pid 0); ``clear``: a float32[N,3] tensor that takes (d_min, d_front, d_block); ``goal``: a float32[N,2] tensor in
+        the robots' frames that stands where ``env.local_goal`` would (mrca_hybrid_plan_goal), as for ``dwa_actions``."""
         if mode is None:
             mode = torch.zeros(self.N, dtype=torch.int32, device=self.device)
         if scale is None:
@@ -331,10 +343,14 @@ class VecStageWorld:
             pid = torch.zeros((self.N, 2), dtype=torch.float32, device=self.device)
         st = None if params is None else params.struct()
         ss = None if safe is None else safe.struct()
-        _lib.check(self.lib.mrca_hybrid_plan(self._h, None if st is None else C.byref(st), None if ss is None else C.byref(ss),
-                                             self._ptr(mask, torch.uint8, self.N), self._ptr(mode, torch.int32, self.N),
-                                             self._ptr(scale, torch.float32, self.N), self._ptr(pid, torch.float32, 2 * self.N),
-                                             self._ptr(clear, torch.float32, 3 * self.N), self._stream()), "mrca_hybrid_plan")
+        args = (self._h, None if st is None else C.byref(st), None if ss is None else C.byref(ss), self._ptr(mask, torch.uint8, self.N),
+                self._ptr(mode, torch.int32, self.N), self._ptr(scale, torch.float32, self.N), self._ptr(pid, torch.float32, 2 * self.N),
+                self._ptr(clear, torch.float32, 3 * self.N))
+        if goal is None:
+            _lib.check(self.lib.mrca_hybrid_plan(*args, self._stream()), "mrca_hybrid_plan")
+        else:
+            _lib.check(self.lib.mrca_hybrid_plan_goal(*args, self._ptr(goal, torch.float32, 2 * self.N), self._stream()),
+                       "mrca_hybrid_plan_goal")
         return mode, scale, pid
 
     def hybrid_commit(self, actions, mode, pid, safe=None, mask=None, out=None):
@@ -396,6 +412,31 @@ class VecStageWorld:
                                           self._ptr(subgoal, torch.float32, 2 * self.N), self._ptr(dist, torch.float32, self.N),
                                           self._ptr(status, torch.int32, self.N), self._stream()), "mrca_subgoals")
         return local, subgoal, dist, status
+
+    def subgoals_los(self, fields, los=None, mask=None, out=None):
+        """The per-tick call with line of sight (mrca_subgoals_los): as ``subgoals``, but the subgoal is the farthest cell of the
+        path, up to ``los.reach`` steps down it, that the robot's planning cell sees (never nearer than ``subgoals``' own) ->
+        ``(local, subgoal, dist, status, ahead)``; ``ahead`` int32[N,2] = (m, m_vis): how many steps down the path the subgoal
+        lies and the farthest visible one (0, 0: no walk).  ``los``: a ``planner.LosParams`` (default: the library's, reach
+        60); ``out``: the five tensors to write into; ``mask``: a uint8[N] tensor, rows with 0 keep what ``out`` holds.  One
+        launch on the current stream, nothing synchronises, nothing of the env is written."""
+        if out is None:
+            out = (torch.zeros((self.N, 2), dtype=torch.float32, device=self.device),
+                   torch.zeros((self.N, 2), dtype=torch.float32, device=self.device),
+                   torch.zeros(self.N, dtype=torch.float32, device=self.device),
+                   torch.zeros(self.N, dtype=torch.int32, device=self.device),
+                   torch.zeros((self.N, 2), dtype=torch.int32, device=self.device))
+        local, subgoal, dist, status, ahead = out
+        G = fields.num_goals
+        st = fields.params.struct()
+        ls = None if los is None else los.struct()
+        _lib.check(self.lib.mrca_subgoals_los(self._h, C.byref(st), None if ls is None else C.byref(ls),
+                                              C.c_void_p(fields.field.data_ptr()), self._ptr(fields.goals, torch.float32, 2 * G), G,
+                                              self._ptr(fields.slot, torch.int32, self.N), self._ptr(mask, torch.uint8, self.N),
+                                              self._ptr(local, torch.float32, 2 * self.N), self._ptr(subgoal, torch.float32, 2 * self.N),
+                                              self._ptr(dist, torch.float32, self.N), self._ptr(status, torch.int32, self.N),
+                                              self._ptr(ahead, torch.int32, 2 * self.N), self._stream()), "mrca_subgoals_los")
+        return local, subgoal, dist, status, ahead
 
     def scan_noise(self, params=None, mask=None):
         """The lidar noise model (mrca_scan_noise) applied IN PLACE to the newest scan row of every robot (``mask``: a uint8[N]
