@@ -33,7 +33,9 @@
 extern "C" {
 #endif
 
-/* 6, additive: mrca_subgoals_los, mrca_los_default_params (the planner's per-tick call with line-of-sight smoothing);
+/* 6, additive: mrca_nhorca_actions, mrca_nhorca_default_params (the NH-ORCA baseline: ORCA over the holonomic velocities a
+ * unicycle tracks within a bound).
+ * 6, additive: mrca_subgoals_los, mrca_los_default_params (the planner's per-tick call with line-of-sight smoothing);
  * mrca_dwa_actions_goal, mrca_hybrid_actions_goal, mrca_hybrid_plan_goal (the sensor-level controllers steered at rows the caller
  * gives, a planner's subgoals for instance, in place of MRCA_F_LOCAL_GOAL).
  * 6, additive: mrca_goal_fields, mrca_subgoals, mrca_planner_grid, mrca_planner_default_params (a global planner: integer goal
@@ -347,6 +349,41 @@ int mrca_orca_actions(mrca_env* env, const mrca_orca_params* params /* host, NUL
 int mrca_orca_actions_any(mrca_env* env, const mrca_orca_params* params /* host, NULL = defaults */,
                           const uint8_t* mask_dev /* u8[N] or NULL = all */, float* actions_dev /* f32[N,2] */,
                           float* vel_dev /* f32[N,2] or NULL */, void* stream);
+
+/* The NH-ORCA baseline (Alonso-Mora, Breitenmoser, Rufli, Beardsley, Siegwart, "Optimal reciprocal collision avoidance for multiple
+ * non-holonomic robots"): ORCA that may choose only holonomic velocities the unicycle can track within track_error metres, every
+ * disc grown by track_error.  A velocity of speed u at angle th from the heading is tracked by omega = th / track_time and
+ * v = u (th/2) / tan(th/2); inside the cone |th| <= min(track_time * 1 rad/s, pi/2) and the disc
+ * |v| <= min(max_speed, track_error / (track_time sin(th_max / 2))) the unicycle stays within track_error of the point that moves
+ * at that velocity over [0, track_time].  The cone enters ORCA's linear program as two hard lines ahead of the static ones.
+ * Two solves per robot: a free one (ORCA with the grown radius) decides whether the tracked one aims at the preferred velocity
+ * or at zero, and which way the robot turns in place when the tracked one stands still.  The rule is
+ * csrc/mrca_nhorca_device.h, reproducible bit for bit (tests/nhorca_ref.py restates it in NumPy); DESIGN.md 5.19.
+ *   params      host; NULL = mrca_nhorca_default_params: ORCA's defaults, then track_error and track_time (chosen by a
+ *               closed-loop sweep, profiles/nhorca/defaults.txt).  k_omega is ignored.
+ *   vel_dev     f32[N,2] or NULL: the tracked solve's velocity
+ *   mode_dev    i32[N] or NULL, 4-byte aligned: MRCA_NHORCA_*
+ * mask_dev, actions_dev, the stream, what is read and that nothing of the env is written: as mrca_orca_actions.  Worlds of ANY
+ * size: up to 64 robots the small launch, above that the neighbours come from the lidar hash under mrca_orca_actions_any's
+ * rules (neighbor_dist <= 19.3 or MRCA_ERR_UNSUPPORTED; the hash must describe the current poses or MRCA_ERR_INVALID).
+ * Validated before the first HIP call (MRCA_ERR_INVALID): every float finite; mrca_orca_actions' rules for its fields;
+ * track_error in (0, 0.5]; track_time in [0.1, 1.5]; max_neighbors 1..46 (two of the 64 constraints are the heading lines). */
+typedef struct mrca_nhorca_params {
+    float radius, neighbor_dist, time_horizon, time_horizon_obst, obst_dist, v_pref, max_speed, responsibility, k_omega, jitter;
+    int32_t max_neighbors; /* 1..46 */
+    float track_error;     /* eps [m] */
+    float track_time;      /* T [s] */
+} mrca_nhorca_params;
+enum {
+    MRCA_NHORCA_TRACK = 0, /* drives at the preferred velocity as far as the constraints allow */
+    MRCA_NHORCA_TURN = 1,  /* turns in place */
+    MRCA_NHORCA_STILL = 2, /* stands still */
+    MRCA_NHORCA_EVADE = 3  /* should turn in place but the constraints make it move */
+};
+int mrca_nhorca_default_params(mrca_nhorca_params* out);
+int mrca_nhorca_actions(mrca_env* env, const mrca_nhorca_params* params /* host, NULL = defaults */,
+                        const uint8_t* mask_dev /* u8[N] or NULL = all */, float* actions_dev /* f32[N,2] */,
+                        float* vel_dev /* f32[N,2] or NULL */, int32_t* mode_dev /* i32[N] or NULL */, void* stream);
 
 /* A second classical baseline on the device, SENSOR-LEVEL where ORCA is agent-level: the dynamic window approach (Fox, Burgard,
  * Thrun, "The dynamic window approach to collision avoidance", 1997).  Per robot it reads what the policy reads and nothing

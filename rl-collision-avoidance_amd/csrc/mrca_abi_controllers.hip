@@ -1,5 +1,5 @@
-// mrca_abi_controllers.hip -- host side of include/mrca_env.h for what acts on an env between its ticks: the renderer, the ORCA
-// and DWA baselines, the lidar noise model, hybrid control and the global planner.  Every entry point has one shape -- take the
+// mrca_abi_controllers.hip -- host side of include/mrca_env.h for what acts on an env between its ticks: the renderer, the ORCA,
+// NH-ORCA and DWA baselines, the lidar noise model, hybrid control and the global planner.  Every entry point has one shape -- take the
 // params (the caller's or the defaults) through their table, check the pointers, then the env, then launch -- and the pieces
 // of that shape are stated once, below.  What can be judged without the env is judged first, in the order it stands here: a
 // caller's mistake is named whatever else is wrong.  The env itself is mrca_abi.hip's (mrca_env_state.h).
@@ -91,6 +91,21 @@ const Rule kOrcaRules[] = {
     ROW(Orca, max_speed, kAbove, 0), ROW(Orca, obst_dist, kClosed, 0, 6), ROW(Orca, responsibility, kClosed, 0, 1),
     ROW(Orca, max_neighbors, kIntRange, 0, mrca::kOrcaMaxNeighbors)};
 int check(const char* fn, const Orca& p) { return check_rules(fn, &p, kOrcaRules); }
+
+using NhOrca = mrca_nhorca_params;
+static_assert(offsetof(NhOrca, max_neighbors) == offsetof(mrca::NhOrcaParams, o.max_neighbors) &&
+                  offsetof(NhOrca, track_time) == offsetof(mrca::NhOrcaParams, track_time),
+              "mrca_nhorca_params and mrca::NhOrcaParams are one layout");
+// (ORCA's rules for ORCA's fields, in ORCA's order; max_neighbors has its own bound here and comes last)
+const Rule kNhOrcaRules[] = {
+    ROW(NhOrca, radius, kFinite), ROW(NhOrca, neighbor_dist, kFinite), ROW(NhOrca, time_horizon, kFinite), ROW(NhOrca, time_horizon_obst, kFinite),
+    ROW(NhOrca, obst_dist, kFinite), ROW(NhOrca, v_pref, kFinite), ROW(NhOrca, max_speed, kFinite), ROW(NhOrca, responsibility, kFinite),
+    ROW(NhOrca, k_omega, kFinite), ROW(NhOrca, jitter, kFinite), ROW(NhOrca, track_error, kFinite), ROW(NhOrca, track_time, kFinite),
+    ROW(NhOrca, radius, kAbove, 0), ROW(NhOrca, neighbor_dist, kAbove, 0), ROW(NhOrca, time_horizon, kAbove, 0),
+    ROW(NhOrca, time_horizon_obst, kAbove, 0), ROW(NhOrca, max_speed, kAbove, 0), ROW(NhOrca, obst_dist, kClosed, 0, 6),
+    ROW(NhOrca, responsibility, kClosed, 0, 1), ROW(NhOrca, track_error, kHalfOpen, 0, 0.5f), ROW(NhOrca, track_time, kClosed, 0.1f, 1.5f),
+    ROW(NhOrca, max_neighbors, kIntRange, 1, mrca::kNhMaxNeighbors)};
+int check(const char* fn, const NhOrca& p) { return check_rules(fn, &p, kNhOrcaRules); }
 
 using Dwa = mrca_dwa_params;
 static_assert(offsetof(Dwa, steps) == offsetof(mrca::DwaParams, steps) && offsetof(Dwa, nw) == offsetof(mrca::DwaParams, nw),
@@ -241,6 +256,41 @@ int mrca_orca_actions_any(mrca_env* env, const mrca_orca_params* params, const u
     return launched(env->cfg.device, [&] {
         if (big) mrca::launch_orca_big(env->view, q, mask_dev, actions_dev, vel_dev, static_cast<hipStream_t>(stream));
         else mrca::launch_orca(env->view, q, mask_dev, actions_dev, vel_dev, static_cast<hipStream_t>(stream));
+    });
+}
+
+int mrca_nhorca_default_params(mrca_nhorca_params* out) {
+    if (!out) return fail(MRCA_ERR_INVALID, "mrca_nhorca_default_params: out is NULL");
+    mrca_orca_params o;
+    mrca_orca_default_params(&o);
+    memcpy(out, &o, sizeof o);       // ORCA's eleven fields lead, in ORCA's layout; k_omega is not used
+    // (track_error, track_time, jitter): chosen by the sweep over the four closed-loop gates, profiles/nhorca/defaults.txt
+    out->track_error = 0.05f;
+    out->track_time = 0.3f;
+    out->jitter = 0.3f;
+    return MRCA_OK;
+}
+
+int mrca_nhorca_actions(mrca_env* env, const mrca_nhorca_params* params, const uint8_t* mask_dev, float* actions_dev, float* vel_dev,
+                        int32_t* mode_dev, void* stream) {
+    const char* fn = "mrca_nhorca_actions";
+    mrca::NhOrcaParams q;
+    CHECK(take_params(fn, params, mrca_nhorca_default_params, &q));
+    CHECK(check_ptr(fn, "actions_dev", actions_dev, 8, true));
+    CHECK(check_ptr(fn, "vel_dev", vel_dev, 4, false));
+    CHECK(check_ptr(fn, "mode_dev", mode_dev, 4, false));
+    if (!env) return fail(MRCA_ERR_INVALID, "env is NULL");
+    const bool big = env->cfg.robots_per_world > mrca::kOrcaMaxRobots;      // (mrca_orca_actions_any's two rules for big worlds)
+    if (big && mrca::orca_rings(q.o.neighbor_dist) == 0)
+        return fail(MRCA_ERR_UNSUPPORTED, "mrca_nhorca_actions: neighbor_dist %g > 19.3 with robots_per_world %d > %d (the search "
+                                          "looks at three rings of 6.5 m cells at most)",
+                    (double)q.o.neighbor_dist, env->cfg.robots_per_world, mrca::kOrcaMaxRobots);
+    if (big && !env->lidar_hash_current)
+        return fail(MRCA_ERR_INVALID, "mrca_nhorca_actions: the lidar hash does not describe the current poses -- call "
+                                      "mrca_observe_worlds (after mrca_move_worlds) or mrca_reset first (robots_per_world %d > %d)",
+                    env->cfg.robots_per_world, mrca::kOrcaMaxRobots);
+    return launched(env->cfg.device, [&] {
+        mrca::launch_nhorca(env->view, q, big, mask_dev, actions_dev, vel_dev, mode_dev, static_cast<hipStream_t>(stream));
     });
 }
 

@@ -13,6 +13,9 @@
 // (orca_kernel<false>).  More (mrca_orca_actions_any, orca_kernel<true>): the candidates come from the env's lidar hash, 64 at a time,
 // and the best max_neighbors keys stay in registers (hashed_neighbours); from "lane 16 + r holds neighbour r" on it is the
 // same code.
+//
+// The NH-ORCA baseline (mrca_nhorca_actions) is the same body with a second flag, orca_kernel<BIG, true>: two
+// heading lines in lanes 0 and 1 and the solve run twice (mrca_nhorca_device.h).
 #include "mrca_orca.h"
 
 #include <type_traits>
@@ -193,11 +196,56 @@ __device__ __forceinline__ Key hashed_neighbours(const OrcaArgs& a, const OrcaHa
 
 struct OrcaNoHash {};
 
+// NH-ORCA (mrca_nhorca_device.h): what nhorca_derive gave (the grown radius travels as a.p.radius), the tracking time, and where
+// the modes go (or nullptr)
+struct NhArgs {
+    float sm, cm, u_cap, track_time;
+    int32_t* mode;
+};
+
+struct OrcaNoNh {};
+
+// The solve over the wave's lines: LP2, and where it falls short LP3, in which the lanes below `hard` stay hard and the robot
+// lines are relaxed evenly.  (rx, ry) is wave-uniform.
+__device__ __forceinline__ void solve_wave(const OrcaLine& line, bool valid, int lane, int hard, float max_speed, float ox, float oy,
+                                           float* rx_out, float* ry_out) {
+    float rx, ry;
+    const int short_at = lp2_wave(line, valid, lane, max_speed, ox, oy, false, &rx, &ry);
+    if (short_at < kWave) {
+        float distance = 0.0f;
+        unsigned long long consider = lanes_from(short_at);
+        for (;;) {
+            const unsigned long long m = __ballot(valid && orca_violation(line, rx, ry) > distance) & consider;
+            if (!m) break;
+            const int i = __ffsll((long long)m) - 1;
+            consider = lanes_from(i + 1);
+            const OrcaLine li = line_of_lane(line, i);
+            OrcaLine pl = line;
+            bool pvalid = valid;
+            if (lane >= hard) pvalid = valid && lane < i && orca_project(li, line, &pl);
+            float tx, ty;
+            if (lp2_wave(pl, pvalid, lane, max_speed, -li.dy, li.dx, true, &tx, &ty) == kWave) {
+                rx = tx;
+                ry = ty;
+            }
+            distance = orca_violation(li, rx, ry);
+        }
+    }
+    *rx_out = rx;
+    *ry_out = ry;
+}
+
 // BIG: worlds of more than kOrcaMaxRobots robots (`hsh` is their lidar hash); otherwise `hsh` is empty and the kernel is, but for
-// its name, the one that worlds of up to 64 robots have always run
-template <bool BIG>
+// its name, the one that worlds of up to 64 robots have always run.
+// NH: the NH-ORCA rule -- lanes 0 and 1 own the two heading lines, the sectors and the neighbours move up by two lanes (so
+// max_neighbors <= kNhMaxNeighbors = 46: lane 63 stays the top-K merge's spare), and the solve runs twice: free (the heading lanes
+// invalid, max_speed), then tracked (all lanes, u_cap).  Otherwise `nh` is empty and nothing of it is compiled.
+template <bool BIG, bool NH>
 __global__ __launch_bounds__(kBlock) void orca_kernel(const OrcaArgs a, const uint8_t* __restrict__ mask, float* __restrict__ actions,
-                                                      float* __restrict__ vel, const std::conditional_t<BIG, OrcaHash, OrcaNoHash> hsh) {
+                                                      float* __restrict__ vel, const std::conditional_t<BIG, OrcaHash, OrcaNoHash> hsh,
+                                                      const std::conditional_t<NH, NhArgs, OrcaNoNh> nh) {
+    constexpr int kFirst = NH ? kNhHeadingLines : 0;        // the lane of sector 0
+    constexpr int kNb = kFirst + kOrcaSectors;              // the lane of the nearest neighbour
     const int lane = threadIdx.x & (kWave - 1);
     const int n = blockIdx.x * kRobotsPerBlock + (threadIdx.x >> 6);
     if (n >= a.N) return;                    // (wave-uniform, like every branch around a shuffle below)
@@ -263,13 +311,13 @@ __global__ __launch_bounds__(kBlock) void orca_kernel(const OrcaArgs a, const ui
             best_b = b;
         }
     }
-    const float sec_r = __shfl(best_r, (4 * lane) & (kWave - 1));
-    const int sec_b = __shfl(best_b, (4 * lane) & (kWave - 1));
+    const float sec_r = __shfl(best_r, (4 * (lane - kFirst)) & (kWave - 1));
+    const int sec_b = __shfl(best_b, (4 * (lane - kFirst)) & (kWave - 1));
 
     int src = -1;
     float nbx, nby, nvx, nvy;
     if constexpr (!BIG) {
-        // ---- the neighbours: rank among the candidates by (dist2, index), then lane 16 + rank fetches its neighbour
+        // ---- the neighbours: rank among the candidates by (dist2, index), then lane kNb + rank fetches its neighbour
         const float ddx = jx - px, ddy = jy - py;
         const float d2 = dot2(ddx, ddy, ddx, ddy);
         const bool cand = lane < a.R && lane != local && d2 < q.neighbor_dist * q.neighbor_dist;
@@ -281,7 +329,7 @@ __global__ __launch_bounds__(kBlock) void orca_kernel(const OrcaArgs a, const ui
         }
         for (unsigned long long m = __ballot(cand && rank < q.max_neighbors); m; m &= m - 1) {
             const int o = __ffsll((long long)m) - 1;
-            if (lane == kOrcaSectors + __shfl(rank, o)) src = o;
+            if (lane == kNb + __shfl(rank, o)) src = o;
         }
         const int from = src < 0 ? 0 : src;
         nbx = __shfl(jx, from);
@@ -289,10 +337,10 @@ __global__ __launch_bounds__(kBlock) void orca_kernel(const OrcaArgs a, const ui
         nvx = __shfl(jvx, from);
         nvy = __shfl(jvy, from);
     } else {
-        // ---- the neighbours from the lidar hash; lane 16 + rank takes the neighbour of that rank and loads its record once
+        // ---- the neighbours from the lidar hash; lane kNb + rank takes the neighbour of that rank and loads its record once
         const Key best = hashed_neighbours(a, hsh, lane, n, world, px, py);
-        const Key mine = __shfl(best, (lane - kOrcaSectors) & (kWave - 1));
-        if (lane >= kOrcaSectors && mine != kOrcaNoKey) src = orca_key_index(mine);
+        const Key mine = __shfl(best, (lane - kNb) & (kWave - 1));
+        if (lane >= kNb && mine != kOrcaNoKey) src = orca_key_index(mine);
         const int from = src < 0 ? n : src;
         nbx = a.pose[3 * (size_t)from];
         nby = a.pose[3 * (size_t)from + 1];
@@ -305,8 +353,8 @@ __global__ __launch_bounds__(kBlock) void orca_kernel(const OrcaArgs a, const ui
     // ---- one constraint per lane
     bool valid;
     float rpx = 0.0f, rpy = 0.0f, rvx = vx, rvy = vy, R, inv_t, resp;
-    if (lane < kOrcaSectors) {
-        valid = sec_b != 0x7fffffff;
+    if (lane < kNb) {
+        valid = lane >= kFirst && sec_b != 0x7fffffff;
         if (valid) orca_static_rel(sec_r, s, c, a.beam_cos[sec_b], a.beam_sin[sec_b], &rpx, &rpy);
         R = q.radius;
         inv_t = 1.0f / q.time_horizon_obst;
@@ -326,35 +374,39 @@ __global__ __launch_bounds__(kBlock) void orca_kernel(const OrcaArgs a, const ui
 
     // ---- solve
     float rx, ry;
-    const int short_at = lp2_wave(line, valid, lane, q.max_speed, ox, oy, false, &rx, &ry);
-    if (short_at < kWave) {                  // LP3: static lines stay hard, robot lines are relaxed evenly
-        float distance = 0.0f;
-        unsigned long long consider = lanes_from(short_at);
-        for (;;) {
-            const unsigned long long m = __ballot(valid && orca_violation(line, rx, ry) > distance) & consider;
-            if (!m) break;
-            const int i = __ffsll((long long)m) - 1;
-            consider = lanes_from(i + 1);
-            const OrcaLine li = line_of_lane(line, i);
-            OrcaLine pl = line;
-            bool pvalid = valid;
-            if (lane >= kOrcaSectors) pvalid = valid && lane < i && orca_project(li, line, &pl);
-            float tx, ty;
-            if (lp2_wave(pl, pvalid, lane, q.max_speed, -li.dy, li.dx, true, &tx, &ty) == kWave) {
-                rx = tx;
-                ry = ty;
+    if constexpr (!NH) {
+        solve_wave(line, valid, lane, kNb, q.max_speed, ox, oy, &rx, &ry);
+        if (lane == 0) {
+            float v, w;
+            orca_command(rx, ry, s, c, q.max_speed, q.k_omega, &v, &w);
+            *reinterpret_cast<float2*>(actions + 2 * (size_t)n) = make_float2(v, w);
+            if (vel) {
+                vel[2 * (size_t)n] = rx;
+                vel[2 * (size_t)n + 1] = ry;
             }
-            distance = orca_violation(li, rx, ry);
         }
-    }
-
-    if (lane == 0) {
-        float v, w;
-        orca_command(rx, ry, s, c, q.max_speed, q.k_omega, &v, &w);
-        *reinterpret_cast<float2*>(actions + 2 * (size_t)n) = make_float2(v, w);
-        if (vel) {
-            vel[2 * (size_t)n] = rx;
-            vel[2 * (size_t)n + 1] = ry;
+    } else {
+        // ---- the free solve decides what the tracked solve aims at; lanes 0 and 1 take the heading lines for the second
+        float s1x, s1y;
+        solve_wave(line, valid, lane, kNb, q.max_speed, ox, oy, &s1x, &s1y);
+        float turn;
+        const bool track = nhorca_aim(s1x, s1y, ox, oy, s, c, nh.cm, &turn);
+        OrcaLine left, right;
+        nhorca_heading_lines(s, c, nh.sm, nh.cm, &left, &right);
+        if (lane < kFirst) {
+            line = lane == 0 ? left : right;
+            valid = true;
+        }
+        solve_wave(line, valid, lane, kNb, nh.u_cap, track ? ox : 0.0f, track ? oy : 0.0f, &rx, &ry);
+        if (lane == 0) {
+            float v, w;
+            const int mode = nhorca_command(rx, ry, s, c, track, turn, q.max_speed, nh.track_time, &v, &w);
+            *reinterpret_cast<float2*>(actions + 2 * (size_t)n) = make_float2(v, w);
+            if (vel) {
+                vel[2 * (size_t)n] = rx;
+                vel[2 * (size_t)n + 1] = ry;
+            }
+            if (nh.mode) nh.mode[n] = mode;
         }
     }
 }
@@ -374,15 +426,30 @@ OrcaArgs orca_args(const EnvView& e, const OrcaParams& p) {
 
 void launch_orca(const EnvView& e, const OrcaParams& p, const uint8_t* mask, float* actions, float* vel, hipStream_t s) {
     const OrcaArgs a = orca_args(e, p);
-    hipLaunchKernelGGL(orca_kernel<false>, dim3((e.N + kRobotsPerBlock - 1) / kRobotsPerBlock), dim3(kBlock), 0, s, a, mask, actions, vel,
-                       OrcaNoHash{});
+    hipLaunchKernelGGL((orca_kernel<false, false>), dim3((e.N + kRobotsPerBlock - 1) / kRobotsPerBlock), dim3(kBlock), 0, s, a, mask, actions,
+                       vel, OrcaNoHash{}, OrcaNoNh{});
 }
 
 void launch_orca_big(const EnvView& e, const OrcaParams& p, const uint8_t* mask, float* actions, float* vel, hipStream_t s) {
     const OrcaArgs a = orca_args(e, p);
     const OrcaHash hsh{e.bw_lstart, e.bw_lsorted, e.bw_lmask, orca_rings(p.neighbor_dist)};
-    hipLaunchKernelGGL(orca_kernel<true>, dim3((e.N + kRobotsPerBlock - 1) / kRobotsPerBlock), dim3(kBlock), 0, s, a, mask, actions, vel,
-                       hsh);
+    hipLaunchKernelGGL((orca_kernel<true, false>), dim3((e.N + kRobotsPerBlock - 1) / kRobotsPerBlock), dim3(kBlock), 0, s, a, mask, actions,
+                       vel, hsh, OrcaNoNh{});
+}
+
+void launch_nhorca(const EnvView& e, const NhOrcaParams& p, bool big, const uint8_t* mask, float* actions, float* vel, int32_t* mode,
+                   hipStream_t s) {
+    const NhOrcaDerived d = nhorca_derive(p);
+    OrcaArgs a = orca_args(e, p.o);
+    a.p.radius = d.radius;
+    const NhArgs nh{d.sm, d.cm, d.u_cap, p.track_time, mode};
+    const dim3 grid((e.N + kRobotsPerBlock - 1) / kRobotsPerBlock);
+    if (big) {
+        const OrcaHash hsh{e.bw_lstart, e.bw_lsorted, e.bw_lmask, orca_rings(p.o.neighbor_dist)};
+        hipLaunchKernelGGL((orca_kernel<true, true>), grid, dim3(kBlock), 0, s, a, mask, actions, vel, hsh, nh);
+    } else {
+        hipLaunchKernelGGL((orca_kernel<false, true>), grid, dim3(kBlock), 0, s, a, mask, actions, vel, OrcaNoHash{}, nh);
+    }
 }
 
 }  // namespace mrca

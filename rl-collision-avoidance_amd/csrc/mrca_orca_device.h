@@ -422,21 +422,15 @@ MRCA_HD int orca_neighbours_hashed(const int32_t* lstart, const int32_t* lsorted
     return kept;
 }
 
-// The rule for robot `local` of one world GIVEN its kept neighbours nb[0 .. kept) (indices inside the world, nearest first).
-// pose[R][3], sincos[R][2] = the head records' (sin, cos), speed_gt[R][2], goal = this robot's, ranges / hits = its newest scan
-// row and hit words, gid = its index in the env.
-// -> (v, omega) in cmd, the holonomic velocity in vel; lines_out / counts (or nullptr): the constraints, [n, n_static]
-MRCA_HD void orca_robot_with(const OrcaParams& q, const int* nb, int kept, int local, uint32_t gid, uint32_t k0, uint32_t k1,
-                             const float* pose, const float* sincos, const float* speed_gt, const float* goal, const float* ranges,
-                             const unsigned long long* hits, int beams, const float* beam_cos, const float* beam_sin, float* cmd,
-                             float* vel, OrcaLine* lines_out, int* counts, int* diag) {
-    OrcaLine lines[kOrcaMaxLines];
+// The constraints of robot `local` of one world in contract order (the static lines of its newest scan row, then its kept
+// neighbours nb[0 .. kept), nearest first), every disc of radius `radius`.  -> their count; *n_static_out: the static ones
+MRCA_HD int orca_lines(const OrcaParams& q, float radius, const int* nb, int kept, int local, const float* pose, const float* sincos,
+                       const float* speed_gt, const float* ranges, const unsigned long long* hits, int beams, const float* beam_cos,
+                       const float* beam_sin, OrcaLine* lines, int* n_static_out) {
     const float px = pose[3 * local], py = pose[3 * local + 1];
     const float s = sincos[2 * local], c = sincos[2 * local + 1];
     const float sp = speed_gt[2 * local];
     const float vx = sp * c, vy = sp * s;
-    float ox, oy;
-    orca_pref_velocity(q, gid, k0, k1, px, py, goal[0], goal[1], &ox, &oy);
     int n = 0;
     float br[kOrcaSectors];
     int bb[kOrcaSectors];
@@ -446,17 +440,35 @@ MRCA_HD void orca_robot_with(const OrcaParams& q, const int* nb, int kept, int l
         if (bb[k] < 0) continue;
         float rx, ry;
         orca_static_rel(br[k], s, c, beam_cos[bb[k]], beam_sin[bb[k]], &rx, &ry);
-        orca_constraint(rx, ry, vx, vy, vx, vy, q.radius, inv_to, 1.0f, &lines[n++]);
+        orca_constraint(rx, ry, vx, vy, vx, vy, radius, inv_to, 1.0f, &lines[n++]);
     }
-    const int n_static = n;
+    *n_static_out = n;
     const float inv_t = 1.0f / q.time_horizon;
     for (int k = 0; k < kept; ++k) {
         const int j = nb[k];
         const float sj = speed_gt[2 * j];
         const float vjx = sj * sincos[2 * j + 1], vjy = sj * sincos[2 * j];
-        orca_constraint(pose[3 * j] - px, pose[3 * j + 1] - py, vx - vjx, vy - vjy, vx, vy, 2.0f * q.radius, inv_t, q.responsibility,
+        orca_constraint(pose[3 * j] - px, pose[3 * j + 1] - py, vx - vjx, vy - vjy, vx, vy, 2.0f * radius, inv_t, q.responsibility,
                         &lines[n++]);
     }
+    return n;
+}
+
+// The rule for robot `local` of one world GIVEN its kept neighbours nb[0 .. kept) (indices inside the world, nearest first).
+// pose[R][3], sincos[R][2] = the head records' (sin, cos), speed_gt[R][2], goal = this robot's, ranges / hits = its newest scan
+// row and hit words, gid = its index in the env.
+// -> (v, omega) in cmd, the holonomic velocity in vel; lines_out / counts (or nullptr): the constraints, [n, n_static]
+MRCA_HD void orca_robot_with(const OrcaParams& q, const int* nb, int kept, int local, uint32_t gid, uint32_t k0, uint32_t k1,
+                             const float* pose, const float* sincos, const float* speed_gt, const float* goal, const float* ranges,
+                             const unsigned long long* hits, int beams, const float* beam_cos, const float* beam_sin, float* cmd,
+                             float* vel, OrcaLine* lines_out, int* counts, int* diag) {
+    OrcaLine lines[kOrcaMaxLines];
+    const float s = sincos[2 * local], c = sincos[2 * local + 1];
+    float ox, oy;
+    orca_pref_velocity(q, gid, k0, k1, pose[3 * local], pose[3 * local + 1], goal[0], goal[1], &ox, &oy);
+    int n_static;
+    const int n = orca_lines(q, q.radius, nb, kept, local, pose, sincos, speed_gt, ranges, hits, beams, beam_cos, beam_sin, lines,
+                             &n_static);
     float rx, ry;
     orca_solve(lines, n, n_static, q.max_speed, ox, oy, &rx, &ry, diag);
     vel[0] = rx;

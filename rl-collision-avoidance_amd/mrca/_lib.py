@@ -32,6 +32,7 @@ EXPORTS = ["mrca_abi_version", "mrca_last_error", "mrca_arena_bytes", "mrca_crea
            "mrca_policy_heads", "mrca_policy_heads_backward_scratch", "mrca_policy_heads_backward", "mrca_relu_cat",
            "mrca_relu_cat_backward", "mrca_policy_heads_backward_bias", "mrca_relu_cat_backward_bias_scratch",
            "mrca_relu_cat_backward_bias", "mrca_render", "mrca_orca_default_params", "mrca_orca_actions", "mrca_orca_actions_any",
+           "mrca_nhorca_default_params", "mrca_nhorca_actions",
            "mrca_dwa_default_params", "mrca_dwa_actions", "mrca_scan_noise_default_params", "mrca_scan_noise",
            "mrca_hybrid_default_params", "mrca_hybrid_actions",
            "mrca_safe_policy_default_params", "mrca_hybrid_plan", "mrca_hybrid_commit", "mrca_lidar_features_scaled",
@@ -59,6 +60,11 @@ class OrcaParamsStruct(C.Structure):
     """include/mrca_env.h: mrca_orca_params"""
     _fields_ = [(k, C.c_float) for k in ("radius", "neighbor_dist", "time_horizon", "time_horizon_obst", "obst_dist", "v_pref",
                                          "max_speed", "responsibility", "k_omega", "jitter")] + [("max_neighbors", C.c_int32)]
+
+
+class NhOrcaParamsStruct(C.Structure):
+    """include/mrca_env.h: mrca_nhorca_params (mrca_orca_params' fields in their layout, then the two of the tracking)"""
+    _fields_ = OrcaParamsStruct._fields_ + [("track_error", C.c_float), ("track_time", C.c_float)]
 
 
 class DwaParamsStruct(C.Structure):
@@ -188,6 +194,8 @@ def load(path=None):
     lib.mrca_orca_default_params.argtypes = [C.POINTER(OrcaParamsStruct)]
     lib.mrca_orca_actions.argtypes = [C.c_void_p, C.POINTER(OrcaParamsStruct), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.mrca_orca_actions_any.argtypes = lib.mrca_orca_actions.argtypes
+    lib.mrca_nhorca_default_params.argtypes = [C.POINTER(NhOrcaParamsStruct)]
+    lib.mrca_nhorca_actions.argtypes = [C.c_void_p, C.POINTER(NhOrcaParamsStruct), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.mrca_dwa_default_params.argtypes = [C.POINTER(DwaParamsStruct)]
     lib.mrca_dwa_actions.argtypes = [C.c_void_p, C.POINTER(DwaParamsStruct), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.mrca_scan_noise_default_params.argtypes = [C.POINTER(ScanNoiseParamsStruct)]

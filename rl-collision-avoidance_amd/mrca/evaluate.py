@@ -84,6 +84,35 @@ def orca_policy_fn(env, params=None, first=None, other=None):
     return mixed
 
 
+def nhorca_policy_fn(env, params=None, first=None, other=None):
+    """The NH-ORCA baseline controller on the device (``VecStageWorld.nhorca_actions``), used like ``orca_policy_fn``: every robot,
+    or with ``first = K`` and ``other`` the robots with local index < K (group "nhorca") beside ``other``'s.
+    ``fn.mode_shares()`` -> the share of its live robot-ticks (robots without a terminal event yet) spent in each mode; the
+    counts are kept on the device and read when that is called."""
+    from .nhorca import MODES
+    codes = torch.arange(len(MODES), dtype=torch.int32, device=env.device)
+    counts = torch.zeros(len(MODES), dtype=torch.int64, device=env.device)
+    mode = torch.zeros(env.N, dtype=torch.int32, device=env.device)
+    mask = None if first is None else (torch.arange(env.N, device=env.device) % env.R < int(first)).to(torch.uint8).contiguous()
+
+    def fn(obs, local_goal, speed):
+        a = None if mask is None else other(obs, local_goal, speed).float().contiguous().clone()
+        a = env.nhorca_actions(params, mask=mask, out=a, mode=mode)
+        live = env.first_result == 0 if mask is None else (env.first_result == 0) & mask.bool()
+        counts.add_(((mode.unsqueeze(1) == codes) & live.unsqueeze(1)).sum(dim=0))
+        return a
+    fn.wants_obs = False if mask is None else getattr(other, "wants_obs", True)
+    if mask is not None:
+        fn.groups = {"nhorca": mask.bool(), "policy": ~mask.bool()}
+
+    def mode_shares():
+        c = counts.tolist()
+        total = sum(c)
+        return {name: (n / total if total else None) for name, n in zip(MODES, c)}
+    fn.mode_shares = mode_shares
+    return fn
+
+
 def dwa_policy_fn(env, params=None, first=None, other=None, other_name="policy", steer=False):
     """The DWA baseline controller on the device (``VecStageWorld.dwa_actions``): it reads the env's own fields (each robot's
     scan, local goal and speed), so it wants no observation stack.  ``first = K`` with ``other``: robots with local index < K
@@ -366,6 +395,16 @@ def main():
     ap.add_argument("--orca-first", type=int, default=None, metavar="K",
                     help="robots with local index < K are driven by ORCA, the rest by --policy (or the stand-in); the metrics "
                          "are reported for both groups")
+    ap.add_argument("--nh-orca", action="store_true",
+                    help="every robot driven by the NH-ORCA baseline controller on the device (mrca_nhorca_actions: ORCA over the "
+                         "velocities a unicycle tracks within a bound, worlds of any size); no --policy is needed; the result "
+                         "line gains nhorca_params and nhorca_modes (the share of live robot-ticks per mode); excluded where "
+                         "--orca is")
+    ap.add_argument("--nh-orca-param", action="append", default=[], metavar="NAME=VALUE",
+                    help="a field of mrca_nhorca_params, e.g. track_error=0.1 (repeatable)")
+    ap.add_argument("--nh-orca-first", type=int, default=None, metavar="K",
+                    help="robots with local index < K are driven by NH-ORCA, the rest by --policy (or the stand-in); the metrics "
+                         "are reported for both groups")
     ap.add_argument("--dwa", action="store_true", help="every robot driven by the DWA baseline controller on the device "
                                                        "(mrca_dwa_actions: sensor-level, worlds of any size); no --policy is needed")
     ap.add_argument("--dwa-param", action="append", default=[], metavar="NAME=VALUE",
@@ -401,6 +440,13 @@ def main():
     a = ap.parse_args()
     if a.fused_bf16:
         a.fused = True
+    if (a.nh_orca or a.nh_orca_first is not None) and (a.orca or a.orca_first is not None):
+        ap.error("--nh-orca / --nh-orca-first and --orca / --orca-first are two baselines for the same robots: choose one")
+    if a.nh_orca_param and not (a.nh_orca or a.nh_orca_first is not None):
+        ap.error("--nh-orca-param goes with --nh-orca or --nh-orca-first")
+    # (NH-ORCA steers at MRCA_F_GOAL like ORCA: what excludes --orca / --orca-first below excludes it)
+    orca_all = a.orca or a.nh_orca
+    orca_first = a.orca_first if a.nh_orca_first is None else a.nh_orca_first
     from .vec_env import VecStageWorld
     doorway = a.scenario == "doorway"
     if doorway and (a.radius != 25.0 or a.one_circle is not None or a.stage_resolution):
@@ -411,11 +457,11 @@ def main():
         ap.error("--planner-param goes with --planner")
     if a.los_param and not a.planner_los:
         ap.error("--los-param goes with --planner-los")
-    if a.planner_los and (a.orca or a.orca_first is not None):
+    if a.planner_los and (orca_all or orca_first is not None):
         ap.error("--planner-los: ORCA steers at the goal in the world frame (MRCA_F_GOAL), it takes no subgoal: not with --orca / "
-                 "--orca-first")
+                 "--orca-first / --nh-orca / --nh-orca-first")
     steer = a.planner_los
-    if a.planner and not a.planner_los and (a.orca or a.dwa or a.hybrid or a.hybrid_safe or a.orca_first is not None or a.dwa_first is not None):
+    if a.planner and not a.planner_los and (orca_all or a.dwa or a.hybrid or a.hybrid_safe or orca_first is not None or a.dwa_first is not None):
         ap.error("--planner hands the subgoal to a controller that takes the local goal as an argument (--policy, the stand-in): the "
                  "kernels of --orca / --dwa / --hybrid / --hybrid-safe read the env's own local goal")
     if a.hybrid_safe_param and not a.hybrid_safe:
@@ -423,7 +469,7 @@ def main():
     if a.hybrid_safe:
         if a.hybrid:
             ap.error("--hybrid-safe is hybrid control in the paper's form, --hybrid the command scaling: choose one")
-        if a.orca or a.dwa:
+        if orca_all or a.dwa:
             ap.error("--hybrid-safe rescales the scan a checkpoint sees: not with --orca / --dwa (use --orca-first / --dwa-first "
                      "for mixed groups)")
         if not a.policy:
@@ -470,7 +516,7 @@ def main():
             except ValueError as e:
                 ap.error(str(e))
             fn = safe_policy_fn(pol, env, hybrid_params, safe_params, fused_bf16=a.fused_bf16,
-                                skip_first=max(a.orca_first or 0, a.dwa_first or 0), steer=steer)
+                                skip_first=max(orca_first or 0, a.dwa_first or 0), steer=steer)
             safe_fn, name = fn, f"hybrid control in the paper's form (mrca_hybrid_plan, mrca_hybrid_commit) around {name}"
     elif doorway:
         fn, name = go_to_goal_policy, "go-to-goal stand-in (no checkpoint given)"
@@ -500,15 +546,27 @@ def main():
             fn, name = orca_policy_fn(env, params), f"ORCA baseline ({orca_call})"
         else:
             fn, name = orca_policy_fn(env, params, first=a.orca_first, other=fn), f"ORCA for local index < {a.orca_first}, else {name}"
-    if a.dwa and (a.orca or a.orca_first is not None):
-        ap.error("--dwa drives every robot: with --orca use --dwa-first K")
+    if a.nh_orca or a.nh_orca_first is not None:
+        from .nhorca import NhOrcaParams
+        try:
+            nh_params = NhOrcaParams.from_assignments(a.nh_orca_param)
+        except ValueError as e:
+            ap.error(str(e))
+        if a.nh_orca_first is None:
+            fn, name = nhorca_policy_fn(env, nh_params), "NH-ORCA baseline (mrca_nhorca_actions)"
+        else:
+            fn = nhorca_policy_fn(env, nh_params, first=a.nh_orca_first, other=fn)
+            name = f"NH-ORCA for local index < {a.nh_orca_first}, else {name}"
+        nh_fn = fn
+    if a.dwa and (orca_all or orca_first is not None):
+        ap.error("--dwa drives every robot: with --orca / --nh-orca use --dwa-first K")
     if a.dwa or a.dwa_first is not None:
         from .dwa import DwaParams
         dwa_params = DwaParams.from_assignments(a.dwa_param)
         if a.dwa_first is None:
             fn, name = dwa_policy_fn(env, dwa_params, steer=steer), "DWA baseline (mrca_dwa_actions)"
         else:
-            fn = dwa_policy_fn(env, dwa_params, first=a.dwa_first, other=fn, other_name="orca" if a.orca else "policy", steer=steer)
+            fn = dwa_policy_fn(env, dwa_params, first=a.dwa_first, other=fn, other_name="orca" if a.orca else ("nhorca" if a.nh_orca else "policy"), steer=steer)
             name = f"DWA for local index < {a.dwa_first}, else {name}"
     if a.hybrid_param and not (a.hybrid or a.hybrid_safe):
         ap.error("--hybrid-param goes with --hybrid or --hybrid-safe")
@@ -541,6 +599,10 @@ def main():
     if a.orca or a.orca_first is not None:
         import dataclasses
         out["orca_params"] = dataclasses.asdict(params)
+    if a.nh_orca or a.nh_orca_first is not None:
+        import dataclasses
+        out["nhorca_params"] = dataclasses.asdict(nh_params)
+        out["nhorca_modes"] = nh_fn.mode_shares()
     if a.dwa or a.dwa_first is not None:
         import dataclasses
         out["dwa_params"] = dataclasses.asdict(dwa_params)

@@ -280,6 +280,23 @@ class VecStageWorld:
                                            self._stream()), name)
         return out
 
+    def nhorca_actions(self, params=None, mask=None, out=None, vel=None, mode=None):
+        """(v, omega) of the NH-ORCA baseline controller (mrca_nhorca_actions) for every robot, as a float32[N,2] tensor on the
+        env's device: ORCA restricted to the holonomic velocities a unicycle tracks within ``track_error`` metres, every disc grown
+        by that much.  One launch on the current stream, nothing synchronises, nothing of the env is written:
+        ``env.step(env.nhorca_actions())`` is a closed-loop scripted tick.  ``params``: an ``nhorca.NhOrcaParams`` (default: the
+        library's); ``mask`` and ``out``: as ``orca_actions``; ``vel``: a float32[N,2] tensor that takes the velocity of the
+        tracked solve; ``mode``: an int32[N] tensor that takes what each robot does (0 tracks its preferred velocity, 1 turns in
+        place, 2 stands still, 3 moves although it should turn).  Worlds of any size, under ``orca_actions``' rules for worlds of
+        more than 64 robots."""
+        if out is None:
+            out = torch.zeros((self.N, 2), dtype=torch.float32, device=self.device)
+        st = None if params is None else params.struct()
+        _lib.check(self.lib.mrca_nhorca_actions(self._h, None if st is None else C.byref(st), self._ptr(mask, torch.uint8, self.N),
+                                                self._ptr(out, torch.float32, 2 * self.N), self._ptr(vel, torch.float32, 2 * self.N),
+                                                self._ptr(mode, torch.int32, self.N), self._stream()), "mrca_nhorca_actions")
+        return out
+
     def dwa_actions(self, params=None, mask=None, out=None, choice=None, score=None, goal=None):
         """(v, omega) of the DWA baseline controller (mrca_dwa_actions) for every robot, as a float32[N,2] tensor on the env's
         device: the sensor-level counterpart of ``orca_actions`` -- it reads each robot's newest scan, local goal and own speed
