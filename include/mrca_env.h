@@ -33,7 +33,9 @@
 extern "C" {
 #endif
 
-/* 6, additive: mrca_nhorca_actions, mrca_nhorca_default_params (the NH-ORCA baseline: ORCA over the holonomic velocities a
+/* 6, additive: mrca_scatter, mrca_scatter_default_params (a scenario sampler: per world, separated random starts and goals clear
+ * of the map, as mrca_reset's poses_dev / goals_dev).
+ * 6, additive: mrca_nhorca_actions, mrca_nhorca_default_params (the NH-ORCA baseline: ORCA over the holonomic velocities a
  * unicycle tracks within a bound).
  * 6, additive: mrca_subgoals_los, mrca_los_default_params (the planner's per-tick call with line-of-sight smoothing);
  * mrca_dwa_actions_goal, mrca_hybrid_actions_goal, mrca_hybrid_plan_goal (the sensor-level controllers steered at rows the caller
@@ -473,6 +475,48 @@ typedef struct mrca_scan_noise_params {
 int mrca_scan_noise_default_params(mrca_scan_noise_params* out);
 int mrca_scan_noise(mrca_env* env, const mrca_scan_noise_params* params /* host, NULL = defaults */,
                     const uint8_t* mask_dev /* u8[N] or NULL = all */, void* stream);
+
+/* The scenario sampler: what mrca_reset(env, mask, poses_dev, goals_dev) accepts, produced where the state lives -- per world a
+ * DIFFERENT set of starts and goals that keep a stated distance from each other and from the map, the same bits for the same
+ * (seed, draw).  The env's own samplers (MRCA_RESET_DISC / _REGION) restate the reference and test neither the map nor the other
+ * robots.  The rule (csrc/mrca_scatter_device.h, separately rounded fp32 steps in a fixed order; tests/scatter_ref.py restates
+ * it in NumPy), with box[i] = (sx0, sy0, sx1, sy1, gx0, gy0, gx1, gy1) per LOCAL index i, shared by all worlds:
+ *   candidate k of robot n:  U = philox4x32_10(n, draw, k, word, seed), word 3 for starts and 7 for goals (the reset sampler
+ *       uses the words 0 and 1, the noise model words with low bits 2: a word with low bits 3 meets neither);
+ *       x = x0 + (x1 - x0) * u01(U.x), y likewise with U.y; a start's heading is wrap(2 pi * u01(U.z)).  A box with x0 == x1
+ *       pins that coordinate: this is how table robots mix with random ones.
+ *   clear of the map: the Chebyshev distance (map cells) from the point's cell to the nearest occupied cell must be
+ *       > clear_cells.  For a cell outside the map, clamped into it to c', the value is max(that of c', cell distance to c'): a
+ *       lower bound of the true distance -- the test may refuse a valid point and never accepts an invalid one.
+ *   apart from a point already placed: !(dx * dx + dy * dy < sep * sep); the goal band likewise on the squares.
+ *   In each world, for i = 0 .. R-1 in order, start_i is the candidate of the LEAST k < max_tries that is clear and min_sep
+ *   apart from start_j for every j < i; then, for i = 0 .. R-1, goal_i is the candidate of the least k that is clear, lies
+ *   goal_min .. goal_max from start_i and goal_sep apart from goal_j for every j < i.  If no k qualifies the robot takes
+ *   candidate max_tries - 1 as it is, its tries entry is -1, and later robots treat it as placed; otherwise tries = k + 1.
+ *   The result hangs on (seed, draw, boxes, params, map) and on nothing else: not on the launch shape or on the other worlds.
+ *   params     host; NULL = mrca_scatter_default_params: min_sep 1, goal_sep 1, goal_min 5, goal_max 1e4, clear_cells 4,
+ *              max_tries 1024, draw 0
+ *   boxes_dev  f32[R,8], device memory and NOT validated on the device: its producer guarantees finite values, x0 <= x1,
+ *              y0 <= y1 and |coordinate| <= 1e4 (a value that is not a number fails every test: the robot reports -1)
+ *   poses_dev  f32[N,3] out;  goals_dev f32[N,2] out;  tries_dev i32[N,2] out (start, goal) or NULL
+ * Asynchronous on `stream`, ONE launch (a workgroup per world, the candidates across its lanes), capturable.  Valid BEFORE the
+ * first mrca_reset: it reads the map, the geometry and the seed, and writes its three buffers and nothing of the env.
+ * robots_per_world <= 4096 (a world's placed points are held in 32 KB of LDS): more gives MRCA_ERR_UNSUPPORTED.  Validated
+ * before the first HIP call (MRCA_ERR_INVALID): every float finite; min_sep >= 0.6 (two 0.44 x 0.38 footprints cannot meet with
+ * centres 2 x 0.2907 m apart); goal_sep >= 0; 0 <= goal_min <= goal_max; clear_cells 0..254; max_tries 1..65536; boxes_dev,
+ * poses_dev, goals_dev not NULL; poses_dev and tries_dev 4-byte, goals_dev 8-byte aligned. */
+typedef struct mrca_scatter_params {
+    float min_sep;        /* starts of one world: centre distance >= this [m]                 */
+    float goal_sep;       /* goals of one world likewise (0: no test)                          */
+    float goal_min, goal_max; /* goal_min <= |goal - own start| <= goal_max                    */
+    int32_t clear_cells;  /* starts and goals: Chebyshev distance to an occupied map cell > this (0..254) */
+    int32_t max_tries;    /* 1..65536 candidates per start and per goal                        */
+    uint32_t draw;        /* scenario number: another draw, another set of scenarios           */
+} mrca_scatter_params;
+int mrca_scatter_default_params(mrca_scatter_params* out);
+int mrca_scatter(mrca_env* env, const mrca_scatter_params* params /* host, NULL = defaults */,
+                 const float* boxes_dev /* f32[R,8] */, float* poses_dev /* f32[N,3] out */,
+                 float* goals_dev /* f32[N,2] out */, int32_t* tries_dev /* i32[N,2] or NULL */, void* stream);
 
 /* Hybrid control behind a policy, after Fan, Long, Liu, Pan (IJRR 2020, Sec. 5): per robot and tick, which of three drives it --
  * a PID law where nothing stands between it and its goal, the policy's command with v scaled down where something is

@@ -24,7 +24,7 @@ FLAGS=(--offload-arch=gfx950 -O3 -std=c++17 -fPIC
 pids=()
 obj="$(mktemp -d)"
 trap 'rm -rf "${obj}"' EXIT
-for src in mrca_kernels mrca_raycast_ticks mrca_abi mrca_abi_controllers mrca_policy mrca_policy_bwd mrca_policy_tail mrca_ppo_loss mrca_adam mrca_rollout_store mrca_policy_heads mrca_policy_bf16 mrca_policy_bf16_rows mrca_policy_bf16_bwd mrca_render mrca_orca mrca_dwa mrca_noise mrca_hybrid mrca_safe mrca_planner; do
+for src in mrca_kernels mrca_raycast_ticks mrca_abi mrca_abi_controllers mrca_policy mrca_policy_bwd mrca_policy_tail mrca_ppo_loss mrca_adam mrca_rollout_store mrca_policy_heads mrca_policy_bf16 mrca_policy_bf16_rows mrca_policy_bf16_bwd mrca_render mrca_orca mrca_dwa mrca_noise mrca_scatter mrca_hybrid mrca_safe mrca_planner; do
     per=()
     [[ "${src}" == "mrca_policy" ]] && per=(-mllvm --amdgpu-mfma-vgpr-form)
     # the env kernels: the first 14 dwords of a kernel's arguments arrive in SGPRs (gfx950's kernarg preload) -- move_kernel and

@@ -1,5 +1,5 @@
 // mrca_abi_controllers.hip -- host side of include/mrca_env.h for what acts on an env between its ticks: the renderer, the ORCA,
-// NH-ORCA and DWA baselines, the lidar noise model, hybrid control and the global planner.  Every entry point has one shape -- take the
+// NH-ORCA and DWA baselines, the lidar noise model, the scenario sampler, hybrid control and the global planner.  Every entry point has one shape -- take the
 // params (the caller's or the defaults) through their table, check the pointers, then the env, then launch -- and the pieces
 // of that shape are stated once, below.  What can be judged without the env is judged first, in the order it stands here: a
 // caller's mistake is named whatever else is wrong.  The env itself is mrca_abi.hip's (mrca_env_state.h).
@@ -18,6 +18,7 @@
 #include "mrca_safe.h"
 #include "mrca_planner.h"
 #include "mrca_render.h"
+#include "mrca_scatter.h"
 #include "mrca_env_state.h"      // (last: its `fail` is a macro)
 
 using namespace mrca::env_state;
@@ -160,6 +161,19 @@ static_assert(offsetof(Los, reach) == offsetof(mrca::LosParams, reach), "mrca_lo
 // (mrca_subgoals_los keeps a planning cell as two 16-bit halves of a word: mrca_create takes no map side above 16384 cells)
 const Rule kLosRules[] = {ROW(Los, reach, kIntRange, 1, mrca::kLosMaxReach)};
 int check(const char* fn, const Los& p) { return check_rules(fn, &p, kLosRules); }
+
+using Scatter = mrca_scatter_params;
+static_assert(offsetof(Scatter, draw) == offsetof(mrca::ScatterParams, draw), "mrca_scatter_params and mrca::ScatterParams are one layout");
+const Rule kScatterFirst[] = {
+    ROW(Scatter, min_sep, kFinite), ROW(Scatter, goal_sep, kFinite), ROW(Scatter, goal_min, kFinite), ROW(Scatter, goal_max, kFinite),
+    ROW(Scatter, min_sep, kAtLeast, mrca::kScatterMinSep), ROW(Scatter, goal_sep, kAtLeast, 0), ROW(Scatter, goal_min, kAtLeast, 0)};
+const Rule kScatterRest[] = {
+    ROW(Scatter, clear_cells, kIntRange, 0, mrca::kScatterMaxClear), ROW(Scatter, max_tries, kIntRange, 1, mrca::kScatterMaxTries)};
+int check(const char* fn, const Scatter& p) {
+    CHECK(check_rules(fn, &p, kScatterFirst));
+    if (!(p.goal_min <= p.goal_max)) return fail(MRCA_ERR_INVALID, "%s: goal_max must be >= goal_min", fn);
+    return check_rules(fn, &p, kScatterRest);
+}
 
 // The params of a call as the kernels take them: the caller's (NULL: the defaults), if their table above accepts them
 template <class P, class Q> int take_params(const char* fn, const P* given, int (*defaults)(P*), Q* out) {
@@ -358,6 +372,37 @@ int mrca_scan_noise(mrca_env* env, const mrca_scan_noise_params* params, const u
     if (q.sigma_const == 0.0f && q.sigma_prop == 0.0f && q.dropout == 0.0f && q.quantum == 0.0f) return MRCA_OK;   // nothing to do
     return launched(env->cfg.device, [&] {
         mrca::launch_scan_noise(env->view, q, mask_dev, env->cfg.lazy_obs ? 0 : (MRCA_VIEW_SCAN | MRCA_VIEW_OBS), static_cast<hipStream_t>(stream));
+    });
+}
+
+int mrca_scatter_default_params(mrca_scatter_params* out) {
+    if (!out) return fail(MRCA_ERR_INVALID, "mrca_scatter_default_params: out is NULL");
+    out->min_sep = 1.0f;            // a robot's length and a half between two footprints
+    out->goal_sep = 1.0f;           // (two goal discs of radius 0.5 m do not overlap)
+    out->goal_min = 5.0f;
+    out->goal_max = 1.0e4f;         // no upper bound on any map the producer's boxes fit in
+    out->clear_cells = 4;           // 0.4 m on 0.1 m cells: the footprint's half diagonal (0.29 m) and a cell of slack
+    out->max_tries = 1024;
+    out->draw = 0;
+    return MRCA_OK;
+}
+
+int mrca_scatter(mrca_env* env, const mrca_scatter_params* params, const float* boxes_dev, float* poses_dev, float* goals_dev,
+                 int32_t* tries_dev, void* stream) {
+    const char* fn = "mrca_scatter";
+    mrca::ScatterParams q;
+    CHECK(take_params(fn, params, mrca_scatter_default_params, &q));
+    CHECK(check_ptr(fn, "boxes_dev", boxes_dev, 4, true));
+    CHECK(check_ptr(fn, "poses_dev", poses_dev, 4, true));
+    CHECK(check_ptr(fn, "goals_dev", goals_dev, 8, true));
+    CHECK(check_ptr(fn, "tries_dev", tries_dev, 4, false));
+    if (!env) return fail(MRCA_ERR_INVALID, "env is NULL");
+    if (env->cfg.robots_per_world > mrca::kScatterMaxRobots)
+        return fail(MRCA_ERR_UNSUPPORTED, "mrca_scatter: robots_per_world %d > %d (a world's placed points are held in 32 KB of LDS)",
+                    env->cfg.robots_per_world, mrca::kScatterMaxRobots);
+    // (valid before the first mrca_reset: the map, the geometry and the key stand since mrca_create)
+    return launched(env->cfg.device, [&] {
+        mrca::launch_scatter(env->view, q, boxes_dev, poses_dev, goals_dev, tries_dev, static_cast<hipStream_t>(stream));
     });
 }
 

@@ -37,7 +37,8 @@ EXPORTS = ["mrca_abi_version", "mrca_last_error", "mrca_arena_bytes", "mrca_crea
            "mrca_hybrid_default_params", "mrca_hybrid_actions",
            "mrca_safe_policy_default_params", "mrca_hybrid_plan", "mrca_hybrid_commit", "mrca_lidar_features_scaled",
            "mrca_planner_default_params", "mrca_planner_grid", "mrca_goal_fields", "mrca_subgoals",
-           "mrca_los_default_params", "mrca_subgoals_los", "mrca_dwa_actions_goal", "mrca_hybrid_actions_goal", "mrca_hybrid_plan_goal"]
+           "mrca_los_default_params", "mrca_subgoals_los", "mrca_dwa_actions_goal", "mrca_hybrid_actions_goal", "mrca_hybrid_plan_goal",
+           "mrca_scatter_default_params", "mrca_scatter"]
 # declared in include/mrca_env.h like the names above, listed apart: tests/test_abi.py's header scan reads names of letters
 # and underscores only (tests/test_policy_bf16_host.py checks these against the header and the library)
 EXPORTS_WITH_DIGITS = ["mrca_lidar_features_bf16", "mrca_lidar_features_bf16_rows", "mrca_lidar_features_bf16_backward",
@@ -76,6 +77,12 @@ class DwaParamsStruct(C.Structure):
 class ScanNoiseParamsStruct(C.Structure):
     """include/mrca_env.h: mrca_scan_noise_params"""
     _fields_ = [(k, C.c_float) for k in ("sigma_const", "sigma_prop", "dropout", "quantum")]
+
+
+class ScatterParamsStruct(C.Structure):
+    """include/mrca_env.h: mrca_scatter_params"""
+    _fields_ = [(k, C.c_float) for k in ("min_sep", "goal_sep", "goal_min", "goal_max")] + \
+        [("clear_cells", C.c_int32), ("max_tries", C.c_int32), ("draw", C.c_uint32)]
 
 
 class HybridParamsStruct(C.Structure):
@@ -200,6 +207,8 @@ def load(path=None):
     lib.mrca_dwa_actions.argtypes = [C.c_void_p, C.POINTER(DwaParamsStruct), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.mrca_scan_noise_default_params.argtypes = [C.POINTER(ScanNoiseParamsStruct)]
     lib.mrca_scan_noise.argtypes = [C.c_void_p, C.POINTER(ScanNoiseParamsStruct), C.c_void_p, C.c_void_p]
+    lib.mrca_scatter_default_params.argtypes = [C.POINTER(ScatterParamsStruct)]
+    lib.mrca_scatter.argtypes = [C.c_void_p, C.POINTER(ScatterParamsStruct)] + [C.c_void_p] * 5
     lib.mrca_hybrid_default_params.argtypes = [C.POINTER(HybridParamsStruct)]
     lib.mrca_hybrid_actions.argtypes = [C.c_void_p, C.POINTER(HybridParamsStruct), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_void_p]

@@ -17,6 +17,8 @@ from . import ppo, scenario
 from .net import CNNPolicy
 
 ACTION_BOUND = ((0.0, -1.0), (1.0, 1.0))     # circle_test.py:92
+# --scenario NAME -> the constructor in mrca.scenario whose boxes the scenario sampler fills (Long et al. 2018, Sec. V)
+SCATTER_SCENARIOS = {"random": "random_box", "swap": "group_swap", "crossing": "group_crossing", "corridor": "corridor"}
 
 
 def go_to_goal_policy(obs, local_goal, speed):
@@ -270,15 +272,37 @@ def perturbed_start(env, jitter_xy, jitter_th, seed):
     return poses.reshape(W * R, 3).contiguous(), goal.reshape(W * R, 2).contiguous()
 
 
-def circle_test(env, policy_fn, max_ticks=1200, perturb=None, seed=0, recorder=None):
+def scattered_start(env, params=None, face_goal=False):
+    """Start poses and goals of every world from the scenario sampler (``VecStageWorld.scatter`` on the scenario's boxes):
+    W worlds are W different scenarios, reproducible bit for bit from (seed, ``params.draw``).  A robot for which none of
+    ``max_tries`` candidates qualified would start on top of another or in a wall: that is an error here, not a scenario.
+    ``face_goal``: the start heading is turned towards the robot's own goal, with torch on the device -- OUTSIDE the bit-pinned
+    rule (atan2 is the runtime's).  -> (poses f32[N,3], goals f32[N,2], tries i32[N,2]) on the env's device."""
+    poses, goals, tries = env.scatter(params=params)
+    failed = (tries < 0).any(dim=1)
+    if bool(failed.any()):
+        n = int(failed.nonzero()[0, 0])
+        raise RuntimeError(f"scatter: no candidate qualified for {int(failed.sum())} of {env.N} robots (the first: world {n // env.R}, "
+                           f"local index {n % env.R}) -- fewer robots, a smaller min_sep / clear_cells or more max_tries")
+    if face_goal:
+        poses[:, 2] = torch.atan2(goals[:, 1] - poses[:, 1], goals[:, 0] - poses[:, 0])
+    return poses, goals, tries
+
+
+def circle_test(env, policy_fn, max_ticks=1200, perturb=None, seed=0, recorder=None, start=None):
     """Runs the circle scenario on ``env`` (any object with the VecStageWorld surface) and returns
     the metrics dict.  Mirrors circle_test.py:52-80: deterministic action, and a robot whose last
     ``get_reward_and_terminate`` said terminal gets v = 0 (``real_action[0] = 0``, :64-65).
     ``perturb = (jitter_xy, jitter_th)``: every circle starts from its own jittered poses (``perturbed_start``); the
     metrics then carry the mean success rate over circles with a 95 % interval.
     ``recorder``: a ``render.Recorder`` whose ``tick(k)`` is called before tick k (pictures of the run, gathered on the device;
-    it reads the env and writes nothing of it, so the metrics are the same with and without)."""
-    if perturb is None:
+    it reads the env and writes nothing of it, so the metrics are the same with and without).
+    ``start = (poses, goals)``: the start state itself, float32[N,3] and float32[N,2] on the env's device (``scattered_start``);
+    excludes ``perturb``."""
+    if start is not None:
+        assert perturb is None, "start and perturb are two start states"
+        env.reset(None, start[0], start[1])
+    elif perturb is None:
         env.reset()
     else:
         poses, goals = perturbed_start(env, perturb[0], perturb[1], seed)
@@ -358,9 +382,18 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--robots", type=int, default=None, help="robots per circle (default 50 = the reference's table; others: "
                                                              "scenario.circle_n) or per doorway room (default 12, at most 24)")
-    ap.add_argument("--scenario", default="circle", choices=["circle", "doorway"],
+    ap.add_argument("--scenario", default="circle", choices=["circle", "doorway"] + sorted(SCATTER_SCENARIOS),
                     help="doorway: scenario.doorway, --circles rooms split by a wall whose one door lies on no robot's straight line "
-                         "to its goal (excludes --radius / --one-circle / --stage-resolution)")
+                         "to its goal (excludes --radius / --one-circle / --stage-resolution); random / swap / crossing / corridor: "
+                         "the paper's other scenarios (scenario.random_box, group_swap, group_crossing, corridor), --circles worlds "
+                         "of --robots robots (default 20; crossing 12) whose starts and goals the scenario sampler draws per world "
+                         "(mrca_scatter); same exclusions, and --perturb")
+    ap.add_argument("--scatter-param", action="append", default=[], metavar="NAME=VALUE",
+                    help="a field of mrca_scatter_params on top of the scenario's, e.g. min_sep=0.8 (repeatable)")
+    ap.add_argument("--scatter-draw", type=int, default=None, metavar="D",
+                    help="the scenario number of the sampler: another draw, another set of worlds (default: --seed)")
+    ap.add_argument("--face-goal", action="store_true",
+                    help="scattered starts face their own goal (set with torch behind the sampler: not part of its bit-pinned rule)")
     ap.add_argument("--planner", action="store_true",
                     help="the global planner under --policy P [--fused | --fused-bf16] or the stand-in: goal fields planned once "
                          "(mrca_goal_fields), the controller handed each robot's subgoal (mrca_subgoals) in place of the local goal; "
@@ -449,10 +482,17 @@ def main():
     orca_first = a.orca_first if a.nh_orca_first is None else a.nh_orca_first
     from .vec_env import VecStageWorld
     doorway = a.scenario == "doorway"
+    scattered = a.scenario in SCATTER_SCENARIOS
+    if scattered and (a.radius != 25.0 or a.one_circle is not None or a.stage_resolution or a.perturb):
+        ap.error(f"--scenario {a.scenario} excludes --radius / --one-circle / --stage-resolution / --perturb")
+    if not scattered and (a.scatter_param or a.scatter_draw is not None or a.face_goal):
+        ap.error("--scatter-param / --scatter-draw / --face-goal go with --scenario " + " / ".join(sorted(SCATTER_SCENARIOS)))
+    if scattered and (a.planner or a.planner_los) and a.scenario != "corridor":
+        ap.error("--planner / --planner-los: of the scattered scenarios only the corridor has something to plan around")
     if doorway and (a.radius != 25.0 or a.one_circle is not None or a.stage_resolution):
         ap.error("--scenario doorway excludes --radius / --one-circle / --stage-resolution")
     if a.robots is None:
-        a.robots = 12 if doorway else 50
+        a.robots = 12 if doorway or a.scenario == "crossing" else (20 if scattered else 50)
     if a.planner_param and not (a.planner or a.planner_los):
         ap.error("--planner-param goes with --planner")
     if a.los_param and not a.planner_los:
@@ -491,6 +531,16 @@ def main():
             sc = scenario.doorway(num_worlds=a.circles, robots=a.robots, seed=a.seed, timeout=a.max_ticks)
         except ValueError as e:
             ap.error(str(e))
+    elif scattered:
+        try:
+            overrides = {}
+            for it in a.scatter_param:        # (min_sep is the constructor's: its coverage rule is judged with it)
+                if it.partition("=")[0] == "min_sep" and it.partition("=")[1]:
+                    overrides["min_sep"] = float(it.partition("=")[2])
+            sc = getattr(scenario, SCATTER_SCENARIOS[a.scenario])(robots=a.robots, num_worlds=a.circles, seed=a.seed, timeout=a.max_ticks,
+                                                                 **overrides)
+        except ValueError as e:
+            ap.error(str(e))
     elif a.robots == 50 and a.radius == 25.0:
         sc = scenario.circle(num_worlds=a.circles, seed=a.seed, stage_resolution=a.stage_resolution)
     else:
@@ -504,6 +554,14 @@ def main():
         except ValueError as e:
             ap.error(str(e))
     env = VecStageWorld(sc, **({} if noise is None else {"scan_noise": noise}))
+    scatter_params = None
+    if scattered:
+        from .scatter import ScatterParams
+        try:
+            scatter_params = ScatterParams.from_assignments(
+                a.scatter_param, start=dict(sc.scatter, draw=(a.seed if a.scatter_draw is None else a.scatter_draw) & 0xFFFFFFFF))
+        except ValueError as e:
+            ap.error(str(e))
     if a.policy:
         pol = CNNPolicy(3, 2).to(env.device)
         pol.load_state_dict(torch.load(a.policy, map_location=env.device))
@@ -591,7 +649,14 @@ def main():
         from .render import Recorder, save_frames
         worlds = [int(w) for w in a.render_worlds.split(",")] if a.render_worlds else None
         recorder = Recorder(env, worlds, a.render_every, a.render_size)
-    out = circle_test(env, fn, a.max_ticks, perturb=perturb, seed=a.seed, recorder=recorder)
+    start = tries = None
+    if scattered:
+        try:
+            poses, goals, tries = scattered_start(env, scatter_params, a.face_goal)
+        except RuntimeError as e:       # the library's validation text, or robots that found no place
+            ap.error(str(e))
+        start = (poses, goals)
+    out = circle_test(env, fn, a.max_ticks, perturb=perturb, seed=a.seed, recorder=recorder, start=start)
     if recorder is not None:      # (reported on stderr: the result line is the same with and without --render)
         frames = recorder.frames()
         print(f"{len(frames)} frames -> {save_frames(frames, a.render)}", file=sys.stderr)
@@ -617,8 +682,11 @@ def main():
         out["hybrid_modes"] = safe_fn.mode_shares()
     if a.planner or a.planner_los:
         out.update(planner_fn.report())
-    if doorway:
+    if doorway or scattered:
         out["scenario"] = a.scenario
+    if scattered:
+        out["scatter_params"], out["scatter_draw"] = scatter_params.as_dict(), scatter_params.draw
+        out["scatter_max_tries_used"], out["face_goal"] = int(tries.max()), bool(a.face_goal)
     out["lidar_noise"] = None if noise is None else noise.as_dict()
     out["robots_per_circle"], out["radius_m"] = a.robots, a.radius
     if a.one_circle is not None:

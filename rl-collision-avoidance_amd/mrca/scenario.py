@@ -77,6 +77,8 @@ class Scenario:
     init_table: np.ndarray = field(default=None)  # [R,3]
     goal_table: np.ndarray = field(default=None)  # [R,2]
     group_id: np.ndarray = field(default=None)
+    boxes: np.ndarray = None      # [R,8] start and goal box per local index (sx0, sy0, sx1, sy1, gx0, gy0, gx1, gy1): VecStageWorld.scatter
+    scatter: dict = None          # ... and the overrides of mrca_scatter_params' defaults that go with them
 
     def __post_init__(self):
         R = self.robots_per_world
@@ -95,6 +97,8 @@ class Scenario:
         self.group_id = np.ascontiguousarray(self.group_id, np.int32)
         self.init_table = np.ascontiguousarray(self.init_table, np.float64).reshape(R, 3)
         self.goal_table = np.ascontiguousarray(self.goal_table, np.float64).reshape(R, 2)
+        if self.boxes is not None:
+            self.boxes = np.ascontiguousarray(self.boxes, np.float64).reshape(R, 8)
 
     @property
     def num_robots(self):
@@ -234,3 +238,88 @@ def circle_n(robots, radius, num_worlds=1, seed=0, train=False, timeout=None, gr
     return Scenario("circle_train" if train else "circle", num_worlds, R, grid or load_map("circle_rink"), timeout=t,
                     w_thresh=0.7, pre_dist_zero=True, auto_reset=AUTO_GROUP if train else AUTO_NONE, seed=seed,
                     reset_mode=mode, goal_mode=mode.copy(), init_table=init, goal_table=-init[:, :2])
+
+
+# ---- the paper's other evaluation scenarios (Long et al. 2018, Sec. V: random, group swap, group crossing, corridor): walled
+# rooms on 0.1 m cells with a 2-cell border like ``doorway``, the circle's episode rules, and per local index a start and a goal
+# BOX in place of a table row -- ``VecStageWorld.scatter`` draws every world's starts and goals in them (mrca_scatter), so W
+# worlds are W different scenarios.  The table rows hold the boxes' centres: what a robot stands on before the first scatter.
+SCATTER_COVERAGE_MAX = 0.30      # of a box's area, by discs of diameter min_sep: random sequential placement jams at 54.7 %
+
+
+def _room(width, height, cell=0.1, border=2):
+    """occupancy of a walled room of ``width`` x ``height`` metres centred at the origin -> (occ bool[h, w], x0, y0, xc, yc):
+    the grid, its corner and the cell centres per axis"""
+    w, h = int(round(width / cell)), int(round(height / cell))
+    occ = np.zeros((h, w), bool)
+    occ[:border, :] = occ[-border:, :] = occ[:, :border] = occ[:, -border:] = True
+    x0, y0 = -0.5 * width, -0.5 * height
+    return occ, x0, y0, x0 + (np.arange(w) + 0.5) * cell, y0 + (np.arange(h) + 0.5) * cell
+
+
+def _box_scenario(name, num_worlds, occ, x0, y0, boxes, seed, timeout, min_sep, scatter):
+    boxes = np.asarray(boxes, np.float64)
+    R = len(boxes)
+    if R < 1:
+        raise ValueError(f"{name}: at least one robot")
+    disc = np.pi * (0.5 * float(min_sep)) ** 2
+    for half in (boxes[:, :4], boxes[:, 4:]):          # the robots dealt into one box, starts and goals alike
+        for box in np.unique(half, axis=0):
+            count = int((half == box).all(axis=1).sum())
+            area = (box[2] - box[0]) * (box[3] - box[1])
+            if count * disc > SCATTER_COVERAGE_MAX * area:
+                raise ValueError(f"{name}: {count} robots in a box of {area:g} m^2 -- discs of diameter min_sep = {min_sep:g} m would "
+                                 f"cover {100.0 * count * disc / area:.1f} % of it, more than {100.0 * SCATTER_COVERAGE_MAX:g} % "
+                                 f"(at most {int(SCATTER_COVERAGE_MAX * area / disc)} fit the rule)")
+    init = np.stack([0.5 * (boxes[:, 0] + boxes[:, 2]), 0.5 * (boxes[:, 1] + boxes[:, 3]), np.zeros(R)], 1)
+    goal = np.stack([0.5 * (boxes[:, 4] + boxes[:, 6]), 0.5 * (boxes[:, 5] + boxes[:, 7])], 1)
+    mode = np.full(R, RESET_TABLE, np.int32)
+    return Scenario(name, num_worlds, R, GridData.from_dense(occ, 0.1, x0, y0), timeout=int(timeout), w_thresh=0.7,
+                    pre_dist_zero=True, auto_reset=AUTO_NONE, seed=seed, reset_mode=mode, goal_mode=mode.copy(), init_table=init,
+                    goal_table=goal, boxes=boxes, scatter=dict(min_sep=float(min_sep), **scatter))
+
+
+def _mirrored(robots, even):
+    """``even`` (sx0, sy0, sx1, sy1, gx0, gy0, gx1, gy1) for the even local indices, mirrored in x for the odd ones"""
+    sx0, sy0, sx1, sy1, gx0, gy0, gx1, gy1 = even
+    odd = (-sx1, sy0, -sx0, sy1, -gx1, gy0, -gx0, gy1)
+    return [even if i % 2 == 0 else odd for i in range(int(robots))]
+
+
+def random_box(robots=20, side=16.0, num_worlds=1, seed=0, timeout=900, min_sep=1.0):
+    """The paper's RANDOM scenario: a walled square room of ``side`` metres; every robot's start and goal are drawn in the box
+    [-side/2 + 1, side/2 - 1]^2, the goal at least 6 m from the start."""
+    occ, x0, y0, _xc, _yc = _room(side, side)
+    a = 0.5 * side - 1.0
+    return _box_scenario("random_box", num_worlds, occ, x0, y0, [(-a, -a, a, a, -a, -a, a, a)] * int(robots), seed, timeout, min_sep,
+                         dict(goal_min=6.0, goal_max=1.0e4))
+
+
+def group_swap(robots=20, num_worlds=1, seed=0, timeout=900, min_sep=1.0):
+    """GROUP SWAP: a room of 20 m x 12 m; the even local indices start in x in [-9, -5], y in [-5, 5] with their goals in
+    x in [5, 9] (the same y range), the odd ones the other way."""
+    occ, x0, y0, _xc, _yc = _room(20.0, 12.0)
+    return _box_scenario("group_swap", num_worlds, occ, x0, y0, _mirrored(robots, (-9.0, -5.0, -5.0, 5.0, 5.0, -5.0, 9.0, 5.0)), seed,
+                         timeout, min_sep, {})
+
+
+def group_crossing(robots=12, num_worlds=1, seed=0, timeout=900, min_sep=1.0):
+    """GROUP CROSSING: a room of 20 m x 20 m; the even local indices go left to right (x in [-9, -6] to x in [6, 9], y in
+    [-3, 3]), the odd ones bottom to top (the same with x and y exchanged).  A box of 3 m x 6 m takes 6 robots of
+    ``min_sep`` 1 m under the coverage rule: 12 robots at most."""
+    occ, x0, y0, _xc, _yc = _room(20.0, 20.0)
+    even = (-9.0, -3.0, -6.0, 3.0, 6.0, -3.0, 9.0, 3.0)
+    odd = (-3.0, -9.0, 3.0, -6.0, -3.0, 6.0, 3.0, 9.0)
+    return _box_scenario("group_crossing", num_worlds, occ, x0, y0, [even if i % 2 == 0 else odd for i in range(int(robots))], seed,
+                         timeout, min_sep, {})
+
+
+def corridor(robots=20, width=4.0, num_worlds=1, seed=0, timeout=900, min_sep=1.0):
+    """CORRIDOR: a room of 24 m x 10 m; two wall blocks over x in [-4, 4] leave a corridor of ``width`` metres around y = 0.
+    The even local indices start in x in [-11, -6], y in [-4, 4] with their goals in x in [6, 11], the odd ones the other way."""
+    if not 1.0 <= float(width) <= 9.0:
+        raise ValueError("corridor: width 1..9 m")
+    occ, x0, y0, xc, yc = _room(24.0, 10.0)
+    occ[np.ix_(np.abs(yc) > 0.5 * float(width), np.abs(xc) < 4.0)] = True
+    return _box_scenario("corridor", num_worlds, occ, x0, y0, _mirrored(robots, (-11.0, -4.0, -6.0, 4.0, 6.0, -4.0, 11.0, 4.0)), seed,
+                         timeout, min_sep, {})

@@ -104,6 +104,7 @@ class VecStageWorld:
         self._eager_views = 0 if lazy_obs else (_lib.VIEW_SCAN | _lib.VIEW_OBS)   # views the library itself keeps current
         self._views_current = 0          # bits of _lib.VIEW_*: which of MRCA_F_SCAN / MRCA_F_OBS follow the ring right now
         self._scan_noise = None if scan_noise is None else scan_noise.struct()
+        self._scatter_boxes = None       # (the boxes' bytes, their float32[R,8] tensor on the device): what scatter() uploaded last
         self._noise_masks = {}           # (first, count) -> uint8[N] with ones in that range of robots: kept, so a capture can replay them
 
     # ------------------------------------------------------------------ the scans and the observation stack
@@ -477,6 +478,37 @@ class VecStageWorld:
             m = self._noise_masks[(first, count)] = torch.zeros(self.N, dtype=torch.uint8, device=self.device)
             m[first:first + count] = 1
         self._apply_noise(self._scan_noise, C.c_void_p(m.data_ptr()))
+
+    def scatter(self, boxes=None, params=None, out=None):
+        """The scenario sampler (mrca_scatter): per world a different set of starts and goals, each robot's drawn in its own
+        start / goal box (``boxes``: [R,8] per local index, default ``scenario.boxes``), clear of the map and apart from the
+        robots placed before it -- reproducible bit for bit from (seed, ``params.draw``).  -> ``(poses, goals, tries)``:
+        float32[N,3], float32[N,2] and int32[N,2] tensors on the env's device (``out``: such a triple to write into), what
+        ``reset(None, poses, goals)`` takes; ``tries`` holds the candidates used per start and goal, -1 where none of
+        ``max_tries`` qualified (the robot then stands on its last candidate).  ``params``: a ``scatter.ScatterParams`` (default:
+        the scenario's ``scatter`` overrides on the library's defaults).  One launch on the current stream, nothing
+        synchronises, nothing of the env is written; valid before the first ``reset``."""
+        from .scatter import ScatterParams, check_boxes
+        if boxes is None:
+            boxes = self.scenario.boxes
+        if boxes is None:
+            raise ValueError("scatter: the scenario has no boxes and none were given")
+        b = check_boxes(boxes, self.R)
+        key = b.tobytes()
+        if self._scatter_boxes is None or self._scatter_boxes[0] != key:      # the uploaded boxes are kept: a capture can replay them
+            self._scatter_boxes = (key, torch.from_numpy(b).to(self.device))
+        if params is None:
+            params = ScatterParams(**(self.scenario.scatter or {}))
+        st = params.struct()
+        if out is None:
+            out = (torch.zeros((self.N, 3), dtype=torch.float32, device=self.device),
+                   torch.zeros((self.N, 2), dtype=torch.float32, device=self.device),
+                   torch.zeros((self.N, 2), dtype=torch.int32, device=self.device))
+        poses, goals, tries = out
+        _lib.check(self.lib.mrca_scatter(self._h, C.byref(st), C.c_void_p(self._scatter_boxes[1].data_ptr()),
+                                         self._ptr(poses, torch.float32, 3 * self.N), self._ptr(goals, torch.float32, 2 * self.N),
+                                         self._ptr(tries, torch.int32, 2 * self.N), self._stream()), "mrca_scatter")
+        return poses, goals, tries
 
     # ------------------------------------------------------------------ lifecycle
     def close(self):
