@@ -10,8 +10,10 @@ import subprocess
 import numpy as np
 import pytest
 
+import dwa_cases as K
 import dwa_ref as R
 import util as U
+from dwa_cases import crafted  # noqa: F401  (the crafted rows live in tests/dwa_cases.py; tests/test_gpu_dwa.py runs them too)
 from util import S
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -149,100 +151,44 @@ def test_random_inputs_equal_the_reference(shim, beams):
     assert seen == {"blocked", "at_goal", "chosen"}
 
 
-def crafted(B=192):
-    """(goal, speed, rows) of robots that each take one special path; -> also their names in order"""
-    per = B // 64
-    open_row = np.full(B, 6.0, f32)
-    names, goals, speeds, rows = [], [], [], []
-
-    def add(name, goal, row, speed=(0.5, 0.0)):
-        names.append(name)
-        goals.append(goal)
-        speeds.append(speed)
-        rows.append(row)
-    add("all_ranges_6", (4.0, 1.0), open_row.copy())
-    r = open_row.copy()
-    r[3 * per], r[10 * per + 1] = f32(-0.0), f32(0.0)
-    add("ranges_0_and_minus_0", (4.0, 1.0), r)
-    r = open_row.copy()
-    r[20 * per:21 * per] = f32(3.0)                                      # exactly obst_dist: does not count
-    r[21 * per + 1] = np.nextafter(f32(3.0), f32(0.0))                   # one ulp below: counts
-    add("return_at_obst_dist", (4.0, -1.0), r)
-    r = open_row.copy()
-    r[30 * per:31 * per] = f32(2.0)
-    r[30 * per] = r[30 * per + 2] = f32(1.5)                             # equal minima in sector 30
-    add("equal_minima", (3.0, 2.0), r)
-    add("goal_half_a_metre_ahead", (0.5, 0.0), open_row.copy())
-    add("goal_half_a_metre_right", (0.0, -0.5), open_row.copy())
-    add("goal_just_outside", (float(np.nextafter(f32(0.5), f32(1.0))), 0.0), open_row.copy())
-    add("goal_dead_ahead_open", (5.0, 0.0), open_row.copy(), speed=(1.0, 0.0))
-    add("boxed_in", (3.0, 1.0), np.full(B, 0.3, f32))
-    add("boxed_in_goal_right", (3.0, -1.0), np.full(B, 0.3, f32))
-    r = open_row.copy()
-    r[32 * per] = f32(0.8)                                               # one return ahead, 0.8 m: some arcs pass, some do not
-    add("post_ahead", (4.0, 0.0), r)
-    r = open_row.copy()
-    r[0] = f32(1.6)                                                      # 1.6 m to the right: clearance above and below the cap
-    add("far_point", (4.0, 0.0), r)
-    return names, np.array(goals, f32), np.array(speeds, f32), np.stack(rows)
-
-
 def test_crafted_inputs_take_every_branch(shim):
+    """tests/dwa_cases.py: ``crafted`` and what each of its rows is made for"""
     B = 192
-    per = B // 64
     names, goal, speed, rows = crafted(B)
-    ix = {k: i for i, k in enumerate(names)}
     p = R.params()
     act, choice, score, d = assert_equal_to_ref(shim, p, goal, speed, rows)
-    cap, nw = p["clear_cap"], p["nw"]
-    # no point at all: every clearance IS the cap, everybody admissible
-    i = ix["all_ranges_6"]
-    assert not d["any_point"][i] and (d["beam"][i] == -1).all() and (d["clear"][i] == cap).all() and d["admissible"][i].all()
-    assert np.isinf(d["px"][i]).all() and choice[i] >= 0
-    # 0 and -0.0 are points AT the robot, both +0 after the rule's + 0: everything is blocked, the robot turns to the goal's side
-    i = ix["ranges_0_and_minus_0"]
-    assert d["beam"][i][3] == 3 * per and d["beam"][i][10] == 10 * per + 1
-    assert (d["px"][i][[3, 10]] == 0).all() and (d["py"][i][[3, 10]] == 0).all()
-    assert not np.signbit(d["px"][i][3])                 # (the beam's cosine is positive: the range -0.0 became +0 first)
-    assert not d["admissible"][i].any() and choice[i] == R.BLOCKED and same_bits(act[i], [0.0, 1.0]) and score[i] == 0
-    # exactly obst_dist does not count, one ulp below does
-    i = ix["return_at_obst_dist"]
-    assert d["beam"][i][20] == -1 and d["beam"][i][21] == 21 * per + 1
-    # equal minima: the lower beam
-    i = ix["equal_minima"]
-    assert d["beam"][i][30] == 30 * per and int((d["beam"][i] >= 0).sum()) == 1
-    # 0.5 m is AT the goal (<=), the next float is not
-    for k in ("goal_half_a_metre_ahead", "goal_half_a_metre_right"):
-        assert d["at_goal"][ix[k]] and choice[ix[k]] == R.AT_GOAL and same_bits(act[ix[k]], [0.0, 0.0])
-    assert not d["at_goal"][ix["goal_just_outside"]] and choice[ix["goal_just_outside"]] >= 0
-    # dead ahead in the open: mirror arcs have EQUAL scores, and straight on at full speed wins
-    i = ix["goal_dead_ahead_open"]
-    sc = d["score"][i].reshape(p["nv"], nw)
-    assert same_bits(sc, sc[:, ::-1])
-    assert choice[i] == (p["nv"] - 1) * nw + nw // 2 and same_bits(act[i], [1.0, 0.0])
-    # boxed in: nobody admissible, the turn follows the sign of gy
-    for k, turn in (("boxed_in", 1.0), ("boxed_in_goal_right", -1.0)):
-        assert not d["admissible"][ix[k]].any() and choice[ix[k]] == R.BLOCKED and same_bits(act[ix[k]], [0.0, turn])
-    # a post ahead: some candidates pass and some do not, and the chosen one passes
-    i = ix["post_ahead"]
-    assert d["admissible"][i].any() and not d["admissible"][i].all() and d["admissible"][i][choice[i]]
-    # a far point: clearances on both sides of the cap among the admissible candidates
-    i = ix["far_point"]
-    assert (d["clear"][i] > cap).any() and ((d["clear"][i] < cap) & d["admissible"][i]).any()
+    K.expectations(names, p, B, act, choice, score, d)
 
 
 def test_a_tie_goes_to_the_lower_candidate(shim):
     """Goal dead ahead in the open with two candidates, (1, -1) and (1, +1): mirror arcs, EQUAL scores -- c = 0 wins.  And with
-    only the clearance weighted, all 105 candidates of the default grid tie (no point: every clearance is the cap)."""
+    only the clearance weighted, all 105 candidates of the default grid tie (no point: every clearance is the cap), as do the
+    1024 of the largest grid."""
     _names, goal, speed, rows = crafted(64)
-    sel = [7]                                            # goal_dead_ahead_open
-    p = R.params(nv=1, nw=2)
-    act, choice, score, d = assert_equal_to_ref(shim, p, goal[sel], speed[sel], rows[sel])
-    assert bits(d["score"][0])[0] == bits(d["score"][0])[1] and d["admissible"][0].all()
-    assert choice[0] == 0 and same_bits(act[0], [1.0, -1.0])
-    p = R.params(w_goal=0.0, w_heading=0.0, w_speed=0.0)
-    act, choice, score, d = assert_equal_to_ref(shim, p, goal[sel], speed[sel], rows[sel])
-    assert len(set(bits(d["score"][0]).tolist())) == 1 and choice[0] == 0 and same_bits(act[0], [0.0, -1.0])
+    sel = [K.TIE_ROW]
+    for name, grid in K.TIE_GRIDS.items():
+        act, choice, score, d = assert_equal_to_ref(shim, R.params(**grid), goal[sel], speed[sel], rows[sel])
+        K.tie_expectations(name, act, choice, d)
+
+
+@pytest.mark.parametrize("beams", [64, 192, 1024])
+def test_sector_counts_special_values_and_winner_places(shim, beams):
+    """The rest of tests/dwa_cases.py, which the GPU test puts into an env: rows with 0 ... 64 occupied sectors, goals and speeds
+    that are no numbers, and the params under which the winner sits in each place of the kernel's deal."""
+    p = R.params()
+    rows = K.sector_rows(beams)
+    n = len(rows)
+    _a, _c, _s, d = assert_equal_to_ref(shim, p, np.tile(f32(K.SECTOR_GOAL), (n, 1)), np.tile(f32([0.5, 0.0]), (n, 1)), rows)
+    K.sector_expectations(d)
+    _names, goal, speed, rows = K.special(beams)
+    act, choice, _s, d = assert_equal_to_ref(shim, p, goal, speed, rows)
+    K.special_expectations(p, act, choice, d)
+    kinds = set()
+    for grid, g in K.WINNER_SETS:
+        q = R.params(**grid)
+        _a, choice, _s, _d = assert_equal_to_ref(shim, q, f32([g]), f32([[0.5, 0.0]]), np.full((1, beams), 6.0, f32))
+        kinds |= K.winner_kinds(q, int(choice[0]))
+    assert kinds == K.WINNER_KINDS, kinds
 
 
 def test_choice_is_the_brute_force_argmax(shim):

@@ -2,15 +2,23 @@
 tests/dwa_ref.py fed with host copies of the env's fields, for EVERY robot (small walled worlds right after a teleport and
 after motion, every candidate-grid size that takes another path through the kernel, the shortest and the longest rollout, ring
 heads that differ, a mask, worlds of more than 64 robots); the call reads the env and writes nothing of it; 30 closed-loop
-ticks equal to the C oracle driven by the host build of the same rule; the error returns; ``mrca.evaluate --dwa``."""
+ticks equal to the C oracle driven by the host build of the same rule; the error returns; ``mrca.evaluate --dwa``.
+
+The crafted cases -- every branch, tie and threshold of the rule, and the inputs at which the kernel's own glue can go wrong
+(the packing of points into groups of four, the deal of candidates to lanes and rounds, the wave maximum, the early exits) --
+live in tests/dwa_cases.py, shared with tests/test_dwa_host.py; tests/controller_inject.py writes them into an env, one case
+per robot, and ``test_crafted_cases_on_the_device`` asserts from the fields read back that each case stood on its edge."""
 import ctypes as C
 
 import numpy as np
 import pytest
 import torch
 
+import controller_inject as J
+import dwa_cases as K
 import dwa_ref as R
 import util as U
+from dwa_cases import CRAFTED_AT, QUAD_AT, SECTORS_AT, SPECIAL_AT, WINNERS_AT
 from test_dwa_host import host_env_actions, shim  # noqa: F401  (shim: the host build of csrc/mrca_dwa_device.h)
 from test_gpu_orca import NAN_BITS, _evaluate, go_to_goal, nan_filled, small_scenario, teleport_poses
 from util import S
@@ -45,14 +53,18 @@ def host_fields(env):
     return env.local_goal.cpu().numpy(), env.speed.cpu().numpy(), rows.cpu().numpy()
 
 
-def check_equal(env, p, mask=None, with_extras=True, fields=None):
-    """One call compared with dwa_ref on the same fields, every robot -> (the reference's choice, its diagnostics)."""
+def check_equal(env, p, mask=None, with_extras=True, fields=None, goal_dev=None, full=False):
+    """One call compared with dwa_ref on the same fields, every robot -> (the reference's choice, its diagnostics), or with
+    ``full`` (its actions, choice, score, diagnostics).  ``goal_dev``: a float32[N,2] tensor that goes in through
+    mrca_dwa_actions_goal; the reference is then fed with a host copy of it in place of ``local_goal``."""
     goal, speed, rows = fields or host_fields(env)
+    if goal_dev is not None:
+        goal = goal_dev.cpu().numpy()
     act = nan_filled(env)
     choice = torch.full((env.N,), 12345, dtype=torch.int32, device=env.device) if with_extras else None
     score = nan_filled(env)[:, 0].contiguous() if with_extras else None
     m = None if mask is None else dev(np.ascontiguousarray(mask, np.uint8))
-    got = env.dwa_actions(dwa_params(p), mask=m, out=act, choice=choice, score=score)
+    got = env.dwa_actions(dwa_params(p), mask=m, out=act, choice=choice, score=score, goal=goal_dev)
     assert got is act
     robots = None if mask is None else np.flatnonzero(mask).tolist()
     wact, wchoice, wscore, diag = R.env_actions(p, goal, speed, rows, robots=robots)
@@ -65,7 +77,7 @@ def check_equal(env, p, mask=None, with_extras=True, fields=None):
         assert np.array_equal(choice.cpu().numpy(), np.where(skipped, 12345, wchoice)), (choice.cpu().numpy(), wchoice)
         s = score.cpu().numpy().view(np.uint32)
         assert np.array_equal(s, np.where(skipped, np.uint32(NAN_BITS), wscore.view(np.uint32))), np.argwhere(s != wscore.view(np.uint32))[:5]
-    return wchoice, diag
+    return (wact, wchoice, wscore, diag) if full else (wchoice, diag)
 
 
 @pytest.mark.parametrize("lazy", [True, False])
@@ -131,6 +143,60 @@ def test_ring_heads_that_differ_between_robots(hip):
     torch.cuda.synchronize()
     assert len(set(env.ring_head.cpu().numpy().tolist())) > 1
     check_equal(env, R.params(obst_dist=6.0))
+    env.close()
+
+
+# ------------------------------------------------------------------------------------------------ the crafted cases, on the device
+# tests/dwa_cases.py, one case per robot (``K.layout``), written by tests/controller_inject.py
+def crafted_env(hip, beams):
+    """A walled env with ring heads that differ and every case of dwa_cases written into it -> (env, names of ``crafted``)"""
+    env = J.walled_env(hip, beams, K.N_CASES)
+    names, goal, speed, rows = K.layout(beams)
+    J.write_cases(env, 0, local_goal=goal, speed=speed, rows=rows)
+    assert J.heads_differ(env)
+    return env, names
+
+
+def crafted_checks(env, names, beams, goal_dev=None):
+    """Every check of the crafted cases on one env, the goals read from ``local_goal`` or from ``goal_dev``"""
+    p = R.params()
+    act, choice, score, d = check_equal(env, p, goal_dev=goal_dev, full=True)
+    K.expectations(names, p, beams, act, choice, score, d)                # (each edge occurred: from the fields read back)
+    K.sector_expectations(d, SECTORS_AT)
+    K.special_expectations(p, act, choice, d, SPECIAL_AT)
+    # the same robots under another window and another horizon: the packed points are walked by other arcs
+    check_equal(env, R.params(acc_v=1.0, acc_w=3.0, obst_dist=6.0, clear_cap=0.5, w_heading=0.4), goal_dev=goal_dev)
+    # ties: two mirror arcs, every candidate of the default grid (across lanes and into the partial round), all 1024 (16 rounds)
+    for name, grid in K.TIE_GRIDS.items():
+        act, choice, _s, d = check_equal(env, R.params(**grid), goal_dev=goal_dev, full=True)
+        K.tie_expectations(name, act, choice, d, CRAFTED_AT + K.TIE_ROW)
+    # the winner in lane 0, in lane 63, in the first round, in the last partial round
+    kinds, done = set(), {}
+    for k, (grid, _g) in enumerate(K.WINNER_SETS):
+        q = R.params(**grid)
+        key = tuple(sorted(grid.items()))
+        if key not in done:
+            done[key] = check_equal(env, q, goal_dev=goal_dev)[0]
+        kinds |= K.winner_kinds(q, int(done[key][WINNERS_AT + k]))
+    assert kinds == K.WINNER_KINDS, kinds
+    # one workgroup whose four robots are masked out, at the goal, blocked and choosing
+    mask = np.ones(env.N, np.uint8)
+    mask[QUAD_AT] = 0
+    choice, _d = check_equal(env, p, mask=mask, goal_dev=goal_dev)
+    assert choice[QUAD_AT + 1] == R.AT_GOAL and choice[QUAD_AT + 2] == R.BLOCKED and choice[QUAD_AT + 3] >= 0
+
+
+@pytest.mark.parametrize("beams", [64, 192, 1024])
+def test_crafted_cases_on_the_device(hip, beams):
+    """Every row of ``dwa_cases.crafted``, rows with 0, 1, 3, 4, 5, 63 and 64 occupied sectors, NaN and Inf in goal and speed, the
+    grids on which ties decide and the four places a winner can take, written into an env -- and once more with the goals
+    handed to mrca_dwa_actions_goal while ``local_goal`` holds something else."""
+    env, names = crafted_env(hip, beams)
+    crafted_checks(env, names, beams)
+    goals = env.local_goal.clone()
+    env.local_goal[:] = dev(np.random.default_rng(beams).uniform(-5.0, 5.0, (env.N, 2)).astype(f32))
+    crafted_checks(env, names, beams, goal_dev=goals)
+    env.check()
     env.close()
 
 

@@ -1,13 +1,20 @@
 """GPU: mrca_hybrid_actions -- command, mode and the three clearances EQUAL, bit for bit, to the NumPy float32 restatement of
 tests/hybrid_ref.py fed with the fields read back, for EVERY robot: small walled worlds driven beside the C oracle (every mode
 occurs), ring heads that differ, masks, in place and out of place, worlds of more than 64 robots, behind mrca_scan_noise, in a
-captured tick; the call writes nothing of the env; the error returns; ``mrca.evaluate --hybrid``."""
+captured tick; the call writes nothing of the env; the error returns; ``mrca.evaluate --hybrid``.
+
+The crafted cases -- every edge of the rule, and the inputs at which the kernel's own glue can go wrong (the deal of beams to
+lanes in rounds of 64, the butterfly merge of minima and counts, the early exits, the lane-0 epilogue) -- live in
+tests/hybrid_cases.py, shared with tests/test_hybrid_host.py; tests/controller_inject.py writes them into an env, one case per
+robot, and ``test_crafted_cases_on_the_device`` asserts from the fields read back that each case stood on its edge."""
 import ctypes as C
 
 import numpy as np
 import pytest
 import torch
 
+import controller_inject as J
+import hybrid_cases as K
 import hybrid_ref as R
 import util as U
 from test_gpu_orca import NAN_BITS, _evaluate, go_to_goal, nan_filled, small_scenario, teleport_poses
@@ -65,23 +72,27 @@ def parity_scene(sc, rng):
     return poses, goals
 
 
-def check_equal(env, p, policy, mask=None, with_extras=True, in_place=False, fields=None):
-    """One call compared with hybrid_ref on the same fields, every robot -> (the reference's actions, modes, clearances)."""
+def check_equal(env, p, policy, mask=None, with_extras=True, in_place=False, fields=None, goal_dev=None, full=False):
+    """One call compared with hybrid_ref on the same fields, every robot -> (the reference's actions, modes, clearances), with
+    ``full`` also its blocking counts.  ``goal_dev``: a float32[N,2] tensor that goes in through mrca_hybrid_actions_goal; the
+    reference is then fed with a host copy of it in place of ``local_goal``."""
     goal, rows = fields or host_fields(env)
+    if goal_dev is not None:
+        goal = goal_dev.cpu().numpy()
     policy = np.ascontiguousarray(policy, f32)
     mode = torch.full((env.N,), MODE_SENTINEL, dtype=torch.int32, device=env.device) if with_extras else None
     clear = torch.full((env.N, 3), NAN_BITS, dtype=torch.int32, device=env.device).view(torch.float32) if with_extras else None
     m = None if mask is None else dev(np.ascontiguousarray(mask, np.uint8))
     if in_place:
         act = dev(policy)
-        got = env.hybrid_actions(act, hybrid_params(p), mask=m, mode=mode, clear=clear)
+        got = env.hybrid_actions(act, hybrid_params(p), mask=m, mode=mode, clear=clear, goal=goal_dev)
         untouched = bits(policy)
     else:
         act, pol = nan_filled(env), dev(policy)
-        got = env.hybrid_actions(pol, hybrid_params(p), mask=m, out=act, mode=mode, clear=clear)
+        got = env.hybrid_actions(pol, hybrid_params(p), mask=m, out=act, mode=mode, clear=clear, goal=goal_dev)
         untouched = np.full((env.N, 2), NAN_BITS, np.uint32)
     assert got is act
-    wact, wmode, wclear, _nb = R.env_actions(p, goal, policy, rows)
+    wact, wmode, wclear, nb = R.env_actions(p, goal, policy, rows)
     sel = np.ones(env.N, bool) if mask is None else np.asarray(mask).astype(bool)
     torch.cuda.synchronize()
     if not in_place:
@@ -94,7 +105,37 @@ def check_equal(env, p, policy, mask=None, with_extras=True, in_place=False, fie
         c = bits(clear.cpu().numpy())
         want_c = np.where(sel[:, None], bits(wclear), np.uint32(NAN_BITS))
         assert np.array_equal(c, want_c), (np.argwhere(c != want_c)[:5], clear.cpu().numpy()[:8], wclear[:8])
-    return wact, wmode, wclear
+    return (wact, wmode, wclear, nb) if full else (wact, wmode, wclear)
+
+
+# ------------------------------------------------------------------------------------------------ the crafted cases, on the device
+@pytest.mark.parametrize("beams", [64, 192, 1024])
+def test_crafted_cases_on_the_device(hip, beams):
+    """``hybrid_cases.device_cases`` -- every edge of the host test's crafted rows rebuilt on the env's own beam table, lone
+    returns on the first and the last lane of the first and the last round, a row in which all B beams block, ranges of 0.0 and
+    -0.0, NaN / Inf / -0.0 commands in every mode -- written into an env one case per robot: out of place, in place, under a
+    mask, and with the goals handed to mrca_hybrid_actions_goal while ``local_goal`` holds something else.  That each row stood
+    on its edge is asserted from the fields read back."""
+    names, goal, policy, rows = K.device_cases(beams)
+    env = J.walled_env(hip, beams, len(names))
+    J.write_cases(env, 0, local_goal=goal, rows=rows)
+    assert J.heads_differ(env)
+    rng = np.random.default_rng(beams)
+    pol = seeded_commands(rng, env.N)
+    pol[:len(names)] = policy
+    p = R.params(**K.PARAMS)
+    goals = env.local_goal.clone()
+    for goal_dev in (None, goals):
+        if goal_dev is not None:
+            env.local_goal[:] = dev(rng.uniform(-5.0, 5.0, (env.N, 2)).astype(f32))
+        for in_place in (False, True):
+            act, mode, clear, nb = check_equal(env, p, pol, in_place=in_place, goal_dev=goal_dev, full=True)
+            K.expectations(names, p, pol, host_fields(env)[1], act, mode, clear, nb)
+            mask = (np.arange(env.N) % 3 != 1).astype(np.uint8)
+            check_equal(env, p, pol, mask=mask, in_place=in_place, goal_dev=goal_dev)
+        check_equal(env, R.params(), pol, goal_dev=goal_dev)             # (the same rows off their edges, under the defaults)
+    env.check()
+    env.close()
 
 
 # ------------------------------------------------------------------------------------------------ parity beside the oracle

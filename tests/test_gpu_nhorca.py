@@ -3,14 +3,20 @@ tests/nhorca_ref.py fed with host copies of the env's fields: small walled world
 neighbours, a dense circle where LP3 decides, robots turned away from and standing at their goals, ring heads that differ, a
 mask; worlds of more than 64 robots (the threshold, a lattice with several chunks of candidates, two worlds in one hash); closed
 loops equal to the C oracle driven by the host build of the same rule; the call writes nothing of the env; the refusals with
-their messages; ``mrca.evaluate --nh-orca``."""
+their messages; ``mrca.evaluate --nh-orca``.
+
+The crafted cases live in tests/orca_cases.py, shared with tests/test_orca_host.py and tests/test_nhorca_host.py;
+tests/controller_inject.py puts them into an env as ONE world, and ``test_crafted_world_on_the_device`` asserts from the fields
+read back that each edge occurred and each situation took its mode."""
 import ctypes as C
 
 import numpy as np
 import pytest
 import torch
 
+import controller_inject as J
 import nhorca_ref as NR
+import orca_cases as K
 import orca_ref as R
 import util as U
 from test_gpu_orca import NAN_BITS, _evaluate, go_to_goal, host_fields, nan_filled, small_scenario, teleport_poses
@@ -108,6 +114,31 @@ def test_a_full_wave_of_neighbours(hip, max_neighbors):
     env.reset()
     _m, diags = check_equal(env, NR.params(max_neighbors=max_neighbors, neighbor_dist=20.0))
     assert max(len(d["branches"]) - d["n_static"] for d in diags.values()) == max_neighbors
+    env.check()
+    env.close()
+
+
+@pytest.mark.parametrize("robots,beams", [(34, 64), (34, 192), (66, 192)])
+def test_crafted_world_on_the_device(hip, robots, beams):
+    """``orca_cases.device_world`` written into an open env whose ring heads differ (tests/controller_inject.py), up to 64
+    robots and through the lidar hash: the ties, touching discs (at twice the GROWN radius) and thresholds of the ORCA test, and
+    the situations of the host test's crafted solves -- free, at its goal, facing away, goal to the left / right, a wall
+    ahead, and the four pushed robots -- with the modes they are made for; all four modes occur.  Asserted from the fields read back."""
+    env = J.open_env(hip, robots, beams)
+    J.write_world(env, K.device_world(env.R, beams))
+    pose, speed_gt, goal, rows, hit = host_fields(env)
+    seen = set()
+    for p in K.nh_device_params():
+        modes, diags = check_equal(env, p)
+        grown = dict(p, radius=NR.derive(p)[3])
+        for w in range(env.W):
+            K.device_expectations(grown, w * env.R, beams, pose, speed_gt, goal, rows, hit, {n: d["free"] for n, d in diags.items()},
+                                  robots=env.R)
+            if p["jitter"] == 0.0:
+                K.nh_device_expectations(p, w * env.R, modes, diags)
+        seen |= set(modes.tolist())
+    assert seen == {NR.TRACK, NR.TURN, NR.STILL, NR.EVADE}, seen
+    check_equal(env, K.nh_device_params()[1], mask=(np.arange(env.N) % 3 != 1).astype(np.uint8))
     env.check()
     env.close()
 

@@ -1,7 +1,13 @@
 """GPU: mrca_orca_actions -- ``actions`` and ``vel`` EQUAL, bit for bit, to the NumPy float32 restatement of tests/orca_ref.py
 fed with host copies of the env's fields (small walled worlds with robots on one spot, a full wave of neighbours, a dense
 circle where LP3 decides, ring heads that differ, a mask); the call reads the env and writes nothing of it; 30 closed-loop
-ticks equal to the C oracle driven by the host build of the same rule; the error returns; ``mrca.evaluate --orca``."""
+ticks equal to the C oracle driven by the host build of the same rule; the error returns; ``mrca.evaluate --orca``.
+
+The crafted cases -- ties between neighbours and between beams, discs that touch, the thresholds of the rule -- live in
+tests/orca_cases.py, shared with tests/test_orca_host.py and tests/test_nhorca_host.py; tests/controller_inject.py puts them
+into an env as ONE world (poses and goals by reset, speed_gt, scan rows and hit flags through the field views), and
+``test_crafted_world_on_the_device`` asserts from the fields read back that each edge occurred.  tests/test_gpu_orca_big.py runs
+the same world with 66 robots through mrca_orca_actions_any."""
 import ctypes as C
 import json
 import os
@@ -121,6 +127,35 @@ def test_a_full_wave_of_neighbours(hip, max_neighbors):
     env.reset()
     diags = check_equal(env, R.params(max_neighbors=max_neighbors, neighbor_dist=20.0))
     assert max(len(d["branches"]) - d["n_static"] for d in diags.values()) == max_neighbors
+    env.close()
+
+
+def crafted_world_checks(env, beams):
+    """``orca_cases.device_world`` written into every world of ``env`` (tests/controller_inject.py) under every set of
+    ``device_params``: equal to the restatement, and each edge occurred -- asserted from the fields read back"""
+    import controller_inject as J
+    import orca_cases as K
+    J.write_world(env, K.device_world(env.R, beams))
+    pose, speed_gt, goal, rows, hit = host_fields(env)
+    for p in K.device_params():
+        diags = check_equal(env, p)
+        for w in range(env.W):
+            K.device_expectations(p, w * env.R, beams, pose, speed_gt, goal, rows, hit, diags, robots=env.R)
+    mask = (np.arange(env.N) % 3 != 1).astype(np.uint8)
+    check_equal(env, K.device_params()[1], mask=mask)
+    env.check()
+
+
+@pytest.mark.parametrize("beams", [64, 192, 1024])
+def test_crafted_world_on_the_device(hip, beams):
+    """Four neighbours at one distance and max_neighbors cutting through the tie, two robots on one spot, centres at exactly
+    2 * radius and one ulp either side, a robot exactly on its goal, speed_gt of 0, -0.0 and the speed limit; sector minima
+    that tie, empty sectors, a minimum that carries the hit-robot flag, a return at exactly obst_dist and one ulp below: two
+    open worlds of 34 robots whose ring heads differ."""
+    import controller_inject as J
+    import orca_cases as K
+    env = J.open_env(hip, K.N_CASES + 1, beams)
+    crafted_world_checks(env, beams)
     env.close()
 
 

@@ -2,16 +2,20 @@
 bit, to the NumPy float32 restatement of tests/orca_ref.py fed with host copies of the env's fields: at the threshold (65 and
 66 robots), on a 300-robot lattice where every robot's cells hold several chunks of candidates, after motion, with two worlds
 laid over each other in one hash, lazy and eager views, a mask after a sliced tick, in closed loop; the call writes nothing of
-the env; worlds of up to 64 robots get mrca_orca_actions' very bits; the error returns; ``mrca.evaluate --one-circle``."""
+the env; worlds of up to 64 robots get mrca_orca_actions' very bits; the error returns; ``mrca.evaluate --one-circle``.
+
+The crafted cases (tests/orca_cases.py, written into an env by tests/controller_inject.py) run here as a world of 66 robots:
+``test_crafted_world_of_66_robots``."""
 import ctypes as C
 
 import numpy as np
 import pytest
 import torch
 
+import controller_inject as J
 import orca_ref as R
 import util as U
-from test_gpu_orca import NAN_BITS, _evaluate, go_to_goal, host_fields, nan_filled, orca_params, small_scenario
+from test_gpu_orca import NAN_BITS, _evaluate, crafted_world_checks, go_to_goal, host_fields, nan_filled, orca_params, small_scenario
 from test_orca_big_host import lattice_poses, rule_robots
 from util import S
 
@@ -81,6 +85,14 @@ def test_the_threshold(hip, robots):
         diags = check_equal(env, p)
     assert max(len(d["branches"]) - d["n_static"] for d in diags.values()) >= 2      # (3.14 m apart: the neighbours on the circle)
     env.check()
+    env.close()
+
+
+def test_crafted_world_of_66_robots(hip):
+    """``orca_cases.device_world`` (tests/test_gpu_orca.py: ``crafted_world_checks``) with 66 robots a world: the same ties,
+    touching discs and thresholds with the neighbours found through the lidar hash"""
+    env = J.open_env(hip, 66, 192)
+    crafted_world_checks(env, 192)
     env.close()
 
 

@@ -10,7 +10,11 @@
   against mrca_hybrid_actions on the same state;
 * the closed loop plan -> act_fused(scan_scale) -> commit -> step against the host chain (safe_ref plan -> act_fused on a
   pre-scaled copy of the ring -> safe_ref commit) and the C oracle;
-* masks, in place, the arena untouched, a captured tick, the error returns, ``mrca.evaluate --hybrid-safe``."""
+* masks, in place, the arena untouched, a captured tick, the error returns, ``mrca.evaluate --hybrid-safe``.
+
+The crafted cases of plan and commit live in tests/hybrid_cases.py and tests/safe_cases.py, shared with the host tests
+(tests/test_hybrid_host.py, tests/test_safe_host.py); tests/controller_inject.py writes the plan's rows into an env, one case
+per robot, and the two tests "on the device" assert from what is read back that each case stood on its edge."""
 import ctypes as C
 import json
 import os
@@ -21,7 +25,10 @@ import numpy as np
 import pytest
 import torch
 
+import controller_inject as J
+import hybrid_cases as HK
 import hybrid_ref as R
+import safe_cases as K
 import safe_ref as SR
 import util as U
 from util import S
@@ -242,16 +249,20 @@ def sentinels(env):
     return mode, scale, pid, clear
 
 
-def check_plan(env, p, sp, mask=None, fields=None, with_clear=True):
+def check_plan(env, p, sp, mask=None, fields=None, with_clear=True, goal_dev=None):
     """One plan compared with safe_ref on the same fields, every robot, and with mrca_hybrid_actions on the same state
-    -> the reference's (mode, scale, pid, clear)."""
+    -> the reference's (mode, scale, pid, clear).  ``goal_dev``: a float32[N,2] tensor that goes in through
+    mrca_hybrid_plan_goal; the reference is then fed with a host copy of it in place of ``local_goal``."""
     goal, rows = fields or host_fields(env)
+    if goal_dev is not None:
+        goal = goal_dev.cpu().numpy()
     mode, scale, pid, clear = sentinels(env)
     m = None if mask is None else dev(np.ascontiguousarray(mask, np.uint8))
-    got = env.hybrid_plan(hybrid_params(p), safe_params(sp), mask=m, mode=mode, scale=scale, pid=pid, clear=clear if with_clear else None)
+    got = env.hybrid_plan(hybrid_params(p), safe_params(sp), mask=m, mode=mode, scale=scale, pid=pid, clear=clear if with_clear else None,
+                          goal=goal_dev)
     assert got[0] is mode and got[1] is scale and got[2] is pid
     hmode, hclear = torch.zeros_like(mode), torch.zeros_like(clear)
-    env.hybrid_actions(dev(seeded_commands(np.random.default_rng(0), env.N)), hybrid_params(p), mode=hmode, clear=hclear)
+    env.hybrid_actions(dev(seeded_commands(np.random.default_rng(0), env.N)), hybrid_params(p), mode=hmode, clear=hclear, goal=goal_dev)
     wmode, wscale, wpid, wclear = SR.plan(p, sp, goal, rows)
     sel = np.ones(env.N, bool) if mask is None else np.asarray(mask).astype(bool)
     torch.cuda.synchronize()
@@ -266,6 +277,71 @@ def check_plan(env, p, sp, mask=None, fields=None, with_clear=True):
     # exactly the mode and the clearances mrca_hybrid_actions reports on the same state
     assert np.array_equal(hmode.cpu().numpy(), wmode) and np.array_equal(bits(hclear.cpu().numpy()), bits(wclear))
     return wmode, wscale, wpid, wclear
+
+
+# ------------------------------------------------------------------------------------------------ the crafted cases, on the device
+@pytest.mark.parametrize("beams", [64, 192, 1024])
+def test_plan_on_the_crafted_rows_on_the_device(hip, beams):
+    """``hybrid_cases.device_cases`` (every edge of the rule on the env's own beam table, lone returns on the first and the last
+    lane of the first and the last round, all B beams blocking, ranges of 0.0 and -0.0) written into an env one case per robot
+    and planned: mode, scale, pid and clear, the scale on the edges of the risk rule; with and without a mask, and with the
+    goals handed to mrca_hybrid_plan_goal while ``local_goal`` holds something else.  That each row stood on its edge is
+    asserted from the fields read back."""
+    names, goal, policy, rows = HK.device_cases(beams)
+    env = J.walled_env(hip["env"], beams, len(names))
+    J.write_cases(env, 0, local_goal=goal, rows=rows)
+    assert J.heads_differ(env)
+    rng = np.random.default_rng(beams)
+    pol = seeded_commands(rng, env.N)
+    pol[:len(names)] = policy
+    p, sp = R.params(**HK.PARAMS), SR.params(**K.PLAN_SAFE)
+    goals = env.local_goal.clone()
+    for goal_dev in (None, goals):
+        if goal_dev is not None:
+            env.local_goal[:] = dev(rng.uniform(-5.0, 5.0, (env.N, 2)).astype(f32))
+        wmode, wscale, wpid, wclear = check_plan(env, p, sp, goal_dev=goal_dev)
+        back = host_fields(env)[1]
+        hact, hmode, hclear, nb = R.env_actions(p, goals.cpu().numpy(), pol, back)
+        HK.expectations(names, p, pol, back, hact, hmode, hclear, nb)
+        K.plan_expectations(names, sp, wmode, wscale, wpid, wclear, (hact, hmode, hclear))
+        check_plan(env, p, sp, mask=(np.arange(env.N) % 3 != 1).astype(np.uint8), goal_dev=goal_dev)
+        check_plan(env, R.params(), SR.params(), goal_dev=goal_dev)      # (the same rows off their edges, under the defaults)
+    env.check()
+    env.close()
+
+
+def test_commit_under_special_commands_in_every_mode_on_the_device(hip):
+    """``safe_cases.commit_cases`` (NaN, Inf, -0.0, v at the cap and one ulp either side, in every mode and in two that are
+    none) through mrca_hybrid_commit: out of place and in place, without a mask, under a mask and under its complement."""
+    mode, pid, policy = K.commit_cases()
+    n = len(mode)
+    env = hip["env"].VecStageWorld(J.small_walled_scenario(64, 1, n))     # (the commit reads nothing of the env but its size)
+    rng = np.random.default_rng(7)
+    N = env.N
+    mode = np.concatenate([mode, rng.integers(-2, 3, N - n).astype(np.int32)])
+    pid = np.concatenate([pid, seeded_commands(rng, N - n)])
+    policy = np.concatenate([policy, seeded_commands(rng, N - n)])
+    sp = SR.params(**K.COMMIT_SAFE)
+    ssp = safe_params(sp)
+    want = SR.commit(sp, mode, pid, policy)
+    K.commit_expectations(want[:n], pid[:n], policy[:n])                  # (the restatement stands on the edges ...)
+    nan_out = torch.full((N, 2), NAN_BITS, dtype=torch.int32, device=env.device).view(torch.float32)
+    dmode, dpid = dev(mode), dev(pid)
+    mask = (np.arange(N) % 3 != 1).astype(np.uint8)
+    out = env.hybrid_commit(dev(policy), dmode, dpid, ssp, out=nan_out.clone())
+    inpl = env.hybrid_commit(dev(policy), dmode, dpid, ssp)
+    part = env.hybrid_commit(dev(policy), dmode, dpid, ssp, mask=dev(mask), out=nan_out.clone())
+    both = env.hybrid_commit(dev(policy), dmode, dpid, ssp, mask=dev(1 - mask), out=part.clone())
+    part_in = env.hybrid_commit(dev(policy), dmode, dpid, ssp, mask=dev(mask))
+    torch.cuda.synchronize()
+    sel = mask.astype(bool)[:, None]
+    for got in (out, inpl, both):                                         # (... and the device equals it, bit for bit)
+        assert np.array_equal(bits(got.cpu().numpy()), bits(want)), np.argwhere(bits(got.cpu().numpy()) != bits(want))[:5]
+    K.commit_expectations(out.cpu().numpy()[:n], pid[:n], policy[:n])
+    assert np.array_equal(bits(part.cpu().numpy()), np.where(sel, bits(want), np.uint32(NAN_BITS)))
+    assert np.array_equal(bits(part_in.cpu().numpy()), np.where(sel, bits(want), bits(policy)))
+    env.check()
+    env.close()
 
 
 @pytest.mark.parametrize("lazy", [True, False])

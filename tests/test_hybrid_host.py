@@ -9,8 +9,10 @@ import subprocess
 import numpy as np
 import pytest
 
+import hybrid_cases as K
 import hybrid_ref as R
 import util as U
+from hybrid_cases import above, below, crafted_table  # noqa: F401  (the crafted rows live in tests/hybrid_cases.py)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "rl-collision-avoidance_amd", "csrc")
@@ -147,120 +149,25 @@ def test_random_inputs_equal_the_reference(shim, beams):
     assert seen == {R.AT_GOAL, R.NORMAL, R.SIMPLE, R.EMERGENT}
 
 
-def crafted_table(B=64):
-    """beam directions with three exact ones: beam 0 = (0, 1) (left), beam 1 = (1, 0) (ahead), beam 2 = (0, -1) (right); the rest
-    the env's own"""
-    bc, bs = beam_table(B)
-    bc, bs = bc.copy(), bs.copy()
-    bc[:3] = [0.0, 1.0, 0.0]
-    bs[:3] = [1.0, 0.0, -1.0]
-    return bc, bs
-
-
-def below(x):
-    return np.nextafter(f32(x), f32(-np.inf))
-
-
-def above(x):
-    return np.nextafter(f32(x), f32(np.inf))
-
-
 def test_crafted_inputs_stand_on_every_edge(shim):
+    """tests/hybrid_cases.py: ``crafted`` on its hand-made beam table, and what each of its rows is made for"""
     B = 64
     bc, bs = crafted_table(B)
-    open_row = np.full(B, 6.0, f32)
-    names, goals, cmds, rows = [], [], [], []
-
-    def add(name, goal, row, cmd=(0.75, -0.25)):
-        names.append(name)
-        goals.append(goal)
-        cmds.append(cmd)
-        rows.append(row)
-
-    def lone(beam, r):
-        row = open_row.copy()
-        row[beam] = f32(r)
-        return row
-    # (its own corridor, look and scale; risk_dist 0.4 so that a return on the corridor's edge, 0.45 m away, is not a risk)
-    p = R.params(risk_dist=0.4, stop_dist=0.3, safe_scale=0.5, corridor=0.45, look=4.0)
-    cor, risk, stop = p["corridor"], p["risk_dist"], p["stop_dist"]
-    add("goal_half_a_metre_ahead", (0.5, 0.0), lone(1, 0.2))
-    add("goal_just_outside", (float(above(0.5)), 0.0), open_row.copy())
-    add("all_ranges_6", (3.0, 1.0), open_row.copy())
-    add("edge_of_corridor_t0", (4.0, 0.0), lone(0, cor))                 # t = 0, |l| = corridor exactly: does not block
-    add("inside_corridor_t0", (4.0, 0.0), lone(0, below(cor)))           # t = 0, one ulp inside: blocks
-    add("inside_corridor_right_t0", (4.0, 0.0), lone(2, below(cor)))
-    add("at_reach", (2.0, 0.0), lone(1, 2.0))                            # t = reach = gl exactly: blocks
-    add("beyond_reach", (2.0, 0.0), lone(1, above(2.0)))
-    add("at_look", (5.5, 0.0), lone(1, 4.0))                             # t = reach = look exactly: blocks
-    add("beyond_look", (5.5, 0.0), lone(1, above(4.0)))
-    add("d_min_is_risk", (0.0, 3.0), lone(2, risk))                      # exactly risk_dist: not emergent
-    add("d_min_below_risk", (0.0, 3.0), lone(2, below(risk)))
-    add("d_front_at_stop", (3.0, 0.0), lone(1, stop))                    # s = 0
-    add("d_front_below_stop", (3.0, 0.0), lone(1, 0.1))                  # s would be negative: 0
-    add("d_front_between", (3.0, 0.0), lone(1, 0.325))                   # s = 0.25 (about)
-    add("risk_beside_front_open", (3.0, 0.0), lone(0, 0.35))             # d_front 6: s = safe_scale
-    row = open_row.copy()
-    row[1], row[5] = f32(-0.0), f32(0.0)
-    add("range_minus_0", (3.0, 0.0), row)
-    add("goal_straight_behind", (-3.0, 0.0), open_row.copy())
-    add("goal_behind_left", (-3.0, 1.0), open_row.copy())
-    add("goal_behind_right", (-3.0, -1.0), open_row.copy())
-    add("goal_ahead_left", (1.0, 0.05), open_row.copy())
-    blocked = lone(1, 1.0)
-    for k, cmd in (("nan", (np.nan, 0.5)), ("inf", (np.inf, -np.inf)), ("minus_0", (-0.0, -0.0)), ("nan_w", (0.5, np.nan))):
-        add("normal_" + k, (3.0, 0.0), blocked, cmd)
-        add("simple_" + k, (3.0, 0.0), open_row.copy(), cmd)
-        add("emergent_" + k, (3.0, 0.0), lone(1, 0.35), cmd)
-        add("at_goal_" + k, (0.1, 0.1), open_row.copy(), cmd)
-    goal, policy, rows = np.array(goals, f32), np.array(cmds, f32), np.stack(rows)
-    ix = {k: i for i, k in enumerate(names)}
+    names, goal, policy, rows = K.crafted(B)
+    p = R.params(**K.PARAMS)
     act, mode, clear, nb = assert_equal_to_ref(shim, p, goal, policy, rows, bc, bs)
+    K.expectations(names, p, policy, rows, act, mode, clear, nb)
 
-    def m(k):
-        return int(mode[ix[k]])
-    # 0.5 m is AT the goal (<=): (0, 0) whatever is near; the next float is not
-    assert m("goal_half_a_metre_ahead") == R.AT_GOAL and same_bits(act[ix["goal_half_a_metre_ahead"]], [0.0, 0.0])
-    assert same_bits(clear[ix["goal_half_a_metre_ahead"]], [0.2, 0.2, 6.0])
-    assert m("goal_just_outside") == R.SIMPLE
-    # nothing anywhere: the PID law, and every clearance is 6
-    i = ix["all_ranges_6"]
-    assert m("all_ranges_6") == R.SIMPLE and same_bits(clear[i], [6.0, 6.0, 6.0]) and act[i][0] > 0.9 and act[i][1] == 1.0
-    # the corridor's edge is outside it (strict), one ulp inside blocks; t = 0 is inside (>=)
-    assert nb[ix["edge_of_corridor_t0"]] == 0 and m("edge_of_corridor_t0") == R.SIMPLE
-    for k in ("inside_corridor_t0", "inside_corridor_right_t0"):
-        assert nb[ix[k]] == 1 and m(k) == R.NORMAL and same_bits(act[ix[k]], policy[ix[k]]) and clear[ix[k]][2] == below(cor)
-    # t = reach is inside (<=), whether the goal's distance or `look` ends the corridor
-    assert nb[ix["at_reach"]] == 1 and m("at_reach") == R.NORMAL and nb[ix["beyond_reach"]] == 0 and m("beyond_reach") == R.SIMPLE
-    assert nb[ix["at_look"]] == 1 and m("at_look") == R.NORMAL and nb[ix["beyond_look"]] == 0 and m("beyond_look") == R.SIMPLE
-    # d_min == risk_dist is not a risk (strict)
-    assert m("d_min_is_risk") == R.SIMPLE and m("d_min_below_risk") == R.EMERGENT
-    # the scale: 0 at and below stop_dist, in between in between, safe_scale where nothing is ahead; omega goes through
-    for k in ("d_front_at_stop", "d_front_below_stop"):
-        assert m(k) == R.EMERGENT and same_bits(act[ix[k]], [0.0, -0.25])
-    i = ix["d_front_between"]
-    assert m("d_front_between") == R.EMERGENT and 0.0 < act[i][0] < 0.75 * 0.5 and same_bits(act[i][1], -0.25)
-    i = ix["risk_beside_front_open"]
-    assert m("risk_beside_front_open") == R.EMERGENT and same_bits(act[i], [0.75 * 0.5, -0.25]) and same_bits(clear[i], [0.35, 6.0, 0.35])
-    # -0.0 is a 0: d_min is +0, the robot is in danger and stops
-    i = ix["range_minus_0"]
-    assert m("range_minus_0") == R.EMERGENT and same_bits(clear[i], [0.0, 0.0, 0.0]) and same_bits(act[i], [0.0, -0.25])
-    # a goal behind (fwd <= 0): stand and turn at full rate, to the left when the goal is straight behind or to the left
-    assert same_bits(act[ix["goal_straight_behind"]], [0.0, 1.0]) and same_bits(act[ix["goal_behind_left"]], [0.0, 1.0])
-    assert same_bits(act[ix["goal_behind_right"]], [0.0, -1.0])
-    assert all(m(k) == R.SIMPLE for k in ("goal_straight_behind", "goal_behind_left", "goal_behind_right", "goal_ahead_left"))
-    i = ix["goal_ahead_left"]
-    assert 0.99 < act[i][0] < 1.0 and 0.29 < act[i][1] < 0.31           # k_omega * uy = 6 * 0.05 (about)
-    # a NaN, an Inf or a -0.0 coming in: normal copies the bits, simple and at-goal do not look at them, emergent scales v
-    for k in ("nan", "inf", "minus_0", "nan_w"):
-        i = ix["normal_" + k]
-        assert m("normal_" + k) == R.NORMAL and np.array_equal(bits(act[i]), bits(policy[i]))
-        assert m("simple_" + k) == R.SIMPLE and same_bits(act[ix["simple_" + k]], [1.0, 0.0])
-        assert m("at_goal_" + k) == R.AT_GOAL and same_bits(act[ix["at_goal_" + k]], [0.0, 0.0])
-        i = ix["emergent_" + k]
-        assert m("emergent_" + k) == R.EMERGENT and np.array_equal(bits(act[i][1]), bits(policy[i][1]))
-    assert np.isnan(act[ix["emergent_nan"]][0]) and np.isinf(act[ix["emergent_inf"]][0])
-    assert same_bits(act[ix["emergent_minus_0"]], [-0.0, -0.0])
+
+@pytest.mark.parametrize("beams", [64, 192, 1024])
+def test_the_device_set_stands_on_every_edge(shim, beams):
+    """``device_cases``: the same edges rebuilt on the env's own beam table, which tests/test_gpu_hybrid.py writes into an env"""
+    names, goal, policy, rows = K.device_cases(beams)
+    p = R.params(**K.PARAMS)
+    act, mode, clear, nb = assert_equal_to_ref(shim, p, goal, policy, rows)
+    K.expectations(names, p, policy, rows, act, mode, clear, nb)
+    lone = [int(k.rsplit("_b", 1)[1]) for k in names if "_b" in k and k.rsplit("_b", 1)[1].isdigit()]
+    assert set(K.edge_beams(beams)) <= set(lone)
 
 
 def test_a_permutation_of_the_beams_changes_no_bit(shim):

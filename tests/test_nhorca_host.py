@@ -10,8 +10,10 @@ import numpy as np
 import pytest
 
 import nhorca_ref as NR
+import orca_cases as K
 import orca_ref as R
 import util as U
+from orca_cases import crafted_solves  # noqa: F401  (the crafted solves live in tests/orca_cases.py)
 from test_orca_host import CSRC, _fp, _ip, as_tuples, bits, line_sets, pack_hits, same_bits  # noqa: F401
 from util import S
 
@@ -159,24 +161,6 @@ def test_atan2_and_derived_values_equal_the_reference(nhshim):
                     assert (viol <= 1e-6) == ok, (h, T, vx, vy, viol)
 
 
-def crafted_solves():
-    """(what, lines without the heading lines, n_static, heading angle, o, mode expected or None)"""
-    vx_le_0 = (0.0, 0.0, 0.0, 1.0)                       # a static line: vx <= 0
-    vx_ge_02 = (0.2, 0.0, 0.0, -1.0)                     # a robot line: vx >= 0.2
-    return [
-        ("free", [], 0, 0.0, (1.0, 0.0), NR.TRACK),
-        ("at its goal", [], 0, 0.7, (0.0, 0.0), NR.STILL),
-        ("facing away", [], 0, np.pi, (1.0, 0.0), NR.TURN),
-        ("goal to the left", [], 0, 0.0, (0.0, 1.0), NR.TURN),
-        ("goal to the right", [], 0, 0.0, (0.3, -1.0), NR.TURN),
-        ("boxed in by a wall ahead", [vx_le_0], 1, 0.0, (1.0, 0.0), NR.STILL),
-        ("pushed forward while it should turn", [vx_ge_02], 0, 0.0, (0.0, 1.0), NR.EVADE),
-        ("pushed at its goal", [vx_ge_02], 0, 0.0, (0.0, 0.0), NR.TRACK),
-        ("pushed sideways at its goal", [(0.0, 0.2, 1.0, 0.0)], 0, 0.0, (0.0, 0.0), NR.EVADE),
-        ("wall ahead and a push", [vx_le_0, vx_ge_02], 1, 0.0, (1.0, 0.0), None),
-    ]
-
-
 def run_solve(nhshim, p, lines, ns, h, o):
     """one set of lines through the host build and through nhorca_ref, compared -> (mode, S2, diag)"""
     s, c = NR.sincos(h)
@@ -198,15 +182,7 @@ def test_crafted_cases_take_the_modes_they_are_made_for(nhshim):
         p = NR.params(track_error=eps, track_time=T)
         for what, lines, ns, h, o, want in crafted_solves():
             mode, s2, diag = run_solve(nhshim, p, lines, ns, h, o)
-            if want is None or T == 1.5:                 # (a cone of 1.5 rad holds some of the velocities that are outside the others)
-                continue
-            assert mode == want, (what, eps, T, mode, s2)
-            if what == "goal to the left":
-                assert diag["turn"] == 1.0
-            if what == "goal to the right":
-                assert diag["turn"] == -1.0
-            if what == "boxed in by a wall ahead":
-                assert R.violation(as_tuples(np.asarray(lines, f32))[0], s2[0], s2[1]) <= 1e-5
+            K.solve_expectations(what, want, T, mode, s2, diag, lines)
 
 
 def test_the_two_solves_equal_the_reference_on_random_lines(nhshim):
@@ -272,10 +248,7 @@ def test_equal_distances_and_a_full_list(nhshim):
     sc = S.circle_n(7, 3.0, grid=S.empty_grid())
     sc.beams, sc.frames = 64, 1
     env = U.COracleEnv(sc)
-    poses = np.asarray(sc.init_table, f32).copy()
-    poses[0, :2] = 0.0
-    poses[4, :2], poses[5, :2], poses[6, :2], poses[2, :2] = (1.0, 0.0), (-1.0, 0.0), (0.0, 1.0), (0.0, -1.0)
-    poses[3, :2] = poses[1, :2]
+    poses = K.equal_distance_poses(sc.init_table)
     env.reset(None, poses, np.asarray(sc.goal_table, f32))
     assert R.neighbours(env.pose[:, :2], 0, 6.0, 2) == [2, 4]
     for p in (NR.params(max_neighbors=2), NR.params(max_neighbors=1, jitter=0.0), NR.params(max_neighbors=NR.MAX_NEIGHBORS)):
@@ -285,6 +258,23 @@ def test_equal_distances_and_a_full_list(nhshim):
         assert same_bits(wact, act) and same_bits(wvel, vel) and np.array_equal(wmode, mode)
         assert counts[0, 0] == 2 + min(p["max_neighbors"], 6) and counts[0, 1] == 0
         MODES_SEEN.update(mode.tolist())
+
+
+@pytest.mark.parametrize("robots,beams", [(34, 64), (64, 192)])
+def test_the_device_world_takes_the_modes_it_is_made_for(nhshim, robots, beams):
+    """``orca_cases.device_world`` (which tests/test_gpu_nhorca.py puts into an env) through the whole rule: host build ==
+    restatement, the situations of ``crafted_solves`` it rebuilds take their modes, and all four modes occur"""
+    pose, speed_gt, goal, rows, hit = K.world_arrays(robots, beams)
+    seen = set()
+    for p in K.nh_device_params():
+        act, vel, mode, s1, _l, _c = host_env_actions(nhshim, p, robots, 5, pose, speed_gt, goal, rows, hit)
+        wact, wvel, wmode, wd = NR.env_actions(p, robots, 5, pose, speed_gt, goal, rows, hit)
+        assert same_bits(wact, act) and same_bits(wvel, vel) and np.array_equal(wmode, mode)
+        K.device_expectations(dict(p, radius=NR.derive(p)[3]), 0, beams, pose, speed_gt, goal, rows, hit, {n: d["free"] for n, d in wd.items()})
+        if p["jitter"] == 0.0:
+            K.nh_device_expectations(p, 0, wmode, wd)
+        seen |= set(wmode[:K.N_CASES].tolist())
+    assert seen == {NR.TRACK, NR.TURN, NR.STILL, NR.EVADE}, seen
 
 
 def test_every_mode_occurred():

@@ -10,6 +10,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import orca_cases as K
 import orca_ref as R
 import util as U
 from util import S
@@ -287,23 +288,7 @@ def test_lp3_keeps_static_lines_hard(shim):
 def test_sector_reduction_with_ties_and_empty_rows(shim):
     rng = np.random.default_rng(3)
     for B in (64, 192, 512, 1024):
-        rows = []
-        for kind in range(6):
-            r = rng.uniform(0.1, 6.0, B).astype(f32)
-            r[rng.random(B) < 0.3] = 6.0
-            hit = rng.random(B) < 0.3
-            if kind == 1:
-                r[:] = 6.0                                # nothing anywhere
-            if kind == 2:
-                r[:] = f32(1.25)                          # all equal: the lowest beam of every sector
-            if kind == 3:
-                hit[:] = True                             # only robots
-            if kind == 4:
-                per = B // 16
-                r[per:2 * per] = f32(2.0)
-                r[per + per // 2] = r[2 * per - 1] = f32(0.5)     # a tie inside sector 1
-                hit[per:2 * per] = False
-            rows.append((r, hit))
+        rows = K.sector_rows(rng, B)                      # (tests/orca_cases.py)
         for obst in (3.0, 6.0, 0.0):
             for r, hit in rows:
                 br, bb = np.zeros(16, f32), np.zeros(16, np.int32)
@@ -312,9 +297,7 @@ def test_sector_reduction_with_ties_and_empty_rows(shim):
                 want = R.sectors(r, hit, f32(obst))
                 assert [b for _r, b in want] == bb.tolist()
                 assert all(b < 0 or same_bits(wr, br[s]) for s, (wr, b) in enumerate(want))
-    r, hit = rows[4]
-    assert R.sectors(r, hit, f32(3.0))[1][1] == B // 16 + B // 32          # the tie went to the lower beam
-    assert all(b < 0 for _r, b in R.sectors(rows[1][0], rows[1][1], f32(6.0)))      # a row of 6.0 gives nothing, even at 6
+    K.sector_expectations(rows, B)                        # the tie went to the lower beam; a row of 6.0 gives nothing
 
 
 def test_neighbour_ranking_with_equal_distances(shim):
@@ -322,25 +305,19 @@ def test_neighbour_ranking_with_equal_distances(shim):
     for Rn in (1, 2, 7, 33, 64):
         xy = rng.uniform(-5, 5, (Rn, 2)).astype(f32)
         if Rn >= 7:
-            xy[3] = xy[1]                                 # two on one spot
-            xy[4] = (xy[0][0] + f32(1.0), xy[0][1])       # equal distances from robot 0, four ways
-            xy[5] = (xy[0][0] - f32(1.0), xy[0][1])
-            xy[6] = (xy[0][0], xy[0][1] + f32(1.0))
-            xy[2] = (xy[0][0], xy[0][1] - f32(1.0))
+            K.place_ties(xy)                              # two on one spot; equal distances from robot 0, four ways
         for local in range(0, Rn, max(1, Rn // 5)):
             for maxn, nd in [(10, 6.0), (48, 6.0), (3, 100.0), (0, 6.0), (48, 0.5)]:
                 out = np.full(48, -1, np.int32)
                 n = shim.shim_neighbours(_fp(xy), Rn, local, nd, maxn, _ip(out))
                 want = R.neighbours(xy, local, nd, maxn)
                 assert out[:n].tolist() == want, (Rn, local, maxn, nd)
-    order = [j for j in R.neighbours(xy, 0, 6.0, 48) if j in (2, 4, 5, 6)]
-    assert order == [2, 4, 5, 6]                          # equal distances: by index
+    K.tie_expectations(xy)                                # equal distances: by index
 
 
 def test_command_mapping_and_preferred_velocity(shim):
     rng = np.random.default_rng(9)
-    cases = [(0.0, 0.0, 0.0, 1.0), (5e-5, 5e-5, 0.0, 1.0), (0.5, 0.0, 0.0, 1.0), (-0.5, 0.0, 0.0, 1.0), (-0.5, 1e-3, 0.0, 1.0),
-             (-0.5, -1e-3, 0.0, 1.0), (0.0, 0.7, 0.0, 1.0), (0.0, -0.7, 0.0, 1.0), (2.0, 0.1, 0.0, 1.0), (0.3, 0.3, 1.0, 0.0)]
+    cases = list(K.COMMAND_CASES)
     for _ in range(200):
         th = rng.uniform(-np.pi, np.pi)
         cases.append((*rng.uniform(-1.2, 1.2, 2), np.sin(th), np.cos(th)))
@@ -355,7 +332,7 @@ def test_command_mapping_and_preferred_velocity(shim):
             assert 0.0 <= out[0] <= ms and -1.0 <= out[1] <= 1.0
             fwd, lat = f32(c) * f32(vx) + f32(s) * f32(vy), f32(c) * f32(vy) - f32(s) * f32(vx)
             kinds.add("still" if np.hypot(vx, vy) < 1e-4 else ("back" if fwd <= 0 else ("straight" if lat == 0 else "turn")))
-    assert kinds == {"still", "back", "straight", "turn"}
+    assert kinds == K.COMMAND_KINDS
     for jitter in (0.0, 0.1, 0.5):
         q = R.params(jitter=jitter, v_pref=0.8)
         cq = cparams(q)
@@ -370,6 +347,18 @@ def test_command_mapping_and_preferred_velocity(shim):
     q0 = cparams(R.params(v_pref=1.0))
     shim.shim_pref(C.byref(q0), 3, 1, 2, 0, 0, 3, 4, _fp(out))
     assert same_bits(out, [f32(3.0) / f32(5.0), f32(4.0) / f32(5.0)])       # jitter 0: no rotation at all
+
+
+@pytest.mark.parametrize("robots,beams", [(34, 64), (34, 192), (64, 1024)])
+def test_the_device_world_stands_on_every_edge(shim, robots, beams):
+    """``orca_cases.device_world`` -- the crafted inputs above as ONE world, which tests/test_gpu_orca.py and
+    tests/test_gpu_orca_big.py put into an env -- through the whole rule: host build == restatement, and every edge occurs"""
+    pose, speed_gt, goal, rows, hit = K.world_arrays(robots, beams)
+    for p in K.device_params():
+        act, vel, _d, _l, _c = host_env_actions(shim, p, robots, 5, pose, speed_gt, goal, rows, hit)
+        wact, wvel, diags = R.env_actions(p, robots, 5, pose, speed_gt, goal, rows, hit)
+        assert same_bits(wact, act) and same_bits(wvel, vel)
+        K.device_expectations(p, 0, beams, pose, speed_gt, goal, rows, hit, diags)
 
 
 # ------------------------------------------------------------------------------------------------ closed loop on the C oracle

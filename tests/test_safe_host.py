@@ -10,7 +10,9 @@ import subprocess
 import numpy as np
 import pytest
 
+import hybrid_cases as HK
 import hybrid_ref as R
+import safe_cases as K
 import safe_ref as SR
 import util as U
 from test_hybrid_host import PARAM_SETS, Params, beam_table, bits, cparams, random_inputs, same_bits
@@ -132,61 +134,43 @@ def test_plan_on_random_rows_equals_the_reference_and_the_existing_rule(shim, be
     assert seen == {R.AT_GOAL, R.NORMAL, R.SIMPLE, R.EMERGENT}
 
 
+# ------------------------------------------------------------------------------------------------ the plan on the crafted rows
+@pytest.mark.parametrize("which,beams", [("host", 64), ("device", 64), ("device", 192), ("device", 1024)])
+def test_plan_on_the_crafted_rows(shim, which, beams):
+    """tests/hybrid_cases.py through the plan: the host set on its hand-made beam table, the device set (which
+    tests/test_gpu_safe_policy.py writes into an env) on the env's own"""
+    names, goal, policy, rows = HK.crafted(beams) if which == "host" else HK.device_cases(beams)
+    bc, bs = HK.crafted_table(beams) if which == "host" else beam_table(beams)
+    p, sp = R.params(**HK.PARAMS), SR.params(**K.PLAN_SAFE)
+    mode, scale, pid, clear = host_plan(shim, p, sp, goal, rows, bc, bs)
+    wmode, wscale, wpid, wclear = SR.plan(p, sp, goal, rows, bc, bs)
+    assert np.array_equal(mode, wmode) and same_bits(scale, wscale) and same_bits(pid, wpid) and same_bits(clear, wclear)
+    hact, hmode, hclear, nb = R.env_actions(p, goal, policy, rows, bc, bs)
+    HK.expectations(names, p, policy, rows, hact, hmode, hclear, nb)
+    K.plan_expectations(names, sp, wmode, wscale, wpid, wclear, (hact, hmode, hclear))
+
+
 # ------------------------------------------------------------------------------------------------ the commit
-def below(x):
-    return np.nextafter(f32(x), f32(-np.inf))
-
-
-def above(x):
-    return np.nextafter(f32(x), f32(np.inf))
-
-
 def test_commit_under_special_commands_in_every_mode(shim):
-    sp = SR.params(scan_scale=0.7, v_cap=0.3)
-    cap = sp["v_cap"]
-    cmds = [(np.nan, 0.5), (np.inf, -np.inf), (-np.inf, np.inf), (-0.0, -0.0), (0.5, np.nan), (float(cap), 0.25),
-            (float(below(cap)), 0.25), (float(above(cap)), 0.25), (0.0, 0.0), (1.0, -1.0)]
-    modes = [R.NORMAL, R.SIMPLE, R.EMERGENT, R.AT_GOAL, 7, -1]          # (7, -1: no mode of the rule -- the command is copied)
-    mode = np.repeat(np.array(modes, np.int32), len(cmds))
-    policy = np.tile(np.array(cmds, f32), (len(modes), 1))
-    pid = np.tile(np.array([[0.625, -0.125]], f32), (len(mode), 1))
-    pid[len(cmds) + 3] = (-0.0, np.nan)                                               # whatever pid holds is what modes 1 and -2 give
+    sp = SR.params(**K.COMMIT_SAFE)
+    mode, pid, policy = K.commit_cases()
     want = SR.commit(sp, mode, pid, policy)
     for in_place in (False, True):
         got = host_commit(shim, sp, mode, pid, policy, in_place)
         assert np.array_equal(bits(got), bits(want)), np.argwhere(bits(got) != bits(want))[:5]
-    got = got.reshape(len(modes), len(cmds), 2)
-    pol = policy.reshape(len(modes), len(cmds), 2)
-    # stated from the rule, not from the restatement:
-    for i in (0, 4, 5):                                                   # copied bit for bit
-        assert np.array_equal(bits(got[i]), bits(pol[i]))
-    for i in (1, 3):                                                      # the pid, whatever comes in
-        assert np.array_equal(bits(got[i]), bits(pid.reshape(len(modes), len(cmds), 2)[i]))
-    e = got[2]
-    assert np.array_equal(bits(e[:, 1]), bits(pol[2][:, 1]))              # omega is kept in mode 2, a NaN included
-    assert np.isnan(e[0, 0]) and same_bits(e[1, 0], cap) and np.isneginf(e[2, 0]) and same_bits(e[3, 0], -0.0)
-    assert same_bits(e[5, 0], cap) and same_bits(e[6, 0], below(cap)) and same_bits(e[7, 0], cap)      # at, below, above the cap
-    assert same_bits(e[9, 0], cap) and same_bits(e[8, 0], 0.0)
+    K.commit_expectations(got, pid, policy)
 
 
 # ------------------------------------------------------------------------------------------------ the scale rule
 def test_the_scale_rule_on_its_edges(shim):
-    six = f32(6.0)
-    x = np.array([0.0, -0.0, 6.0, np.nextafter(six, f32(0.0)), np.nextafter(six, f32(7.0)), 1.0, 0.1, 5.999, 3.0000002, 2.0 ** -126,
-                  np.inf, 7.5], f32)
     rng = np.random.default_rng(4)
-    x = np.concatenate([x, rng.uniform(0.0, 6.0, 4096).astype(f32)])
-    for s in (0.7, 0.8, 0.5, 1.0, 2.0 ** -20, float(np.nextafter(f32(1.0), f32(0.0)))):
+    x = np.concatenate([K.SCALE_EDGES, rng.uniform(0.0, 6.0, 4096).astype(f32)])
+    for s in K.SCALE_FACTORS:
         out = np.zeros_like(x)
         shim.shim_scale(len(x), _fp(x), f32(s), _fp(out))
         want = SR.scaled_range(x, s)
         assert np.array_equal(bits(out), bits(want)), (s, np.argwhere(bits(out) != bits(want))[:5])
-        assert same_bits(out[0], 0.0) and same_bits(out[2], 6.0)         # 0 stays 0; "nothing" stays nothing
-        assert same_bits(out[1], -0.0)                                    # (the front ends fold the sign BEFORE the rule: |x|)
-        assert same_bits(out[3], f32(x[3]) * f32(s)) and out[3] < six   # the last float below 6 is a return: scaled, below 6
-        assert same_bits(out[4], x[4]) and same_bits(out[10], np.inf) and same_bits(out[11], 7.5)      # beyond the range: kept
-        if s == 1.0:
-            assert np.array_equal(bits(out), bits(x))                     # ones are the identity
+        K.scale_expectations(x, s, out)
     # 0.7 is no dyadic rational: the product is rounded, once, as float32 rounds it
     assert same_bits(SR.scaled_range(f32(0.1), 0.7), f32(0.1) * f32(0.7)) and float(f32(0.1) * f32(0.7)) != float(f32(0.1)) * float(f32(0.7))
     # the ring form: |x| first, all three frames by the robot's factor
